@@ -6,7 +6,7 @@ halo2-snark-aggregator-api/src/mock/arith/ecc.rs:106-129) over synthetic inputs 
 resident in HBM: bases P_i = k_i*G (Montgomery affine table built on the GPU), scalars s_i canonical
 32-byte integers, both derived from a seeded PRNG, so the expected result (sum k_i s_i)*G is known.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 20]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2n 20] [--dump-outputs DIR]
 
 N > 1: launched by torch.distributed.run, one rank per GPU.  Independent proofs shard one-per-GPU (each
 rank runs its own MSMs: weak scaling, no data-path collective), then the per-rank accumulators are
@@ -45,6 +45,28 @@ def gen_scalars(seed: int, n: int):
     vals = [int.from_bytes(raw[64 * i:64 * i + 64], "little") % R_MOD for i in range(n)]
     buf = b"".join(v.to_bytes(32, "little") for v in vals)
     return vals, np.frombuffer(buf, dtype=np.uint8).reshape(n, 32)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def affine_array(aff: bytes) -> np.ndarray:
+    """canonical affine points (64 B each: x then y, 32-byte little-endian integers) -> float32 [points, 2, 32] of their
+    bytes, exact in float32: the form --dump-outputs writes, so two builds compare point for point"""
+    return np.frombuffer(aff, dtype=np.uint8).reshape(-1, 2, 32).astype(np.float32)
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: arrays -> out_dir/<name>.npy (float32 / float64 only, at most DUMP_LIMIT_BYTES in all)"""
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("%s: dumped outputs are float32 or float64, not %s" % (name, a.dtype))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("dumped outputs would take %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(bases_aff: bytes, scalars: bytes, sample: int):
@@ -857,7 +879,12 @@ def main():
                     help="1: also run BASELINE.json configs[4]'s per-GPU share (16 proofs x 2^22-point instance MSMs); 0: skip")
     ap.add_argument("--agg-instance-log2", type=int, default=17,
                     help="k of the per-proof instance-column commitment MSM (2^k - 6 scalars); 0 = leave it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's MSM result (and with N > 1 the folded sum over the "
+                         "ranks) to DIR/<name>.npy as canonical affine x, y bytes in float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -994,6 +1021,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     eng.profile_enable(False)
+    timed_out = bytes(d_out[:args.steps].cpu().numpy().tobytes())    # the K timed outputs, before the power sample reuses d_out
 
     # ---- what the package draws while the same MSMs run back to back (untimed, behind the timed region): the step is
     # power-bound, and the judge of the roofline fraction should see that from this run, not from a document
@@ -1002,13 +1030,18 @@ def main():
         power = sample_power(lambda: [step(i % d_out.shape[0]) for i in range(60)], eng.synchronize, dev.index or 0)
 
     # every one of the K timed outputs, not only the first: all steps ran the same MSM, all must hold the checked result
-    outs_aff = eng.g1_batch_to_affine(bytes(d_out[:max(args.steps, 1)].cpu().numpy().tobytes()))
+    outs_aff = eng.g1_batch_to_affine(timed_out)
     if any(outs_aff[64 * i:64 * i + 64] != want for i in range(args.steps)):
         raise SystemExit("rank %d: a timed step's output differs from (sum k_i s_i)*G — refusing to report a number" % rank)
     folded_ok = True
     if gathered is not None:
         folded = eng.g1_sum(bytes(gathered.cpu().numpy().tobytes()))     # W = sum of per-rank accumulators
         folded_ok = len(folded) == 96
+    if args.dump_outputs and rank == 0:
+        arrays = {"msm_result_affine": affine_array(outs_aff[64 * (args.steps - 1):])}
+        if gathered is not None:
+            arrays["msm_folded_affine"] = affine_array(eng.g1_batch_to_affine(folded))
+        dump_outputs(args.dump_outputs, arrays)
 
     t_all = torch.tensor([dt, dt_cold], dtype=torch.float64, device=coll_dev)
     if dist is not None:

@@ -1,7 +1,7 @@
 """Offline differential run of the schema path (random ASTs, tests/test_gpu_schema.py::test_random_schema_trees_vs_oracle)
 over many seeds; not collected by pytest.  795 seeds clean in 150 s on the GPU box."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as entry
 import tests.test_gpu_schema as T
 pkg = entry.load_package(); eng = pkg.H2Agg(0)

@@ -80,3 +80,21 @@ def test_a_launch_that_does_not_match_gpus_is_refused():
                         "--master-port", str(free_port()), "bench.py", "--gpus", "4", "--agg-proofs", "0"] + COMMON,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode != 0 and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_holds_the_last_timed_result(tmp_path):
+    """--dump-outputs DIR: the last timed step's MSM result, (sum k_i s_i) * G for bench.py's seeded inputs, as affine bytes"""
+    import numpy as np
+    import bench
+    from oracle import bn254 as O
+    line = run([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "0", "--no-power-sample", "--dump-outputs", str(tmp_path)]
+               + COMMON, dict(os.environ))
+    assert line["steps"] == 2
+    assert sorted(os.listdir(tmp_path)) == ["msm_result_affine.npy"]
+    got = np.load(str(tmp_path / "msm_result_affine.npy"))
+    assert got.dtype == np.float32 and got.shape == (1, 2, 32)
+    seed, n = 0x48324147, 1 << 16                       # bench.py's rank-0 inputs at --log2n 16
+    ks, _ = bench.gen_scalars(seed, n)
+    ss, _ = bench.gen_scalars(seed + 1, n)
+    want = O.aff_to_bytes(O.scalar_mul(sum(k * s for k, s in zip(ks, ss)) % O.R, O.G1))
+    assert got.astype(np.uint8).tobytes() == want

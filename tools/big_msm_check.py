@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import __graft_entry__ as entry
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
