@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libh2agg.so")
@@ -83,6 +83,7 @@ def load_library():
         "h2agg_g1_batch_compress": (i32, [ctxp, u8p, sz, vp]),
         "h2agg_g1_msm": (i32, [ctxp, vp, vp, sz, vp]),
         "h2agg_g1_msm_jac": (i32, [ctxp, vp, vp, sz, vp]),
+        "h2agg_g1_msm_segmented": (i32, [ctxp, vp, vp, sz, C.POINTER(u64), sz, vp]),
         "h2agg_host_alloc": (i32, [ctxp, sz, C.POINTER(vp)]),
         "h2agg_host_free": (i32, [ctxp, vp]),
         "h2agg_eval_flat": (i32, [ctxp, u8p, u8p, u8p, sz, vp]),
@@ -126,6 +127,7 @@ def load_library():
         "h2agg_verify_aggregation_ex": (i32, [ctxp, vp, sz, u8p, u8p, vp, vp, vp, C.POINTER(i32), vp, sz]),
         "h2agg_verify_aggregation_sharded": (i32, [ctxp, vp, sz, vp, u8p, u8p, vp, vp, vp, C.POINTER(i32), vp, sz]),   # see verifier.py
         "h2agg_debug_configure": (i32, [ctxp, C.c_char_p, i32]),
+        "h2agg_verify_proofs": (i32, [ctxp, vp, sz, u8p, u8p, vp, vp, C.POINTER(C.c_int32), C.POINTER(i32), vp, sz]),
         "h2agg_verify_plan_stats": (i32, [ctxp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "h2agg_last_phases": (C.c_char_p, [ctxp]),
         "h2agg_transcript_configure": (i32, [ctxp, i32]),
@@ -352,6 +354,22 @@ class H2Agg:
         out = C.create_string_buffer(96)
         self._check(self._lib.h2agg_g1_msm_jac(self._ctx, C.cast(points_jac, C.c_void_p), C.cast(scalars, C.c_void_p), n, out))
         return out.raw
+
+    def g1_msm_segmented(self, bases_aff: bytes, scalars: bytes, seg_lens: Sequence[int]) -> List[bytes]:
+        """h2agg_g1_msm_segmented: one multi_exp per segment of seg_lens[s] consecutive (base, scalar) pairs, one set of
+        device launches for all of them -> a 96-byte Jacobian result per segment"""
+        n = len(scalars) // 32
+        _need(scalars, 32 * n, "scalars")
+        _need(bases_aff, 64 * n, "bases_aff")
+        starts = [0]
+        for ln in seg_lens:
+            starts.append(starts[-1] + int(ln))
+        nseg = len(seg_lens)
+        seg = (C.c_uint64 * len(starts))(*starts)
+        out = C.create_string_buffer(96 * max(nseg, 1))
+        self._check(self._lib.h2agg_g1_msm_segmented(self._ctx, C.cast(bases_aff, C.c_void_p), C.cast(scalars, C.c_void_p), n,
+                                                     seg, nseg, out))
+        return [out.raw[96 * s: 96 * (s + 1)] for s in range(nseg)]
 
     def host_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()

@@ -28,6 +28,7 @@
 
 #include "scalar_mul_kernels.hpp"
 #include "lp_kernels.hpp"
+#include "seg_msm_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -167,6 +168,8 @@ struct h2agg_ctx {
 
     // h2agg_debug_configure: test hooks read per call (chained host-buffer slices, comb route, plan cache)
     int dbg_pcie_slices = 0, dbg_pcie_glv = 0, dbg_pcie_chain = 1, dbg_comb_msm = 1, dbg_plan_cache = 1, dbg_small_sort = 1, dbg_eval_split = 1, dbg_pre_big = 0, dbg_lean_acc = 1, dbg_shard_fail = 0, dbg_shard_calls = 0, dbg_phases = 0, dbg_tape_lds = 1, dbg_prewake = 1;
+    int dbg_seg_chunk = 0, dbg_seg_c = 0;   // segmented multi_exp: points per set of launches (0 = automatic), window bits (0 = default)
+    DevBuf seg_wsum, seg_dev, seg_out;      // segmented multi_exp: window sums, segment offsets, results (csrc/seg_msm.inc)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -1327,7 +1330,8 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->offs[0], &c->offs[1], &c->pmeta[0], &c->pmeta[1], &c->item_idx, &c->item_sub, &c->order[0], &c->order[1], &c->entries[0], &c->entries[1],
                       &c->r2d_ticket[0], &c->r2d_ticket[1], &c->r2d_ticket[2], &c->buckets[0], &c->buckets[1], &c->buckets[2], &c->segsum[0], &c->segsum[1], &c->segsum[2],
                       &c->wsum[0], &c->wsum[1], &c->wsum[2], &c->big_list[0], &c->big_list[1], &c->big_keys[0], &c->big_keys[1], &c->big_part[0], &c->big_part[1], &c->fix_list[0], &c->fix_list[1], &c->glv_buf, &c->parts, &c->small, &c->endo_buf, &c->tile_counts, &c->fb_long,
-                      &c->sch_regs, &c->sch_in, &c->sch_scalars[0], &c->sch_scalars[1], &c->sch_bases[0], &c->sch_bases[1], &c->sch_endo};
+                      &c->sch_regs, &c->sch_in, &c->sch_scalars[0], &c->sch_scalars[1], &c->sch_bases[0], &c->sch_bases[1], &c->sch_endo,
+                      &c->seg_wsum, &c->seg_dev, &c->seg_out};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -2305,6 +2309,11 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
     }       // 0: every Fr tape through k_tape_run (register file in L2) instead of the LDS one
     else if (k == "prewake") c->dbg_prewake = value;         // 0: the sponge workers sleep until their chains are posted (A/B of the pre-wake)
     else if (k == "phases") c->dbg_phases = value;           // 1: every h2agg_verify_aggregation* call keeps its wall-clock split for h2agg_last_phases
+    else if (k == "seg_chunk") c->dbg_seg_chunk = value;     // segmented multi_exp: at most n points per set of launches (0 = automatic)
+    else if (k == "seg_c") {                                 // segmented multi_exp: window bits 4 .. 8 (0 = default)
+        if (value != 0 && (value < 4 || value > 8)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: seg_c must be 0 or 4 .. 8");
+        c->dbg_seg_c = value;
+    }
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
     return H2AGG_OK;
@@ -2513,5 +2522,6 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 
 #include "schema_api.inc"
 #include "transcript.inc"
+#include "seg_msm.inc"
 #include "comm.inc"
 #include "verifier.inc"

@@ -773,9 +773,17 @@ extern "C" {
 // (canonical affine) — the fourth return value of verify_aggregation_proofs_in_chip (`commits`, verify.rs:852-856,927-939),
 // which the production caller feeds to `coherent` (halo2-snark-aggregator-circuit/src/verify_circuit.rs:487-492).
 // advice_cap: bytes available; too small -> H2AGG_ERR_INVALID before any work.
+// each (h2agg_verify_proofs): no aggregation challenge and no fold — every proof's own (left, right) to each->pairs (128 B per
+// proof of this call, in its order), a proof whose W count does not fit its rotation groups gets H2AGG_ERR_INVALID in
+// each->status and is left out; left_aff / right_aff, lambda_out, s_g2 are not used.  The recording is never cached.
+struct EachOut {
+    uint8_t* pairs;
+    int32_t* status;
+};
 static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* circuits, size_t ncircuits, const h2agg_shard* shard,
                                    const uint8_t* s_g2, const uint8_t* g2, uint8_t left_aff[64], uint8_t right_aff[64],
-                                   uint8_t lambda_out[32], int* pairing_ok, uint8_t* advice_out, size_t advice_cap) try {
+                                   uint8_t lambda_out[32], int* pairing_ok, uint8_t* advice_out, size_t advice_cap,
+                                   EachOut* each = nullptr) try {
     TRY(bind(c));
     if (!circuits || ncircuits == 0 || !left_aff || !right_aff) return fail(c, H2AGG_ERR_INVALID, "null argument");
     if ((s_g2 == nullptr) != (g2 == nullptr) || (s_g2 && !pairing_ok))
@@ -1112,6 +1120,8 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
             if (h.inst_aff.size() > 1) memcpy(h.inst_aff.data(), c->h_down + late.off_inst, h.inst_aff.size() - 1);
             trace.mark("points_down");
         }
+    } else if (each) {
+        TRY(finish(c));   // every transcript has run: bad point encodings / non-canonical scalars surface here
     } else if (!shard) {
         uint32_t upto = (uint32_t)total_proofs;
         TRY(ensure(c, c->tr_in, 256));
@@ -1127,7 +1137,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         TRY(finish(c));   // (sharded, device sponges: lambda follows the exchange further down)
     }
     // ---- a recording of this shape from an earlier call?
-    const bool cache_on = c->dbg_plan_cache != 0;   // (h2agg_debug_configure "plan_cache" 0: record every call afresh)
+    const bool cache_on = c->dbg_plan_cache != 0 && !each;   // (h2agg_debug_configure "plan_cache" 0: record every call afresh)
     std::string sig;
     for (size_t ci = 0; ci < ncircuits; ++ci) {
         char buf[96];
@@ -1147,6 +1157,8 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
             if (pl.sig == sig) plan = &pl;
     AggPlan fresh;
     h2agg_schema* sc = nullptr;
+    std::vector<std::pair<uint32_t, uint32_t>> each_roots;   // each: (w_x, w_g) of every proof that has them ...
+    std::vector<size_t> each_idx;                            // ... and its place in the call
     if (plan) {
         sc = plan->sc;
         plan->stamp = ++c->agg_plans->clock;
@@ -1167,6 +1179,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
     Rec R(S);
     std::vector<AggPlan::ChalPatch>& patches = fresh.chal;
     std::vector<std::pair<uint32_t, uint32_t>> proofs;   // (w_x, w_g) per proof, in aggregation order
+    each_idx.clear();
     for (size_t ci = 0; ci < ncircuits; ++ci) {
         const h2agg_circuit_proofs& cp = circuits[ci];
         const h2agg_vk& vk = *cp.vk;
@@ -1243,12 +1256,21 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
             }
             const uint8_t* w = pts + 64 * (h.npoints - h.n_w);
             uint32_t w_x = 0, w_g = 0;
-            if (!S.batch_multi_open_regs(key.c_str(), qs.size(), rot.data(), preg.data(), qnode.data(), h.n_w, w, P.v, P.u, w_x, w_g))
-                return fail(c, H2AGG_ERR_INVALID, S.err);
+            if (!S.batch_multi_open_regs(key.c_str(), qs.size(), rot.data(), preg.data(), qnode.data(), h.n_w, w, P.v, P.u, w_x, w_g)) {
+                if (!each) return fail(c, H2AGG_ERR_INVALID, S.err);
+                each->status[h.first_proof + i] = H2AGG_ERR_INVALID;   // (this proof only: the others go on)
+                continue;
+            }
             proofs.push_back({w_x, w_g});
+            if (each) each_idx.push_back(h.first_proof + i);
         }
     }
     trace.mark("host_queries");
+    if (each) {
+        each_roots = proofs;
+        fresh.sc = sc;
+        plan = &fresh;
+    } else {
     // ---- acc = acc * lambda + proof  (verify.rs:926-938)
     // Recorded in its distributed form  sum_i lambda^(N-1-i) * proof_i  (what the nested fold expands to; field arithmetic is
     // exact, the entries keep the fold's order): every proof's entries meet ONE factor, lambda^e built by halving, instead of
@@ -1307,6 +1329,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
     fresh.acc_x = acc_x;
     fresh.acc_g = acc_g;
     plan = &fresh;
+    }   // (aggregation)
     }   // (recorded afresh)
     Schema& S = sc->s;
     const uint32_t lam_reg = plan->lam_reg, acc_x = plan->acc_x, acc_g = plan->acc_g;
@@ -1319,7 +1342,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         }
         const uint32_t upto = (uint32_t)total_proofs;
         host_flags |= sponge_bad.load();
-        if (!shard) host_flags |= poseidon_run_host(agg_host.data(), 32 * total_proofs, &upto, 1, 1, lambda, 1);
+        if (!shard && !each) host_flags |= poseidon_run_host(agg_host.data(), 32 * total_proofs, &upto, 1, 1, lambda, 1);
         trace.mark("sponge_wait");
         TRY(finish(c, host_flags));   // every transcript has run: bad point encodings / non-canonical scalars surface here
     }
@@ -1335,8 +1358,16 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         trace.mark("lambda_exchange");
         if (c->dbg_shard_fail == 2) return fail(c, H2AGG_ERR_INVALID, "injected failure between the exchanges (debug key shard_fail)");
     }
-    if (lambda_out) memcpy(lambda_out, lambda, 32);
     for (const AggPlan::ChalPatch& pt : plan->chal) S.tape.set_const(pt.reg, H[pt.circuit].chal.data() + pt.off);
+    if (each) {   // verify_single_proof_in_chip: every proof's own evaluate_multiopen_proof, 2N sides in one set of launches
+        if (each_roots.empty()) return H2AGG_OK;
+        std::vector<uint8_t> pairs(128 * each_roots.size());
+        TRY(evaluate_multiopen_many(sc, each_roots, pairs.data()));
+        for (size_t k = 0; k < each_idx.size(); ++k) memcpy(each->pairs + 128 * each_idx[k], pairs.data() + 128 * k, 128);
+        trace.mark("evaluate");
+        return H2AGG_OK;
+    }
+    if (lambda_out) memcpy(lambda_out, lambda, 32);
     S.tape.set_const(lam_reg, lambda);
     // (the pairing behind the evaluation wants one worker awake: its second pair's Miller loop runs there)
     if (s_g2 && !shard && c->dbg_prewake) HostPool::get().prewake(1);
@@ -1392,6 +1423,222 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         c->err = why;
     }
     return rc;
+} catch (const std::bad_alloc&) {
+    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
+} catch (...) {
+    return H2AGG_ERR_INVALID;
+}
+
+}  // extern "C"
+
+namespace {
+// e(left_i, s_g2) * e(right_i, -g2) == 1 for every proof whose status is OK, one proof per job on the host pool; the prepared
+// lines of s_g2 and -g2 are made once for all of them
+template <class P>
+int pair_checks_t(h2agg_ctx* c, const uint8_t* pairs, const int32_t* status, size_t n, const uint8_t s_g2[128], const uint8_t g2[128],
+                  int* ok) {
+    std::vector<typename P::G1> ps(2 * n);
+    std::vector<typename P::G2> qs(2);
+    uint8_t g2s[256];
+    memcpy(g2s, s_g2, 128);
+    memcpy(g2s + 128, g2, 128);
+    {   // (the G2 points' checks, beside the generator of G1)
+        uint8_t gen2[128] = {0};
+        gen2[0] = gen2[64] = 1;
+        gen2[32] = gen2[96] = 2;
+        std::vector<typename P::G1> p0;
+        TRY(pairing_load<P>(c, gen2, g2s, 2, p0, qs));
+    }
+    P::negate(qs[1]);
+    const std::shared_ptr<const typename P::Prepared> keep[2] = {P::prepared(s_g2, false, qs[0]), P::prepared(g2, true, qs[1])};
+    const std::vector<const typename P::Prepared*> preps = {keep[0].get(), keep[1].get()};
+    std::vector<size_t> todo;
+    for (size_t i = 0; i < n; ++i) {
+        ok[i] = 0;
+        if (status[i] != H2AGG_OK) continue;
+        for (int side = 0; side < 2; ++side) {
+            const int r = P::load1(pairs + 128 * i + 64 * side, ps[2 * i + side]);
+            if (r == 1) return fail(c, H2AGG_ERR_HIP, "pairing: an evaluated G1 coordinate is >= p");
+            if (r) return fail(c, H2AGG_ERR_HIP, "pairing: an evaluated G1 point is not on the curve");
+        }
+        todo.push_back(i);
+    }
+    HostPool::get().run(todo.size(), HostPool::get().size(), [&](size_t j) {
+        const size_t i = todo[j];
+        ok[i] = P::check_prepared(std::vector<typename P::G1>{ps[2 * i], ps[2 * i + 1]}, preps) ? 1 : 0;
+    });
+    return H2AGG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int h2agg_verify_proofs(h2agg_ctx* c, const h2agg_circuit_proofs* circuits, size_t ncircuits, const uint8_t* s_g2, const uint8_t* g2,
+                        uint8_t* left_aff, uint8_t* right_aff, int32_t* status, int* pairing_ok, uint8_t* advice_out,
+                        size_t advice_cap) try {
+    TRY(bind(c));
+    if (!circuits || ncircuits == 0 || !left_aff || !right_aff || !status) return fail(c, H2AGG_ERR_INVALID, "null argument");
+    if ((s_g2 == nullptr) != (g2 == nullptr) || (s_g2 && !pairing_ok))
+        return fail(c, H2AGG_ERR_INVALID, "pass s_g2, g2 and pairing_ok together (or none)");
+    size_t N = 0, advice_need = 0;
+    std::vector<size_t> advice_at;   // byte offset of every proof's advice commitments in advice_out
+    for (size_t ci = 0; ci < ncircuits; ++ci) {
+        const h2agg_circuit_proofs& cp = circuits[ci];
+        if (!cp.vk || cp.vk->ctx != c || !cp.name) return fail(c, H2AGG_ERR_INVALID, "circuit without a verifying key / name");
+        if (cp.nproofs == 0) continue;
+        const h2agg_vk& vk = *cp.vk;
+        if (!cp.transcripts || !cp.transcript_lens || (vk.num_instance && (!cp.instances || !cp.instance_lens)))
+            return fail(c, H2AGG_ERR_INVALID, "null proof data");
+        if (vk.num_instance && c->tables.find(cp.g_lagrange) == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown g_lagrange handle");
+        for (size_t i = 0; i < cp.nproofs; ++i) {
+            if (!cp.transcripts[i]) return fail(c, H2AGG_ERR_INVALID, "null proof data");
+            size_t pl = 0;
+            for (size_t col = 0; col < vk.num_instance; ++col) pl += cp.instance_lens[i * vk.num_instance + col];
+            if (pl && !cp.instances[i]) return fail(c, H2AGG_ERR_INVALID, "null instance data");
+            advice_at.push_back(advice_need);
+            advice_need += (size_t)vk.num_advice * 64;
+        }
+        N += cp.nproofs;
+    }
+    if (N == 0) return fail(c, H2AGG_ERR_INVALID, "no proofs");
+    if (advice_out && advice_need > advice_cap) return fail(c, H2AGG_ERR_INVALID, "advice_out is too small for the proofs' advice commitments");
+    memset(left_aff, 0, 64 * N);
+    memset(right_aff, 0, 64 * N);
+    if (pairing_ok) memset(pairing_ok, 0, sizeof(int) * N);
+    if (advice_out) memset(advice_out, 0, advice_need);
+    for (size_t i = 0; i < N; ++i) status[i] = H2AGG_OK;
+    // ---- what is decided by a proof's shape alone (verify.rs:487-490, :601-603): that proof's status, before any work
+    struct Item { size_t ci, i, g; };
+    std::vector<Item> items;
+    {
+        size_t g = 0;
+        for (size_t ci = 0; ci < ncircuits; ++ci) {
+            const h2agg_circuit_proofs& cp = circuits[ci];
+            if (cp.nproofs == 0) continue;
+            const h2agg_vk& vk = *cp.vk;
+            const size_t fixed_items = script_fixed_items(vk);
+            const uint64_t max_len = ((uint64_t)1 << vk.k) - (vk.blinding_factors + 1);
+            const size_t table_n = vk.num_instance ? c->tables.find(cp.g_lagrange)->second.n : 0;
+            for (size_t i = 0; i < cp.nproofs; ++i, ++g) {
+                const size_t plen = cp.transcript_lens[i];
+                bool bad = plen % 32 != 0 || plen / 32 < fixed_items;
+                for (size_t col = 0; col < vk.num_instance; ++col) {
+                    const uint32_t l = cp.instance_lens[i * vk.num_instance + col];
+                    if (l > max_len || l > table_n) bad = true;
+                }
+                if (bad) status[g] = H2AGG_ERR_INVALID;
+                else items.push_back({ci, i, g});
+            }
+        }
+    }
+    // ---- one verify_aggregation_impl call (per-proof mode) over a list of proofs: each circuit's proofs grouped by length
+    // (the device transcripts take one length per launch); results scattered back to the proofs' places
+    std::vector<uint8_t> pairs(128 * N);
+    auto run = [&](const std::vector<Item>& list) -> int {
+        std::vector<h2agg_circuit_proofs> sub;
+        std::vector<std::string> names;
+        std::vector<std::vector<const uint8_t*>> tr, in;
+        std::vector<std::vector<size_t>> lens;
+        std::vector<std::vector<uint32_t>> ilens;
+        std::vector<size_t> order;   // the call's proof j -> the item's place g
+        std::vector<bool> taken(list.size(), false);
+        for (size_t a = 0; a < list.size(); ++a) {
+            if (taken[a]) continue;
+            const h2agg_circuit_proofs& cp = circuits[list[a].ci];
+            const size_t plen = cp.transcript_lens[list[a].i], ncol = cp.vk->num_instance;
+            tr.emplace_back();
+            in.emplace_back();
+            lens.emplace_back();
+            ilens.emplace_back();
+            for (size_t b = a; b < list.size(); ++b) {
+                if (taken[b] || list[b].ci != list[a].ci || cp.transcript_lens[list[b].i] != plen) continue;
+                taken[b] = true;
+                tr.back().push_back(cp.transcripts[list[b].i]);
+                lens.back().push_back(plen);
+                if (ncol) {
+                    in.back().push_back(cp.instances[list[b].i]);
+                    for (size_t col = 0; col < ncol; ++col) ilens.back().push_back(cp.instance_lens[list[b].i * ncol + col]);
+                }
+                order.push_back(list[b].g);
+            }
+            // (a circuit split by length: every group's keys of its own, "{name}_p{i}" must not meet twice in one schema)
+            names.push_back(std::string(cp.name) + "#" + std::to_string(names.size()));
+            h2agg_circuit_proofs g = cp;
+            g.nproofs = tr.back().size();
+            sub.push_back(g);
+        }
+        for (size_t k = 0; k < sub.size(); ++k) {
+            sub[k].name = names[k].c_str();
+            sub[k].transcripts = tr[k].data();
+            sub[k].transcript_lens = lens[k].data();
+            sub[k].instances = in[k].empty() ? nullptr : in[k].data();
+            sub[k].instance_lens = ilens[k].empty() ? nullptr : ilens[k].data();
+        }
+        const size_t n = order.size();
+        std::vector<uint8_t> p(128 * n, 0), adv;
+        std::vector<int32_t> st(n, H2AGG_OK);
+        size_t adv_need = 0;
+        for (const h2agg_circuit_proofs& g : sub) adv_need += g.nproofs * (size_t)g.vk->num_advice * 64;
+        if (advice_out) adv.resize(adv_need + 1);
+        EachOut eo{p.data(), st.data()};
+        uint8_t l0[64], r0[64];
+        const int rc = verify_aggregation_impl(c, sub.data(), sub.size(), nullptr, nullptr, nullptr, l0, r0, nullptr, nullptr,
+                                               advice_out ? adv.data() : nullptr, adv_need, &eo);
+        if (rc != H2AGG_OK) return rc;
+        size_t aoff = 0;
+        for (size_t j = 0; j < n; ++j) {
+            const size_t g = order[j];
+            status[g] = st[j];
+            if (st[j] == H2AGG_OK) memcpy(pairs.data() + 128 * g, p.data() + 128 * j, 128);
+        }
+        if (advice_out) {   // (in the call's order: circuit groups, proofs in order)
+            for (size_t j = 0; j < n; ++j) {
+                const size_t g = order[j];
+                size_t ci = 0, base = 0;
+                while (g >= base + circuits[ci].nproofs) base += circuits[ci++].nproofs;
+                const size_t bytes = (size_t)circuits[ci].vk->num_advice * 64;
+                if (st[j] == H2AGG_OK) memcpy(advice_out + advice_at[g], adv.data() + aoff, bytes);
+                aoff += bytes;
+            }
+        }
+        return H2AGG_OK;
+    };
+    if (!items.empty()) {
+        const int rc = run(items);
+        if (rc == H2AGG_ERR_BAD_POINT || rc == H2AGG_ERR_NONCANONICAL) {
+            // a proof's bytes do not decode (the device's flags are batch-wide): verify the proofs one by one to name it
+            for (const Item& it : items) {
+                const int r1 = run(std::vector<Item>{it});
+                if (r1 == H2AGG_ERR_BAD_POINT || r1 == H2AGG_ERR_NONCANONICAL || r1 == H2AGG_ERR_INVALID || r1 == H2AGG_ERR_EMPTY)
+                    status[it.g] = r1;
+                else if (r1 != H2AGG_OK)
+                    return r1;
+            }
+        } else if (rc != H2AGG_OK) {
+            return rc;
+        }
+    }
+    for (size_t g = 0; g < N; ++g) {
+        memcpy(left_aff + 64 * g, pairs.data() + 128 * g, 64);
+        memcpy(right_aff + 64 * g, pairs.data() + 128 * g + 64, 64);
+    }
+    // (h2agg_last_phases: the phases of the per-proof verification as the aggregation names them, then the pairings)
+    if (s_g2) {
+        const auto t0 = std::chrono::steady_clock::now();
+        int rc;
+#ifdef H2AGG_PAIRING_ADX_BUILD
+        if (pairing_adx_ok()) rc = pair_checks_t<pairing_adx::Api>(c, pairs.data(), status, N, s_g2, g2, pairing_ok);
+        else
+#endif
+        rc = pair_checks_t<pairing::Api>(c, pairs.data(), status, N, s_g2, g2, pairing_ok);
+        TRY(rc);
+        if (c->dbg_phases) {
+            char buf[64];
+            snprintf(buf, sizeof buf, " pairing=%.3f", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            c->last_phases += buf;
+        }
+    }
+    return H2AGG_OK;
 } catch (const std::bad_alloc&) {
     return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
 } catch (...) {

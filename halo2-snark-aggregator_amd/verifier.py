@@ -149,6 +149,36 @@ def verify_aggregation(eng, circuits: Sequence[Tuple[VerifyingKey, str, int, Seq
     return res + (commits,)
 
 
+def verify_proofs(eng, circuits: Sequence[Tuple[VerifyingKey, str, int, Sequence[Tuple[Sequence[bytes], bytes]]]],
+                  s_g2: Optional[bytes] = None, g2: Optional[bytes] = None, with_commits: bool = False):
+    """h2agg_verify_proofs: verify_single_proof_in_chip (verify.rs:779-833) for every proof of `circuits` (the layout of
+    verify_aggregation), in one call.  -> one record per proof in aggregation order: (left_aff, right_aff, status,
+    pairing_ok or None), status = OK or that proof's own error code; with_commits: a fifth element, the proof's advice
+    commitments ([64-byte affine point per advice column]; zeros for a proof whose status is not OK)"""
+    lib = eng._lib
+    arr, keep = _marshal_circuits(circuits)
+    n = sum(len(proofs) for _vk, _n, _g, proofs in circuits)
+    nb = max(n, 1)
+    left, right = C.create_string_buffer(64 * nb), C.create_string_buffer(64 * nb)
+    status = (C.c_int32 * nb)()
+    ok = (C.c_int * nb)()
+    ncommit = [vk.num_advice_columns for vk, _n, _g, proofs in circuits for _p in proofs]
+    cap = 64 * sum(ncommit) if with_commits else 0
+    adv = C.create_string_buffer(max(cap, 1)) if with_commits else None
+    rc = lib.h2agg_verify_proofs(eng._ctx, C.cast(arr, C.c_void_p), len(circuits), s_g2, g2 if s_g2 is not None else None,
+                                 left, right, status, ok if s_g2 is not None else None, adv, cap)
+    eng._check(rc)
+    out, off = [], 0
+    for i in range(n):
+        rec = (left.raw[64 * i: 64 * (i + 1)], right.raw[64 * i: 64 * (i + 1)], int(status[i]),
+               (bool(ok[i]) if s_g2 is not None else None))
+        if with_commits:
+            rec += ([adv.raw[off + 64 * j: off + 64 * (j + 1)] for j in range(ncommit[i])],)
+            off += 64 * ncommit[i]
+        out.append(rec)
+    return out
+
+
 _ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 

@@ -141,6 +141,15 @@ int h2agg_g1_msm(h2agg_ctx* ctx, const uint8_t* bases_aff, const uint8_t* scalar
  * have to run `batch_normalize` over a million points on one host core first (mock/arith/ecc.rs:106-129 takes
  * `points: Vec<Self::AssignedPoint>` = `C::CurveExt`); 128 instead of 96 bytes per point cross PCIe. */
 int h2agg_g1_msm_jac(h2agg_ctx* ctx, const uint8_t* points_jac, const uint8_t* scalars, size_t n, uint8_t out_jac[96]);
+/* S independent multi_exps (mock/arith/ecc.rs:106-129) over the segments [seg_start[s], seg_start[s+1]) of one
+ * host-side point / scalar array, one set of device launches (replaces S calls of h2agg_g1_msm: the many small multi_exp
+ * calls a drop-in caller makes, and the 2N evaluation sides of h2agg_verify_proofs).  seg_start: S + 1 non-decreasing
+ * offsets, seg_start[0] = 0, seg_start[S] = n.  out_jac: S x 96 B canonical Jacobian.  An empty segment -> H2AGG_ERR_EMPTY
+ * (as h2agg_g1_msm for n == 0: the reference's acc.unwrap()); a scalar >= r -> H2AGG_ERR_NONCANONICAL.  Segments are taken
+ * in groups of whole segments of up to 16384 points per set of launches (test key "seg_chunk"); a longer segment is an
+ * ordinary multi_exp of its own. */
+int h2agg_g1_msm_segmented(h2agg_ctx* ctx, const uint8_t* bases_aff, const uint8_t* scalars, size_t n,
+                           const uint64_t* seg_start, size_t nseg, uint8_t* out_jac);
 
 /* replaces: eval()'s flat tail — multi_exp over the entries that carry a scalar, then `pchip.add` of
  * every scalar-less point (halo2-snark-aggregator-api/src/systems/halo2/evaluation.rs:189-200).
@@ -385,7 +394,28 @@ int h2agg_verify_aggregation_sharded(h2agg_ctx* ctx, const h2agg_circuit_proofs*
  * This reports how often that happened; any pointer may be NULL.  h2agg_debug_configure(ctx, "plan_cache", 0) records every
  * call afresh. */
 int h2agg_verify_plan_stats(h2agg_ctx* ctx, uint64_t* hits, uint64_t* misses, uint64_t* plans_kept);
-/* After h2agg_debug_configure(ctx, "phases", 1): the wall-clock split of the context's last h2agg_verify_aggregation* call as
+/* verify_single_proof_in_chip (halo2-snark-aggregator-api/src/systems/halo2/verify.rs:779-833) for EVERY proof of
+ * `circuits`, in one call: no aggregation challenge, no fold (verify_single_proof_no_eval, :651-688, then
+ * evaluate_multiopen_proof, :690-745, per proof).  Per proof i (aggregation order: circuits in order, proofs in order):
+ *   left_aff[64 i], right_aff[64 i]  that proof's evaluate_multiopen_proof pair, canonical affine;
+ *   status[i]   H2AGG_OK, or THIS proof's error: H2AGG_ERR_BAD_POINT / H2AGG_ERR_NONCANONICAL (its bytes do not decode),
+ *               H2AGG_ERR_INVALID (its transcript length does not fit the key, its W count != rotation groups,
+ *               multiopen.rs:48, an instance column too long, verify.rs:601-603) — the other proofs are still verified;
+ *   pairing_ok[i] (with s_g2 / g2, both or none) e(left_i, s_g2) * e(right_i, -g2) == 1; 0 when status[i] != OK.
+ * The proofs of one circuit may differ in length here (each is checked against the key on its own).
+ * advice_out / advice_cap as in h2agg_verify_aggregation_ex (the fourth return value of verify_single_proof_in_chip); a
+ * proof whose status is not OK leaves zeros there.
+ * Call-level errors only for the call itself: null buffers, no proofs, bad vk / table handle, H2AGG_ERR_NOMEM / _HIP,
+ * and H2AGG_ERR_DIV_ZERO (one shared Fr tape; a zero denominator needs a challenge on a root of unity).
+ * The common path is one set of launches for all proofs: the instance MSMs, transcripts and query recording of the
+ * aggregation, then the 2N multi_exps as one segmented multi_exp (h2agg_g1_msm_segmented's kernels) and the N pairings on
+ * the host pool.  When a proof's bytes do not decode, the proofs are verified again one by one to name it.  Per-proof
+ * recordings are not kept in the aggregation's plan cache (h2agg_verify_plan_stats counts aggregation calls only). */
+int h2agg_verify_proofs(h2agg_ctx* ctx, const h2agg_circuit_proofs* circuits, size_t ncircuits, const uint8_t* s_g2,
+                        const uint8_t* g2, uint8_t* left_aff, uint8_t* right_aff, int32_t* status, int* pairing_ok,
+                        uint8_t* advice_out, size_t advice_cap);
+/* After h2agg_debug_configure(ctx, "phases", 1): the wall-clock split of the context's last h2agg_verify_aggregation* (or
+ * h2agg_verify_proofs) call as
  * one line — " name=milliseconds" per phase in order, then the CPU the calling thread started and ended on and how often it was
  * preempted, then every host sponge chain's start offset, run time (microseconds) and CPU.  For latency reports (which phase a
  * slow call spent its time in); costs a few clock reads per call.  Owned by the context, valid until its next call. */
@@ -497,6 +527,9 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         (default 1; 0: the three latency measures of round 6 off, for an A/B)
  *       "phases" 0|1      keep every aggregation call's wall-clock split for h2agg_last_phases
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
+ *       "seg_chunk" n     h2agg_g1_msm_segmented / h2agg_verify_proofs: at most n points per set of launches of the segmented
+ *                         multi_exp (0 = automatic, 16384); a segment longer than that is an ordinary multi_exp of its own
+ *       "seg_c" 4..8      window bits of the segmented multi_exp (0 = the default, 5; measurement only)
  *       "shard_fail" 0..4  this rank of h2agg_verify_aggregation_sharded fails before (1) / between (2) its exchanges, or inside
  *                         exchange 1 (3) / 2 (4) before its all-gather */
 int h2agg_debug_configure(h2agg_ctx* ctx, const char* key, int value);
