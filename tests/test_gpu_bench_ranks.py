@@ -36,8 +36,8 @@ def run(cmd, env):
 def test_two_ranks_reproduce_one_rank():
     env = dict(os.environ, H2AGG_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     two = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-               "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--agg-proofs", "2"] + COMMON, env)
-    one = run([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "4"] + COMMON, dict(os.environ))
+               "--master-port", str(free_port()), "bench.py", "--gpus", "2", "--agg-proofs", "2", "--full"] + COMMON, env)
+    one = run([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "4", "--full"] + COMMON, dict(os.environ))
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1 and two["scaling"] == "weak"
     assert two["value"] > 0 and two["steps"] == 2
     a2, a1 = two["aggregate"], one["aggregate"]
@@ -66,9 +66,9 @@ def test_gpus_flag_without_a_launcher_starts_the_ranks_itself():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     env.pop("LOCAL_RANK", None)
-    two = run([sys.executable, "bench.py", "--gpus", "2", "--agg-proofs", "2"] + COMMON, env)
+    two = run([sys.executable, "bench.py", "--gpus", "2", "--agg-proofs", "2", "--full"] + COMMON, env)
     assert two["n_gpus"] == 2
-    one = run([sys.executable, "bench.py", "--agg-proofs", "4"] + COMMON, dict(os.environ))     # no --gpus at all: one rank
+    one = run([sys.executable, "bench.py", "--agg-proofs", "4", "--full"] + COMMON, dict(os.environ))     # no --gpus at all: one rank
     assert one["n_gpus"] == 1
     assert two["aggregate"]["final_pair_sha"] == one["aggregate"]["final_pair_sha"]
     assert two["aggregate"]["from_bytes_sharded"]["final_pair_sha"] == one["aggregate"]["from_bytes_sharded"]["final_pair_sha"]
@@ -80,6 +80,17 @@ def test_a_launch_that_does_not_match_gpus_is_refused():
                         "--master-port", str(free_port()), "bench.py", "--gpus", "4", "--agg-proofs", "0"] + COMMON,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode != 0 and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_a_plain_run_prints_only_the_headline():
+    """without --full: the headline line alone, none of the secondary legs (their options left at their defaults)"""
+    line = run([sys.executable, "bench.py", "--gpus", "1", "--log2n", "16", "--steps", "2", "--warmup", "1"], dict(os.environ))
+    assert line["metric"] == "BN254 G1 MSM points/sec" and line["unit"] == "points/s" and line["higher_is_better"] is True
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["config"]["verified"].startswith("(sum k_i s_i)*G on every one of the 2 timed outputs")
+    for key in ("aggregate", "pcie_inclusive", "cpu_baseline", "value_no_spinup", "secondary_leg_error"):
+        assert key not in line, key
+    assert line["roofline"]["power"] is None
 
 
 def test_dump_outputs_holds_the_last_timed_result(tmp_path):

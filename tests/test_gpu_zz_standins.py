@@ -102,9 +102,9 @@ def test_bench_two_processes_over_the_librarys_communicator(tmp_path):
     env = dict(os.environ, H2AGG_DIST_BACKEND="gloo", H2AGG_RCCL_LIB=stub, MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    two = run_bench([sys.executable, "bench.py", "--gpus", "2", "--agg-proofs", "2"] + BENCH, env)
+    two = run_bench([sys.executable, "bench.py", "--gpus", "2", "--agg-proofs", "2", "--full"] + BENCH, env)
     plain = {k: v for k, v in os.environ.items() if k not in ("H2AGG_RCCL_LIB", "H2AGG_DIST_BACKEND")}
-    one = run_bench([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "4"] + BENCH, plain)
+    one = run_bench([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "4", "--full"] + BENCH, plain)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
     a2, a1 = two["aggregate"], one["aggregate"]
     assert "error" not in a2 and "error" not in a1, (a2, a1)

@@ -5,4 +5,4 @@ run() { f=$out/$1.txt; shift; { echo "\$ $*   ($(date -u +%FT%TZ))"; timeout 900
 run fuzz_fixed_base python tests/fuzz_fixed_base.py 270 61
 run fuzz_msm python tests/fuzz_msm.py --seconds 150 --seed 6
 run fuzz_schema python tests/fuzz_schema.py
-python bench.py > $out/bench_default_second_box.json 2> $out/bench_default_second_box.err; head -c 300 $out/bench_default_second_box.json
+python bench.py --full > $out/bench_default_second_box.json 2> $out/bench_default_second_box.err; head -c 300 $out/bench_default_second_box.json

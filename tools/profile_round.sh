@@ -56,7 +56,7 @@ bash tools/pipeline_trace.sh > /dev/null 2>&1; (cat $out/pipeline_trace/timeline
 (python tools/agg_leg_phases.py --proofs 4; python tools/agg_leg_phases.py --proofs 16) > $out/${tag}_agg_leg_phases.txt 2>/dev/null
 # the default bench line itself (no profiler attached); it reads the PMC evidence just collected from profiles/
 mkdir -p profiles && cp $out/${tag}_traffic.json $out/${tag}_batch_traffic.json profiles/
-python bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
+python bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
 # everything to keep goes to profiles/ in ONE step (commit once):
 mkdir -p profiles && cp $out/${tag}_* profiles/
 ls -la $out | grep $tag

@@ -23,7 +23,7 @@ def run(cmd, env):
 
 
 plain = {k: v for k, v in os.environ.items() if k not in ("H2AGG_RCCL_LIB", "H2AGG_DIST_BACKEND", "WORLD_SIZE", "RANK", "LOCAL_RANK")}
-one, err = run([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "4"] + COMMON, plain)
+one, err = run([sys.executable, "bench.py", "--gpus", "1", "--agg-proofs", "4", "--full"] + COMMON, plain)
 assert one, err
 a1, f1 = one["aggregate"], one["aggregate"]["from_bytes_sharded"]
 env = dict(plain, H2AGG_DIST_BACKEND="gloo", H2AGG_RCCL_LIB=stub, MASTER_ADDR="127.0.0.1")
@@ -31,7 +31,7 @@ ok = bad = 0
 t0 = time.time()
 with open(out_path, "w") as f:
     for i in range(N):
-        two, err = run([sys.executable, "bench.py", "--gpus", "2", "--agg-proofs", "2"] + COMMON, env)
+        two, err = run([sys.executable, "bench.py", "--gpus", "2", "--agg-proofs", "2", "--full"] + COMMON, env)
         good = False
         if two:
             a2 = two["aggregate"]
