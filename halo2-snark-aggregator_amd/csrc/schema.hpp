@@ -25,17 +25,11 @@
 #include <vector>
 
 #include "msm_kernels.hpp"
+#include "tape_compile.hpp"   // TapeOp, the opcodes, the LDS encoding's constants
 
 namespace h2agg {
 
 // ------------------------------------------------------------------ device side: Fr tape
-enum : uint32_t { TAPE_MUL = 0, TAPE_ADD = 1, TAPE_SUB = 2, TAPE_INV = 3,     // INV: dst = 1 / a (b unused); 1 / 0 raises FLAG_DIV_ZERO
-                  TAPE_SQRN = 4 };   // dst = a^(2^b), b an IMMEDIATE count (not a register): `pow_constant(x, n)` for n = 2^k
-                                     // (verify.rs:498) as ONE operation — k dependent squarings are k levels of the tape otherwise,
-                                     // each a round trip through the register file; recorded by the verifier pipeline only
-struct TapeOp {
-    uint32_t dst, a, b, op;
-};
 constexpr int REG_WORDS = NL;  // a register = 9 limbs, Montgomery, value < 2r
 
 FP_INLINE Fr reg_load(const uint32_t* regs, uint32_t i) {
@@ -90,15 +84,6 @@ __global__ void __launch_bounds__(BLOCK) k_tape_load_consts(const uint8_t* __res
     if (!fp_is_canonical<FrParams>(x)) atomicOr(flags, FLAG_NONCANONICAL);
     reg_store(regs, i, fp_to_mont<FrParams>(x));
 }
-// one dependency level of the tape: every op's inputs were produced by earlier levels
-// MockFieldChip::mul / add / sub  (mock/arith/field.rs:98-105, 39-55)
-__global__ void __launch_bounds__(BLOCK) k_tape_level(const TapeOp* __restrict__ ops, uint32_t n,
-                                                      uint32_t* __restrict__ regs, uint32_t* flags) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const TapeOp op = ops[i];
-    reg_store(regs, op.dst, tape_exec(op, regs, flags));
-}
 // The whole tape in ONE launch: a single 1024-lane workgroup walks the dependency levels with a barrier
 // in between.  Horner chains make tapes deep and narrow (hundreds of levels of a few operations), which is
 // launch-bound as one kernel per level; wide levels are strip-mined by the 1024 lanes.
@@ -131,17 +116,12 @@ __global__ void __launch_bounds__(TAPE_THREADS) k_tape_run(const TapeOp* __restr
 
 // The same walk with the register file in LDS.  A level of k_tape_run is a dependent round trip through
 // L2 — results stored, barrier, the next level's operands loaded: ~0.8 us of the ~2.4 us a level takes.  Here every value the
-// tape itself reads again lives in an LDS slot for as long as it is live (the host's liveness allocator below hands the slots
+// tape itself reads again lives in an LDS slot for as long as it is live (the host's liveness allocator, tape_compile.hpp, hands the slots
 // out level by level and reuses them: an aggregation's tape has ~9 500 values, ~150 KiB of LDS hold 4 096), so a level's
 // operands are an LDS read behind an LDS-only barrier; constants are converted and placed by this same launch (no separate
 // k_tape_load_consts).  Every result still goes to the global register file as well — fire and forget, nothing in here waits
 // for those stores — because the consumers behind the tape (k_eval_prep, k_tape_gather) read it from there.
-//   op.a / op.b:  bit 31 set: LDS slot (low bits); clear: never happens for a register operand (constants have slots too)
-//   op.op:        opcode | (LDS slot of the result, or TAPE_NOSLOT when nothing in the tape reads it) << 8
-// A tape whose live values do not fit runs through k_tape_run.
-constexpr uint32_t TAPE_LDS_SLOTS = 4096;          // x 36 B = 144 KiB of the CU's 160
-constexpr uint32_t TAPE_NOSLOT = 0xffffffu;
-constexpr uint32_t TAPE_SLOTBIT = 0x80000000u;
+// The encoding of op.a / op.b / op.op: tape_compile.hpp.  A tape whose live values do not fit runs through k_tape_run.
 FP_INLINE Fr slot_load(const uint32_t* file, uint32_t s) {
     Fr r;
 #pragma unroll
@@ -431,6 +411,16 @@ struct Tape {
         return lvl[0];
     }
     uint32_t resolve(uint32_t r) const { return (r & OPBIT) ? nconst + (r & ~OPBIT) : r; }
+    // the operations with final register numbers (what compile_tape takes): the tape must be final, nconst included
+    std::vector<TapeOp> resolved_ops() const {
+        std::vector<TapeOp> r(ops);
+        for (TapeOp& o : r) {
+            o.dst = resolve(o.dst);
+            o.a = resolve(o.a);
+            if (o.op != TAPE_SQRN) o.b = resolve(o.b);   // (SQRN: b is an immediate count, not a register)
+        }
+        return r;
+    }
 };
 
 struct SchemaNode {

@@ -28,123 +28,11 @@ struct h2agg_schema {
         EvalLists L[2];
         int64_t extra[2] = {-1, -1};
         std::vector<uint32_t> all_names;
-        std::vector<TapeOp> sorted;
-        std::vector<uint32_t> lstart;
-        uint32_t maxlevel = 0;
-        bool lds = false;                 // `sorted` is in k_tape_run_lds's encoding, cslot holds the constants' slots
-        std::vector<uint32_t> cslot;
-        uint32_t lds_peak = 0;            // most values live at once (slots needed)
+        CompiledTape tape;
     } prep;
 };
 
 namespace {
-
-// Dependency levels of a tape (operands precede results): ops sorted by level, lstart[l] .. lstart[l + 1] = the ops of
-// level l + 1.  Returns false if an operand is not defined before its use.
-bool schedule_levels(const std::vector<TapeOp>& ops, uint32_t nreg, std::vector<TapeOp>& sorted,
-                     std::vector<uint32_t>& lstart, uint32_t& maxlevel) {
-    const uint32_t nops = (uint32_t)ops.size();
-    std::vector<uint32_t> level(nreg, 0);
-    maxlevel = 0;
-    // An inversion level costs a whole safegcd (~13 k instructions of one wave's latency) however many inversions share it
-    // (every lane of the level inverts its own operand, in lock step: no batching trick, and none needed): put EVERY inversion
-    // on the level of the latest one.  First pass: as soon as possible; second pass: the same with the inversions held back
-    // to that level.
-    uint32_t inv_level = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        maxlevel = 0;
-        uint32_t latest_inv = 0;
-        for (uint32_t k = 0; k < nops; ++k) {
-            const TapeOp& o = ops[k];
-            const bool imm_b = o.op == TAPE_SQRN;   // b = number of squarings (<= 255), not an operand
-            if (o.dst >= nreg || o.a >= o.dst || (imm_b ? o.b > 255u : o.b >= o.dst)) return false;
-            const uint32_t lb = imm_b ? 0u : level[o.b];
-            uint32_t lv = 1 + (level[o.a] > lb ? level[o.a] : lb);
-            if (o.op == TAPE_INV) {
-                if (lv > latest_inv) latest_inv = lv;
-                if (pass == 1 && lv < inv_level) lv = inv_level;
-            }
-            level[o.dst] = lv;
-            if (lv > maxlevel) maxlevel = lv;
-        }
-        if (pass == 0) {
-            if (latest_inv == 0) break;   // no inversions: the first pass is final
-            inv_level = latest_inv;
-            std::fill(level.begin(), level.end(), 0u);
-        }
-    }
-    std::vector<uint32_t> start(maxlevel + 2, 0);
-    for (uint32_t k = 0; k < nops; ++k) start[level[ops[k].dst] + 1]++;
-    for (uint32_t l = 1; l <= maxlevel + 1; ++l) start[l] += start[l - 1];
-    std::vector<uint32_t> cur(start.begin(), start.end());
-    sorted.resize(nops);
-    for (uint32_t k = 0; k < nops; ++k) sorted[cur[level[ops[k].dst]]++] = ops[k];
-    lstart.assign(start.begin() + 1, start.end());
-    return true;
-}
-
-// Liveness allocation of the tape's values to the LDS register file of k_tape_run_lds (schema.hpp).  `sorted` / `lstart` come
-// from schedule_levels; a value is live from the level that makes it (constants: from the start) to the last level that reads
-// it, and its slot is handed out again one level later (inside a level one lane may still be reading what another would
-// overwrite).  Values nothing in the tape reads get no slot.  On success `sorted` is rewritten in the kernel's encoding and
-// cslot[i] is constant i's slot; false (nothing touched): more than TAPE_LDS_SLOTS values are live at some level.
-bool tape_lds_assign(std::vector<TapeOp>& sorted, const std::vector<uint32_t>& lstart, uint32_t nconst, uint32_t nreg,
-                     std::vector<uint32_t>& cslot, uint32_t* peak_out = nullptr) {
-    const uint32_t nlevels = lstart.empty() ? 0 : (uint32_t)lstart.size() - 1;
-    std::vector<uint32_t> last(nreg, 0), slot(nreg, TAPE_NOSLOT);   // last[r]: last level (1-based) that reads register r
-    for (uint32_t l = 0; l < nlevels; ++l)
-        for (uint32_t k = lstart[l]; k < lstart[l + 1]; ++k) {
-            const TapeOp& o = sorted[k];
-            last[o.a] = l + 1;
-            if (o.op != TAPE_SQRN) last[o.b] = l + 1;
-        }
-    // values to release after each level, as lists threaded through `next_dead`
-    std::vector<uint32_t> dead_head(nlevels + 2, 0xffffffffu), next_dead(nreg, 0xffffffffu);
-    auto retire_at = [&](uint32_t r) {
-        next_dead[r] = dead_head[last[r]];
-        dead_head[last[r]] = r;
-    };
-    std::vector<uint32_t> free_slots;
-    uint32_t fresh = 0, peak = 0, live = 0;
-    auto take = [&]() -> uint32_t {
-        ++live;
-        if (live > peak) peak = live;
-        if (!free_slots.empty()) {
-            const uint32_t sl = free_slots.back();
-            free_slots.pop_back();
-            return sl;
-        }
-        return fresh++;
-    };
-    for (uint32_t r = 0; r < nconst; ++r)
-        if (last[r]) {
-            slot[r] = take();
-            retire_at(r);
-        }
-    bool fits = fresh <= TAPE_LDS_SLOTS;
-    for (uint32_t l = 0; l < nlevels && fits; ++l) {
-        for (uint32_t k = lstart[l]; k < lstart[l + 1]; ++k) {
-            const uint32_t d = sorted[k].dst;
-            if (!last[d]) continue;
-            slot[d] = take();
-            retire_at(d);
-        }
-        fits = fresh <= TAPE_LDS_SLOTS;
-        for (uint32_t r = dead_head[l + 1]; r != 0xffffffffu; r = next_dead[r]) {   // read for the last time in this level
-            free_slots.push_back(slot[r]);
-            --live;
-        }
-    }
-    if (peak_out) *peak_out = peak;
-    if (!fits) return false;
-    for (TapeOp& o : sorted) {
-        o.op = (o.op & 0xffu) | (slot[o.dst] << 8);
-        o.a = slot[o.a] | TAPE_SLOTBIT;
-        if ((o.op & 0xffu) != TAPE_SQRN) o.b = slot[o.b] | TAPE_SLOTBIT;
-    }
-    cslot.assign(slot.begin(), slot.begin() + nconst);
-    return true;
-}
 
 // host half of eval(): eval_prepare + the partition of evaluation.rs:183-196
 int eval_lists(h2agg_schema* sc, uint32_t node, EvalLists& L) {
@@ -190,6 +78,77 @@ int ensure_stage(h2agg_ctx* c, size_t bytes) {
     return H2AGG_OK;
 }
 
+// The tape's part of a staging block and of the launches behind it: every caller packs what the device needs into ONE pinned
+// block (256-byte aligned regions; the tape's four first, the caller's own behind them), uploads it with ONE copy, then runs the
+// tape.
+size_t stage_align(size_t x) { return (x + 255) & ~(size_t)255; }
+struct TapeOffsets {
+    size_t consts = 0, ops = 0, lvl = 0, cslot = 0;
+};
+TapeOffsets tape_layout(size_t& off, const CompiledTape& ct, uint32_t nconst) {
+    TapeOffsets o;
+    o.consts = off;  off = stage_align(off + (size_t)nconst * 32);
+    o.ops = off;     off = stage_align(off + ct.sorted.size() * sizeof(TapeOp));
+    o.lvl = off;     off = stage_align(off + ct.lstart.size() * 4);
+    o.cslot = off;   off = stage_align(off + ct.cslot.size() * 4);
+    return o;
+}
+void tape_fill(uint8_t* h, const TapeOffsets& o, const CompiledTape& ct, const uint8_t* consts, uint32_t nconst) {
+    if (nconst) memcpy(h + o.consts, consts, (size_t)nconst * 32);
+    if (!ct.sorted.empty()) memcpy(h + o.ops, ct.sorted.data(), ct.sorted.size() * sizeof(TapeOp));
+    if (!ct.lstart.empty()) memcpy(h + o.lvl, ct.lstart.data(), ct.lstart.size() * 4);
+    if (!ct.cslot.empty()) memcpy(h + o.cslot, ct.cslot.data(), ct.cslot.size() * 4);
+}
+// d: the uploaded block on the device.  Fills c->sch_regs (the caller has sized it) on the context's stream.
+void tape_launch(h2agg_ctx* c, const uint8_t* d, const TapeOffsets& o, const CompiledTape& ct, uint32_t nconst) {
+    hipStream_t st = c->stream;
+    uint32_t* regs = (uint32_t*)c->sch_regs.p;
+    if (ct.lds) {   // constants + every level in one launch, the register file in LDS (schema.hpp)
+        hipLaunchKernelGGL(k_tape_run_lds, dim3(1), dim3(TAPE_THREADS), 0, st, d + o.consts, (const uint32_t*)(d + o.cslot), nconst,
+                           (const TapeOp*)(d + o.ops), (const uint32_t*)(d + o.lvl), ct.maxlevel, regs, c->d_flags);
+        return;
+    }
+    if (nconst)
+        hipLaunchKernelGGL(k_tape_load_consts, dim3((nconst + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d + o.consts, nconst, regs,
+                           c->d_flags);
+    if (!ct.sorted.empty())
+        hipLaunchKernelGGL(k_tape_run, dim3(1), dim3(TAPE_THREADS), 0, st, (const TapeOp*)(d + o.ops), (const uint32_t*)(d + o.lvl),
+                           ct.maxlevel, regs, c->d_flags);
+}
+
+// (X, Y, ZZ, ZZZ) as the device leaves its results (128 B each, canonical) -> affine x = X / ZZ, y = Y / ZZZ (64 B each; the
+// identity: zeros, as the device's affine store writes it).  The division happens on the host: ONE field inversion for all n
+// (Montgomery's trick) is ~10 us on a host core and ~55 us of a lone wave's latency on the device, at the very end of an
+// evaluation's chain.  false: a coordinate is not canonical.
+bool xyzz_to_affine(const uint8_t* xyzz, size_t n, uint8_t* out_aff) {
+    namespace pr = h2agg::pairing;
+    struct Pt {
+        pr::Fq X, Y, ZZ, ZZZ, before;   // before: the product of the earlier points' denominators
+    };
+    Pt two[2];   // (the two sides of one evaluation: no allocation)
+    std::vector<Pt> many(n > 2 ? n : 0);
+    Pt* p = n > 2 ? many.data() : two;
+    pr::Fq acc = pr::fq_one();
+    for (size_t s = 0; s < n; ++s) {
+        const uint8_t* o = xyzz + 128 * s;
+        if (!pr::fq_from_bytes(o, p[s].X) || !pr::fq_from_bytes(o + 32, p[s].Y) || !pr::fq_from_bytes(o + 64, p[s].ZZ) ||
+            !pr::fq_from_bytes(o + 96, p[s].ZZZ))
+            return false;
+        p[s].before = acc;
+        if (!pr::fq_is_zero(p[s].ZZ)) acc = pr::fq_mul(acc, pr::fq_mul(p[s].ZZ, p[s].ZZZ));
+    }
+    pr::Fq inv = pr::fq_inv(acc);   // 1 / prod(ZZ ZZZ)
+    memset(out_aff, 0, 64 * n);
+    for (size_t s = n; s-- > 0;) {
+        if (pr::fq_is_zero(p[s].ZZ)) continue;
+        const pr::Fq dinv = pr::fq_mul(inv, p[s].before);                      // 1 / (ZZ_s ZZZ_s)
+        inv = pr::fq_mul(inv, pr::fq_mul(p[s].ZZ, p[s].ZZZ));
+        pr::fq_to_bytes(pr::fq_mul(p[s].X, pr::fq_mul(dinv, p[s].ZZZ)), out_aff + 64 * s);        // X / ZZ
+        pr::fq_to_bytes(pr::fq_mul(p[s].Y, pr::fq_mul(dinv, p[s].ZZ)), out_aff + 64 * s + 32);   // Y / ZZZ
+    }
+    return true;
+}
+
 // Device half of eval(), for one evaluation or for the two sides of evaluate_multiopen_proof at once.
 // Everything the device needs (tape constants, the tape sorted by dependency level, per side the scalar
 // register indices, the points and the scalar-less points) is packed into ONE pinned staging block and uploaded
@@ -204,40 +163,18 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
     for (int s = 0; s < nsides; ++s)
         if (L[s].regs_s.empty())                              // pchip.multi_exp(ctx, [], []) panics
             return fail(c, H2AGG_ERR_EMPTY, "multi_exp of zero pairs (reference panics: mock/arith/ecc.rs:128)");
-    // ---- the tape is final from here on: resolve provisional ids, sort the operations by dependency level
+    // ---- the tape is final from here on: its dependency levels (the prepared ones, if they are this tape's)
     const uint32_t nconst = t.nconst, nops = (uint32_t)t.ops.size(), nreg = nconst + nops;
     const bool need_tape = !(c->sch_owner == sc && sc->tape_done_ops == nops && sc->tape_done_consts == nconst);
-    std::vector<TapeOp> sorted_own;
-    std::vector<uint32_t> lstart_own, cslot_own;
-    bool lds_own = false;
-    uint32_t maxlevel = 0;
-    const bool sched_ready = pre && pre->ops_n == nops && pre->consts_n == nconst && pre->sorted.size() == nops;
-    const std::vector<TapeOp>& sorted = sched_ready && need_tape ? pre->sorted : sorted_own;
-    const std::vector<uint32_t>& lstart = sched_ready && need_tape ? pre->lstart : lstart_own;
-    if (sched_ready) maxlevel = pre->maxlevel;
-    if (need_tape && nops && !sched_ready) {
-        std::vector<TapeOp> ops(nops);
-        for (uint32_t k = 0; k < nops; ++k) {
-            TapeOp o = t.ops[k];
-            o.dst = t.resolve(o.dst);
-            o.a = t.resolve(o.a);
-            if (o.op != TAPE_SQRN) o.b = t.resolve(o.b);   // (SQRN: b is an immediate count, not a register)
-            ops[k] = o;
-        }
-        if (!schedule_levels(ops, nreg, sorted_own, lstart_own, maxlevel))
-            return fail(c, H2AGG_ERR_INVALID, "tape: operand not yet defined");
-        lds_own = c->dbg_tape_lds && tape_lds_assign(sorted_own, lstart_own, nconst, nreg, cslot_own);
-    }
-    const bool use_pre_sched = sched_ready && need_tape;
-    const bool tape_lds = need_tape && nops && (use_pre_sched ? pre->lds : lds_own);
-    const std::vector<uint32_t>& cslot = use_pre_sched ? pre->cslot : cslot_own;
+    const bool use_prepared = need_tape && pre && pre->ops_n == nops && pre->consts_n == nconst && pre->tape.sorted.size() == nops;
+    CompiledTape own;
+    if (need_tape && !use_prepared && !compile_tape(t.resolved_ops(), nconst, c->dbg_tape_lds, own))
+        return fail(c, H2AGG_ERR_INVALID, "tape: operand not yet defined");
+    const CompiledTape& ct = use_prepared ? pre->tape : own;   // (by reference: an aggregation's tape is megabytes)
     // ---- staging layout
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t off = 0;
-    const size_t off_consts = off;  off = align(off + (need_tape ? (size_t)nconst * 32 : 0));
-    const size_t off_ops = off;     off = align(off + sorted.size() * sizeof(TapeOp));
-    const size_t off_lvl = off;     off = align(off + lstart.size() * 4);
-    const size_t off_cslot = off;   off = align(off + (tape_lds ? (size_t)nconst * 4 : 0));
+    TapeOffsets to;
+    if (need_tape) to = tape_layout(off, ct, nconst);
     size_t off_idx[2] = {0, 0}, off_pts[2] = {0, 0}, off_pns[2] = {0, 0}, m[2] = {0, 0}, k[2] = {0, 0};
     for (int s = 0; s < nsides; ++s) {
         m[s] = L[s].regs_s.size() + (extra_pt && extra_pt[s] ? 1 : 0);
@@ -247,17 +184,17 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
     // and its latency chain no longer queue behind the first one's accumulation
     const bool split = nsides == 2 && c->dbg_eval_split && msm_split_ok(c, m[0] + m[1]);
     if (split) {
-        off_idx[0] = off;  off_idx[1] = off + m[0] * 4;   off = align(off + (m[0] + m[1]) * 4);
-        off_pts[0] = off;  off_pts[1] = off + m[0] * 64;  off = align(off + (m[0] + m[1]) * 64);
+        off_idx[0] = off;  off_idx[1] = off + m[0] * 4;   off = stage_align(off + (m[0] + m[1]) * 4);
+        off_pts[0] = off;  off_pts[1] = off + m[0] * 64;  off = stage_align(off + (m[0] + m[1]) * 64);
         for (int s = 0; s < 2; ++s) {
             off_pns[s] = off;
-            off = align(off + k[s] * 64);
+            off = stage_align(off + k[s] * 64);
         }
     } else {
         for (int s = 0; s < nsides; ++s) {
-            off_idx[s] = off;  off = align(off + m[s] * 4);
-            off_pts[s] = off;  off = align(off + m[s] * 64);
-            off_pns[s] = off;  off = align(off + k[s] * 64);
+            off_idx[s] = off;  off = stage_align(off + m[s] * 4);
+            off_pts[s] = off;  off = stage_align(off + m[s] * 64);
+            off_pns[s] = off;  off = stage_align(off + k[s] * 64);
         }
     }
     const size_t total = off;
@@ -265,10 +202,7 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
     TRY(ensure(c, c->sch_in, total));
     if (need_tape) TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
     uint8_t* h = c->h_stage;
-    if (need_tape && nconst) memcpy(h + off_consts, t.consts.data(), (size_t)nconst * 32);
-    if (!sorted.empty()) memcpy(h + off_ops, sorted.data(), sorted.size() * sizeof(TapeOp));
-    if (!lstart.empty()) memcpy(h + off_lvl, lstart.data(), lstart.size() * 4);
-    if (tape_lds && nconst) memcpy(h + off_cslot, cslot.data(), (size_t)nconst * 4);
+    if (need_tape) tape_fill(h, to, ct, t.consts.data(), nconst);
     for (int s = 0; s < nsides; ++s) {
         uint32_t* idx = (uint32_t*)(h + off_idx[s]);
         const size_t base_m = L[s].regs_s.size();
@@ -286,18 +220,7 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
     uint8_t* d = (uint8_t*)c->sch_in.p;
     HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
     if (need_tape) {
-        if (tape_lds) {   // constants + every level in one launch, the register file in LDS (schema.hpp)
-            hipLaunchKernelGGL(k_tape_run_lds, dim3(1), dim3(TAPE_THREADS), 0, st, (const uint8_t*)(d + off_consts),
-                               (const uint32_t*)(d + off_cslot), nconst, (const TapeOp*)(d + off_ops),
-                               (const uint32_t*)(d + off_lvl), maxlevel, (uint32_t*)c->sch_regs.p, c->d_flags);
-        } else {
-        if (nconst)
-            hipLaunchKernelGGL(k_tape_load_consts, dim3((nconst + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st,
-                               (const uint8_t*)(d + off_consts), nconst, (uint32_t*)c->sch_regs.p, c->d_flags);
-        if (nops)
-            hipLaunchKernelGGL(k_tape_run, dim3(1), dim3(TAPE_THREADS), 0, st, (const TapeOp*)(d + off_ops),
-                               (const uint32_t*)(d + off_lvl), maxlevel, (uint32_t*)c->sch_regs.p, c->d_flags);
-        }
+        tape_launch(c, d, to, ct, nconst);
         c->sch_owner = sc;
         sc->tape_done_ops = nops;
         sc->tape_done_consts = nconst;
@@ -550,6 +473,100 @@ int multiopen_lists(h2agg_schema* sc, uint32_t w_x, uint32_t w_g, EvalLists L[2]
     }
     return H2AGG_OK;
 }
+
+// (seg_msm.inc)
+int seg_msm_run(h2agg_ctx* c, const uint8_t* d_bases, const uint8_t* d_scalars, const uint64_t* seg, size_t S,
+                const uint32_t* d_seg, uint8_t* d_out_jac);
+
+// evaluate_multiopen_proof (verify.rs:690-745) for many (w_x, w_g) pairs of one schema at once: every side's eval_prepare walk
+// recorded on the tape, ONE tape run, the 2N multi_exps as ONE segmented multi_exp (the (G, +/- e) pair folded into each side
+// as in eval_launch_sides), the scalar-less points, and one field inversion for all sides (Montgomery's trick).
+// out_aff: 128 B per pair (left, right), canonical affine.
+int evaluate_multiopen_many(h2agg_schema* sc, const std::vector<std::pair<uint32_t, uint32_t>>& roots, uint8_t* out_aff) {
+    h2agg_ctx* c = sc->ctx;
+    Schema& S = sc->s;
+    Tape& t = S.tape;
+    const size_t nsides = 2 * roots.size();
+    std::vector<EvalLists> L(nsides);
+    std::vector<int64_t> extra(nsides, -1);
+    std::vector<uint32_t> names;
+    for (size_t p = 0; p < roots.size(); ++p) TRY(multiopen_lists(sc, roots[p].first, roots[p].second, &L[2 * p], &extra[2 * p], names));
+    // ---- the tape is final: its dependency levels
+    const uint32_t nconst = t.nconst, nops = (uint32_t)t.ops.size(), nreg = nconst + nops;
+    CompiledTape ct;
+    if (!compile_tape(t.resolved_ops(), nconst, c->dbg_tape_lds, ct)) return fail(c, H2AGG_ERR_INVALID, "tape: operand not yet defined");
+    // ---- one staging block: tape, then per side (in side order) the (register, point) pairs, the scalar-less points, and
+    // both segmentations
+    std::vector<uint64_t> seg(nsides + 1, 0);
+    std::vector<uint32_t> seg32(nsides + 1, 0), pseg(nsides + 1, 0);
+    for (size_t s = 0; s < nsides; ++s) {
+        seg[s + 1] = seg[s] + L[s].regs_s.size() + (extra[s] >= 0 ? 1 : 0);
+        pseg[s + 1] = pseg[s] + (uint32_t)(L[s].pts_ns.size() / 64);
+    }
+    const size_t M = seg[nsides], K = pseg[nsides];
+    if (M >= ((size_t)1 << 30)) return fail(c, H2AGG_ERR_INVALID, "too many evaluation pairs");
+    for (size_t s = 0; s <= nsides; ++s) seg32[s] = (uint32_t)seg[s];
+    size_t off = 0;
+    const TapeOffsets to = tape_layout(off, ct, nconst);
+    const size_t off_idx = off;     off = stage_align(off + M * 4);
+    const size_t off_pts = off;     off = stage_align(off + M * 64);
+    const size_t off_pns = off;     off = stage_align(off + K * 64);
+    const size_t off_seg = off;     off = stage_align(off + (nsides + 1) * 4);
+    const size_t off_pseg = off;    off = stage_align(off + (nsides + 1) * 4);
+    const size_t total = off;
+    TRY(ensure_stage(c, total));
+    TRY(ensure(c, c->sch_in, total));
+    TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
+    TRY(ensure(c, c->sch_scalars[0], M * 32 + 32));
+    TRY(ensure(c, c->sch_bases[0], M * 64 + 64));
+    TRY(ensure(c, c->seg_out, nsides * (96 + 128) + 256));
+    uint8_t gen[64] = {0};
+    gen[0] = 1;
+    gen[32] = 2;   // pchip.assign_one = generator (1, 2)   verify.rs:714
+    uint8_t* h = c->h_stage;
+    tape_fill(h, to, ct, t.consts.data(), nconst);
+    uint32_t* idx = (uint32_t*)(h + off_idx);
+    for (size_t s = 0; s < nsides; ++s) {
+        const size_t m = L[s].regs_s.size(), o = seg[s];
+        for (size_t i = 0; i < m; ++i) idx[o + i] = t.resolve(L[s].regs_s[i]);
+        memcpy(h + off_pts + 64 * o, L[s].pts_s.data(), m * 64);
+        if (extra[s] >= 0) {
+            idx[o + m] = t.resolve((uint32_t)extra[s]);
+            memcpy(h + off_pts + 64 * (o + m), gen, 64);
+        }
+        if (!L[s].pts_ns.empty()) memcpy(h + off_pns + 64 * (size_t)pseg[s], L[s].pts_ns.data(), L[s].pts_ns.size());
+    }
+    memcpy(h + off_seg, seg32.data(), (nsides + 1) * 4);
+    memcpy(h + off_pseg, pseg.data(), (nsides + 1) * 4);
+    hipStream_t st = c->stream;
+    uint8_t* d = (uint8_t*)c->sch_in.p;
+    TRY(clear_flags(c));
+    HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
+    tape_launch(c, d, to, ct, nconst);
+    c->sch_owner = sc;
+    sc->tape_done_ops = nops;
+    sc->tape_done_consts = nconst;
+    // gather + Montgomery form of every side's pairs in one launch, then the segmented multi_exp
+    hipLaunchKernelGGL(k_eval_prep<false>, dim3((unsigned)((M + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, (const uint32_t*)c->sch_regs.p,
+                       (const uint32_t*)(d + off_idx), (const uint8_t*)(d + off_pts), (uint32_t)M, (uint8_t*)c->sch_scalars[0].p,
+                       (uint8_t*)c->sch_bases[0].p, (uint8_t*)nullptr, c->d_flags);
+    uint8_t* d_jac = (uint8_t*)c->seg_out.p;
+    uint8_t* d_tail = d_jac + 96 * nsides;
+    TRY(seg_msm_run(c, (const uint8_t*)c->sch_bases[0].p, (const uint8_t*)c->sch_scalars[0].p, seg.data(), nsides,
+                    (const uint32_t*)(d + off_seg), d_jac));
+    TRY(join_tails(c));
+    hipLaunchKernelGGL(k_seg_tail, dim3((unsigned)nsides), dim3(64), 0, st, (const uint8_t*)d_jac, (const uint8_t*)(d + off_pns),
+                       (const uint32_t*)(d + off_pseg), d_tail, c->d_flags);
+    std::vector<uint8_t> xyzz(nsides * 128);
+    HIP_TRY(c, hipMemcpyAsync(xyzz.data(), d_tail, xyzz.size(), hipMemcpyDeviceToHost, st));
+    TRY(finish(c));
+    S.point_list_len = L[nsides - 1].regs_s.size();
+    S.names = names;
+    if (!xyzz_to_affine(xyzz.data(), nsides, out_aff))
+        return fail(c, H2AGG_ERR_HIP, "evaluate_multiopen_proof: the device returned a non-canonical coordinate");
+    return H2AGG_OK;
+}
+
 }   // namespace
 
 int h2agg_evaluate_multiopen_prepare(h2agg_schema* sc, uint32_t w_x, uint32_t w_g) try {
@@ -559,26 +576,14 @@ int h2agg_evaluate_multiopen_prepare(h2agg_schema* sc, uint32_t w_x, uint32_t w_
     h2agg_schema::Prep& P = sc->prep;
     P = h2agg_schema::Prep();
     TRY(multiopen_lists(sc, w_x, w_g, P.L, P.extra, P.all_names));
-    Tape& t = S.tape;
-    const uint32_t nconst = t.nconst, nops = (uint32_t)t.ops.size();
-    if (nops) {   // the tape is final for this evaluation: its dependency levels (eval_launch_sides takes them as they are)
-        std::vector<TapeOp> ops(nops);
-        for (uint32_t k = 0; k < nops; ++k) {
-            TapeOp o = t.ops[k];
-            o.dst = t.resolve(o.dst);
-            o.a = t.resolve(o.a);
-            if (o.op != TAPE_SQRN) o.b = t.resolve(o.b);   // (SQRN: b is an immediate count, not a register)
-            ops[k] = o;
-        }
-        if (!schedule_levels(ops, nconst + nops, P.sorted, P.lstart, P.maxlevel))
-            return fail(c, H2AGG_ERR_INVALID, "tape: operand not yet defined");
-        P.lds = c->dbg_tape_lds && tape_lds_assign(P.sorted, P.lstart, nconst, nconst + nops, P.cslot, &P.lds_peak);
-    }
+    // the tape is final for this evaluation: its dependency levels (eval_launch_sides takes them as they are)
+    if (!compile_tape(S.tape.resolved_ops(), S.tape.nconst, c->dbg_tape_lds, P.tape))
+        return fail(c, H2AGG_ERR_INVALID, "tape: operand not yet defined");
     P.w_x = w_x;
     P.w_g = w_g;
     P.nodes_n = S.nodes.size();
-    P.ops_n = nops;
-    P.consts_n = nconst;
+    P.ops_n = S.tape.ops.size();
+    P.consts_n = S.tape.nconst;
     P.valid = true;
     return H2AGG_OK;
 } catch (const std::bad_alloc&) {
@@ -651,38 +656,18 @@ int h2agg_evaluate_multiopen_proof(h2agg_schema* sc, uint32_t w_x, uint32_t w_g,
     lap("launch");
     TRY(join_tails(c));
     // scalar-less points (evaluation.rs:198-200) + to_value (verify.rs:730-731), both sides in one launch
-    // The device leaves both results as (X, Y, ZZ, ZZZ); the division x = X / ZZ, y = Y / ZZZ happens HERE: one field inversion
-    // for both sides (Montgomery's trick) is ~10 us on a host core and ~55 us of a lone wave's latency on the device, at the
-    // very end of the evaluation's chain.
+    // The device leaves both results as (X, Y, ZZ, ZZZ): xyzz_to_affine.
     hipLaunchKernelGGL(k_eval_tail_affine2, dim3(2), dim3(BLOCK), 0, c->stream, sc->side_xyzz[0], sc->side_xyzz[1],
                        sc->side_pns[0], sc->side_pns[1], sc->side_k[0], sc->side_k[1], (uint8_t*)nullptr, c->d_flags,
                        (uint8_t*)c->small.p + 512);
     HIP_TRY(c, hipMemcpyAsync(c->h_pinned + 512, (uint8_t*)c->small.p + 512, 256, hipMemcpyDeviceToHost, c->stream));
     TRY(finish(c));
     lap("device wait");
-    {
-        namespace pr = h2agg::pairing;
-        pr::Fq X[2], Y[2], ZZ[2], ZZZ[2], den[2];
-        bool inf[2];
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const uint8_t* o = c->h_pinned + 512 + 128 * s2;
-            if (!pr::fq_from_bytes(o, X[s2]) || !pr::fq_from_bytes(o + 32, Y[s2]) || !pr::fq_from_bytes(o + 64, ZZ[s2]) ||
-                !pr::fq_from_bytes(o + 96, ZZZ[s2]))
-                return fail(c, H2AGG_ERR_HIP, "evaluate_multiopen_proof: the device returned a non-canonical coordinate");
-            inf[s2] = pr::fq_is_zero(ZZ[s2]);
-            den[s2] = inf[s2] ? pr::fq_one() : pr::fq_mul(ZZ[s2], ZZZ[s2]);
-        }
-        const pr::Fq inv01 = pr::fq_inv(pr::fq_mul(den[0], den[1]));   // 1 / (ZZ0 ZZZ0 ZZ1 ZZZ1)
-        const pr::Fq dinv[2] = {pr::fq_mul(inv01, den[1]), pr::fq_mul(inv01, den[0])};
-        uint8_t* outs[2] = {left_aff, right_aff};
-        for (int s2 = 0; s2 < 2; ++s2) {
-            if (inf[s2]) continue;   // the identity: zeros (as the device's affine store writes it)
-            const pr::Fq x = pr::fq_mul(X[s2], pr::fq_mul(dinv[s2], ZZZ[s2]));   // X / ZZ
-            const pr::Fq y = pr::fq_mul(Y[s2], pr::fq_mul(dinv[s2], ZZ[s2]));    // Y / ZZZ
-            pr::fq_to_bytes(x, outs[s2]);
-            pr::fq_to_bytes(y, outs[s2] + 32);
-        }
-    }
+    uint8_t aff[128];
+    if (!xyzz_to_affine(c->h_pinned + 512, 2, aff))
+        return fail(c, H2AGG_ERR_HIP, "evaluate_multiopen_proof: the device returned a non-canonical coordinate");
+    memcpy(left_aff, aff, 64);
+    memcpy(right_aff, aff + 64, 64);
     S.names = all_names;  // points_wx ++ points_wg  (verify.rs:711-712)
     return H2AGG_OK;
 } catch (const std::bad_alloc&) {
@@ -704,50 +689,32 @@ int h2agg_fr_tape_eval(h2agg_ctx* c, const uint8_t* consts, size_t nconst, const
     if (nconst + nops >= ((size_t)1 << 30)) return fail(c, H2AGG_ERR_INVALID, "program too large");
     if (nout == 0) return H2AGG_OK;
     const uint32_t nreg = (uint32_t)(nconst + nops);
-    std::vector<TapeOp> ops(nops), sorted;
+    std::vector<TapeOp> ops(nops);
     for (size_t k = 0; k < nops; ++k) {
         if (ops3[3 * k] > TAPE_INV) return fail(c, H2AGG_ERR_INVALID, "unknown tape opcode");
         ops[k] = TapeOp{(uint32_t)(nconst + k), ops3[3 * k + 1], ops3[3 * k + 2], ops3[3 * k]};
     }
-    std::vector<uint32_t> lstart;
-    uint32_t maxlevel = 0;
-    if (!schedule_levels(ops, nreg, sorted, lstart, maxlevel))
+    CompiledTape ct;
+    if (!compile_tape(ops, (uint32_t)nconst, c->dbg_tape_lds, ct))
         return fail(c, H2AGG_ERR_INVALID, "tape: operand not defined before its use");
     for (size_t i = 0; i < nout; ++i)
         if (out_regs[i] >= nreg) return fail(c, H2AGG_ERR_INVALID, "tape: output register out of range");
-    std::vector<uint32_t> cslot;
-    const bool tape_lds = nops && c->dbg_tape_lds && tape_lds_assign(sorted, lstart, (uint32_t)nconst, nreg, cslot);
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t off_consts = 0, off_ops = align(nconst * 32), off_lvl = align(off_ops + nops * sizeof(TapeOp)),
-                 off_idx = align(off_lvl + lstart.size() * 4), off_cslot = align(off_idx + nout * 4),
-                 total = align(off_cslot + (tape_lds ? nconst * 4 : 0));
+    size_t off = 0;
+    const TapeOffsets to = tape_layout(off, ct, (uint32_t)nconst);
+    const size_t off_idx = off, total = stage_align(off + nout * 4);
     TRY(ensure_stage(c, total));
     TRY(ensure(c, c->sch_in, total));
     TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
     TRY(ensure(c, c->sch_scalars[0], nout * 32));
     c->sch_owner = nullptr;   // the register file no longer reflects any schema's tape
     uint8_t* h = c->h_stage;
-    if (nconst) memcpy(h + off_consts, consts, nconst * 32);
-    if (nops) memcpy(h + off_ops, sorted.data(), nops * sizeof(TapeOp));
-    if (!lstart.empty()) memcpy(h + off_lvl, lstart.data(), lstart.size() * 4);
+    tape_fill(h, to, ct, consts, (uint32_t)nconst);
     memcpy(h + off_idx, out_regs, nout * 4);
-    if (tape_lds && nconst) memcpy(h + off_cslot, cslot.data(), nconst * 4);
     uint8_t* d = (uint8_t*)c->sch_in.p;
     hipStream_t st = c->stream;
     TRY(clear_flags(c));
     HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
-    if (tape_lds) {
-        hipLaunchKernelGGL(k_tape_run_lds, dim3(1), dim3(TAPE_THREADS), 0, st, (const uint8_t*)(d + off_consts),
-                           (const uint32_t*)(d + off_cslot), (uint32_t)nconst, (const TapeOp*)(d + off_ops),
-                           (const uint32_t*)(d + off_lvl), maxlevel, (uint32_t*)c->sch_regs.p, c->d_flags);
-    } else {
-    if (nconst)
-        hipLaunchKernelGGL(k_tape_load_consts, dim3((unsigned)((nconst + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st,
-                           (const uint8_t*)(d + off_consts), (uint32_t)nconst, (uint32_t*)c->sch_regs.p, c->d_flags);
-    if (nops)
-        hipLaunchKernelGGL(k_tape_run, dim3(1), dim3(TAPE_THREADS), 0, st, (const TapeOp*)(d + off_ops),
-                           (const uint32_t*)(d + off_lvl), maxlevel, (uint32_t*)c->sch_regs.p, c->d_flags);
-    }
+    tape_launch(c, d, to, ct, (uint32_t)nconst);
     hipLaunchKernelGGL(k_tape_gather, dim3((unsigned)((nout + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st,
                        (const uint32_t*)c->sch_regs.p, (const uint32_t*)(d + off_idx), (uint32_t)nout,
                        (uint8_t*)c->sch_scalars[0].p);

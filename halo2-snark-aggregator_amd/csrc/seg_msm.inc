@@ -1,5 +1,5 @@
 // Segmented multi_exp, host side (included into h2agg.hip: shares the context internals; kernels in seg_msm_kernels.hpp):
-// h2agg_g1_msm_segmented and the 2N-side evaluation of h2agg_verify_proofs.
+// seg_msm_run and h2agg_g1_msm_segmented.  (Its other caller, the 2N-side evaluation of h2agg_verify_proofs: schema_api.inc.)
 
 namespace {
 
@@ -63,154 +63,9 @@ int seg_msm_run(h2agg_ctx* c, const uint8_t* d_bases, const uint8_t* d_scalars, 
 }
 
 bool fr_bytes_canonical(const uint8_t* b) {   // little-endian integer < r
-    static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-    for (int i = 3; i >= 0; --i) {
-        uint64_t w;
-        memcpy(&w, b + 8 * i, 8);
-        if (w != R[i]) return w < R[i];
-    }
-    return false;
-}
-
-// evaluate_multiopen_proof (verify.rs:690-745) for many (w_x, w_g) pairs of one schema at once: every side's eval_prepare walk
-// recorded on the tape, ONE tape run, the 2N multi_exps as ONE segmented multi_exp (the (G, +/- e) pair folded into each side
-// as in eval_launch_sides), the scalar-less points, and one field inversion for all sides (Montgomery's trick).
-// out_aff: 128 B per pair (left, right), canonical affine.
-int evaluate_multiopen_many(h2agg_schema* sc, const std::vector<std::pair<uint32_t, uint32_t>>& roots, uint8_t* out_aff) {
-    h2agg_ctx* c = sc->ctx;
-    Schema& S = sc->s;
-    Tape& t = S.tape;
-    const size_t nsides = 2 * roots.size();
-    std::vector<EvalLists> L(nsides);
-    std::vector<int64_t> extra(nsides, -1);
-    std::vector<uint32_t> names;
-    for (size_t p = 0; p < roots.size(); ++p) TRY(multiopen_lists(sc, roots[p].first, roots[p].second, &L[2 * p], &extra[2 * p], names));
-    // ---- the tape is final: its dependency levels
-    const uint32_t nconst = t.nconst, nops = (uint32_t)t.ops.size(), nreg = nconst + nops;
-    std::vector<TapeOp> sorted;
-    std::vector<uint32_t> lstart, cslot;
-    uint32_t maxlevel = 0;
-    bool tape_lds = false;
-    if (nops) {
-        std::vector<TapeOp> ops(nops);
-        for (uint32_t k = 0; k < nops; ++k) {
-            TapeOp o = t.ops[k];
-            o.dst = t.resolve(o.dst);
-            o.a = t.resolve(o.a);
-            if (o.op != TAPE_SQRN) o.b = t.resolve(o.b);   // (SQRN: b is an immediate count, not a register)
-            ops[k] = o;
-        }
-        if (!schedule_levels(ops, nreg, sorted, lstart, maxlevel)) return fail(c, H2AGG_ERR_INVALID, "tape: operand not yet defined");
-        tape_lds = c->dbg_tape_lds && tape_lds_assign(sorted, lstart, nconst, nreg, cslot);
-    }
-    // ---- one staging block: tape, then per side (in side order) the (register, point) pairs, the scalar-less points, and
-    // both segmentations
-    std::vector<uint64_t> seg(nsides + 1, 0);
-    std::vector<uint32_t> seg32(nsides + 1, 0), pseg(nsides + 1, 0);
-    for (size_t s = 0; s < nsides; ++s) {
-        seg[s + 1] = seg[s] + L[s].regs_s.size() + (extra[s] >= 0 ? 1 : 0);
-        pseg[s + 1] = pseg[s] + (uint32_t)(L[s].pts_ns.size() / 64);
-    }
-    const size_t M = seg[nsides], K = pseg[nsides];
-    if (M >= ((size_t)1 << 30)) return fail(c, H2AGG_ERR_INVALID, "too many evaluation pairs");
-    for (size_t s = 0; s <= nsides; ++s) seg32[s] = (uint32_t)seg[s];
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    const size_t off_consts = off;  off = align(off + (size_t)nconst * 32);
-    const size_t off_ops = off;     off = align(off + sorted.size() * sizeof(TapeOp));
-    const size_t off_lvl = off;     off = align(off + lstart.size() * 4);
-    const size_t off_cslot = off;   off = align(off + (tape_lds ? (size_t)nconst * 4 : 0));
-    const size_t off_idx = off;     off = align(off + M * 4);
-    const size_t off_pts = off;     off = align(off + M * 64);
-    const size_t off_pns = off;     off = align(off + K * 64);
-    const size_t off_seg = off;     off = align(off + (nsides + 1) * 4);
-    const size_t off_pseg = off;    off = align(off + (nsides + 1) * 4);
-    const size_t total = off;
-    TRY(ensure_stage(c, total));
-    TRY(ensure(c, c->sch_in, total));
-    TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
-    TRY(ensure(c, c->sch_scalars[0], M * 32 + 32));
-    TRY(ensure(c, c->sch_bases[0], M * 64 + 64));
-    TRY(ensure(c, c->seg_out, nsides * (96 + 128) + 256));
-    uint8_t gen[64] = {0};
-    gen[0] = 1;
-    gen[32] = 2;   // pchip.assign_one = generator (1, 2)   verify.rs:714
-    uint8_t* h = c->h_stage;
-    if (nconst) memcpy(h + off_consts, t.consts.data(), (size_t)nconst * 32);
-    if (!sorted.empty()) memcpy(h + off_ops, sorted.data(), sorted.size() * sizeof(TapeOp));
-    if (!lstart.empty()) memcpy(h + off_lvl, lstart.data(), lstart.size() * 4);
-    if (tape_lds && nconst) memcpy(h + off_cslot, cslot.data(), (size_t)nconst * 4);
-    uint32_t* idx = (uint32_t*)(h + off_idx);
-    for (size_t s = 0; s < nsides; ++s) {
-        const size_t m = L[s].regs_s.size(), o = seg[s];
-        for (size_t i = 0; i < m; ++i) idx[o + i] = t.resolve(L[s].regs_s[i]);
-        memcpy(h + off_pts + 64 * o, L[s].pts_s.data(), m * 64);
-        if (extra[s] >= 0) {
-            idx[o + m] = t.resolve((uint32_t)extra[s]);
-            memcpy(h + off_pts + 64 * (o + m), gen, 64);
-        }
-        if (!L[s].pts_ns.empty()) memcpy(h + off_pns + 64 * (size_t)pseg[s], L[s].pts_ns.data(), L[s].pts_ns.size());
-    }
-    memcpy(h + off_seg, seg32.data(), (nsides + 1) * 4);
-    memcpy(h + off_pseg, pseg.data(), (nsides + 1) * 4);
-    hipStream_t st = c->stream;
-    uint8_t* d = (uint8_t*)c->sch_in.p;
-    TRY(clear_flags(c));
-    HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
-    if (tape_lds) {   // constants + every level in one launch, the register file in LDS (schema.hpp)
-        hipLaunchKernelGGL(k_tape_run_lds, dim3(1), dim3(TAPE_THREADS), 0, st, (const uint8_t*)(d + off_consts),
-                           (const uint32_t*)(d + off_cslot), nconst, (const TapeOp*)(d + off_ops), (const uint32_t*)(d + off_lvl),
-                           maxlevel, (uint32_t*)c->sch_regs.p, c->d_flags);
-    } else {
-        if (nconst)
-            hipLaunchKernelGGL(k_tape_load_consts, dim3((nconst + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st,
-                               (const uint8_t*)(d + off_consts), nconst, (uint32_t*)c->sch_regs.p, c->d_flags);
-        if (nops)
-            hipLaunchKernelGGL(k_tape_run, dim3(1), dim3(TAPE_THREADS), 0, st, (const TapeOp*)(d + off_ops),
-                               (const uint32_t*)(d + off_lvl), maxlevel, (uint32_t*)c->sch_regs.p, c->d_flags);
-    }
-    c->sch_owner = sc;
-    sc->tape_done_ops = nops;
-    sc->tape_done_consts = nconst;
-    // gather + Montgomery form of every side's pairs in one launch, then the segmented multi_exp
-    hipLaunchKernelGGL(k_eval_prep<false>, dim3((unsigned)((M + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, (const uint32_t*)c->sch_regs.p,
-                       (const uint32_t*)(d + off_idx), (const uint8_t*)(d + off_pts), (uint32_t)M, (uint8_t*)c->sch_scalars[0].p,
-                       (uint8_t*)c->sch_bases[0].p, (uint8_t*)nullptr, c->d_flags);
-    uint8_t* d_jac = (uint8_t*)c->seg_out.p;
-    uint8_t* d_tail = d_jac + 96 * nsides;
-    TRY(seg_msm_run(c, (const uint8_t*)c->sch_bases[0].p, (const uint8_t*)c->sch_scalars[0].p, seg.data(), nsides,
-                    (const uint32_t*)(d + off_seg), d_jac));
-    TRY(join_tails(c));
-    hipLaunchKernelGGL(k_seg_tail, dim3((unsigned)nsides), dim3(64), 0, st, (const uint8_t*)d_jac, (const uint8_t*)(d + off_pns),
-                       (const uint32_t*)(d + off_pseg), d_tail, c->d_flags);
-    std::vector<uint8_t> xyzz(nsides * 128);
-    HIP_TRY(c, hipMemcpyAsync(xyzz.data(), d_tail, xyzz.size(), hipMemcpyDeviceToHost, st));
-    TRY(finish(c));
-    S.point_list_len = L[nsides - 1].regs_s.size();
-    S.names = names;
-    // ---- x = X / ZZ, y = Y / ZZZ for every side with ONE inversion
-    namespace pr = h2agg::pairing;
-    std::vector<pr::Fq> X(nsides), Y(nsides), ZZ(nsides), ZZZ(nsides), pre(nsides + 1);
-    std::vector<char> inf(nsides);
-    pre[0] = pr::fq_one();
-    for (size_t s = 0; s < nsides; ++s) {
-        const uint8_t* o = xyzz.data() + 128 * s;
-        if (!pr::fq_from_bytes(o, X[s]) || !pr::fq_from_bytes(o + 32, Y[s]) || !pr::fq_from_bytes(o + 64, ZZ[s]) ||
-            !pr::fq_from_bytes(o + 96, ZZZ[s]))
-            return fail(c, H2AGG_ERR_HIP, "evaluate_multiopen_proof: the device returned a non-canonical coordinate");
-        inf[s] = pr::fq_is_zero(ZZ[s]);
-        pre[s + 1] = inf[s] ? pre[s] : pr::fq_mul(pre[s], pr::fq_mul(ZZ[s], ZZZ[s]));
-    }
-    pr::Fq inv = pr::fq_inv(pre[nsides]);   // 1 / prod(ZZ ZZZ)
-    memset(out_aff, 0, 64 * nsides);        // the identity: zeros (as the device's affine store writes it)
-    for (size_t s = nsides; s-- > 0;) {
-        if (inf[s]) continue;
-        const pr::Fq dinv = pr::fq_mul(inv, pre[s]);                      // 1 / (ZZ_s ZZZ_s)
-        inv = pr::fq_mul(inv, pr::fq_mul(ZZ[s], ZZZ[s]));
-        pr::fq_to_bytes(pr::fq_mul(X[s], pr::fq_mul(dinv, ZZZ[s])), out_aff + 64 * s);        // X / ZZ
-        pr::fq_to_bytes(pr::fq_mul(Y[s], pr::fq_mul(dinv, ZZ[s])), out_aff + 64 * s + 32);   // Y / ZZZ
-    }
-    return H2AGG_OK;
+    uint64_t w[4];
+    memcpy(w, b, 32);
+    return !poseidon_host::geq_mod(w);
 }
 
 }  // namespace

@@ -1293,8 +1293,8 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
     trace.mark("host_prepare");
     if (trace.on) {
         char buf[160];
-        snprintf(buf, sizeof buf, " [tape: %zu ops, %u levels, %u consts, %u live at once: %s]", S.tape.ops.size(), sc->prep.maxlevel,
-                 S.tape.nconst, sc->prep.lds_peak, sc->prep.lds ? "register file in LDS" : "register file in L2");
+        snprintf(buf, sizeof buf, " [tape: %zu ops, %u levels, %u consts, %u live at once: %s]", S.tape.ops.size(), sc->prep.tape.maxlevel,
+                 S.tape.nconst, sc->prep.tape.lds_peak, sc->prep.tape.lds ? "register file in LDS" : "register file in L2");
         trace.line += buf;
     }
     // where the points came from: this call's decompressed proof points / instance commitments (refilled next time) or the

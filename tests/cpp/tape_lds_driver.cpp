@@ -1,19 +1,15 @@
-// CPU check of the LDS register-file allocator of the Fr tape (csrc/schema_api.inc: schedule_levels + tape_lds_assign), which
-// tests/test_tape_lds_alloc.py extracts from the product source into tape_lds_extract.inc next to this file's build.
+// CPU check of the Fr tape's host half (csrc/tape_compile.hpp: schedule_levels + tape_lds_assign, and compile_tape, which the
+// product calls), included from the product's csrc/ as it stands.
 // The kernel (csrc/schema.hpp k_tape_run_lds) is simulated with the semantics the hardware gives it: inside a level every lane
 // reads its operands' slots and writes its result's slot in no particular order, so a slot written in a level must not be read
 // or written by any other operation of that level; between levels there is a barrier.  Values are integers mod 2^61 - 1.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
-namespace h2agg {
-enum : uint32_t { TAPE_MUL = 0, TAPE_ADD = 1, TAPE_SUB = 2, TAPE_INV = 3, TAPE_SQRN = 4 };
-struct TapeOp { uint32_t dst, a, b, op; };
-constexpr uint32_t TAPE_LDS_SLOTS = H2AGG_TAPE_LDS_SLOTS, TAPE_NOSLOT = H2AGG_TAPE_NOSLOT, TAPE_SLOTBIT = 0x80000000u;
-#include "tape_lds_extract.inc"
-}
+#include "tape_compile.hpp"
 using namespace h2agg;
 
 static const uint64_t P = (1ull << 61) - 1;
@@ -66,6 +62,17 @@ static int run(int kind, uint32_t nconst, uint32_t nops, bool expect_fit) {
     if (!schedule_levels(ops, nconst + nops, sorted, lstart, maxlevel)) { printf("schedule_levels refused\n"); return 1; }
     const std::vector<TapeOp> plain = sorted;
     const bool fit = tape_lds_assign(sorted, lstart, nconst, nconst + nops, cslot, &peak);
+    // compile_tape is the two steps above and nothing else: the same tape when it fits, the plain schedule when refused
+    CompiledTape ct;
+    auto same_ops = [](const std::vector<TapeOp>& x, const std::vector<TapeOp>& y) {
+        return x.size() == y.size() && (x.empty() || !memcmp(x.data(), y.data(), x.size() * sizeof(TapeOp)));
+    };
+    if (!compile_tape(ops, nconst, true, ct)) { printf("compile_tape refused\n"); return 1; }
+    if (ct.lds != fit || !same_ops(ct.sorted, fit ? sorted : plain) || ct.lstart != lstart || ct.cslot != cslot ||
+        ct.maxlevel != maxlevel || ct.lds_peak != peak) { printf("kind %d: compile_tape differs from schedule_levels + tape_lds_assign\n", kind); return 1; }
+    CompiledTape l2;
+    if (!compile_tape(ops, nconst, false, l2) || l2.lds || !same_ops(l2.sorted, plain) || l2.lstart != lstart || !l2.cslot.empty() ||
+        l2.maxlevel != maxlevel) { printf("kind %d: compile_tape without the LDS file differs from schedule_levels\n", kind); return 1; }
     if (fit != expect_fit) { printf("kind %d: fit = %d, expected %d (peak %u)\n", kind, (int)fit, (int)expect_fit, peak); return 1; }
     if (!fit) {
         for (size_t i = 0; i < sorted.size(); ++i)

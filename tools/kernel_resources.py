@@ -53,7 +53,6 @@ SCRATCH_ALLOWED = {
     "k_part_scatter_staged": (36, 0, "stack"),
     "k_poseidon_transcript": (316, 150, "the device sponge (thousands of proofs): a 9-word state x 9 limbs per lane at one wave per SIMD"),
     "k_small_sort": (36, 0, "stack"),
-    "k_tape_level": (48, 0, "stack"),
     "k_tape_run": (48, 0, "stack"),
     "k_tape_run_lds": (48, 0, "stack"),
 }
