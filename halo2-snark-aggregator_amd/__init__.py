@@ -122,6 +122,10 @@ def load_library():
         "h2agg_poseidon_squeeze_batch": (i32, [ctxp, u8p, sz, sz, C.POINTER(C.c_uint32), sz, vp]),
         "h2agg_transcript_read_batch": (i32, [ctxp, u8p, sz, sz, C.c_char_p, sz, u8p, sz, u8p, sz, vp, vp]),
         "h2agg_vk_create": (i32, [ctxp, u8p, sz, C.POINTER(C.c_void_p)]),
+        "h2agg_vk_set_transcript": (i32, [C.c_void_p, i32]),
+        "h2agg_hash_transcript_read_batch": (i32, [ctxp, i32, u8p, sz, sz, C.c_char_p, sz, u8p, sz, u8p, sz, vp, vp]),
+        "h2agg_hash_transcript_read_batch_host": (i32, [i32, u8p, sz, sz, C.c_char_p, sz, u8p, sz, u8p, sz, vp, vp, i32]),
+        "h2agg_hash_digest_host": (i32, [i32, u8p, sz, vp]),
         "h2agg_vk_destroy": (None, [C.c_void_p]),
         "h2agg_verify_aggregation": (i32, [ctxp, vp, sz, u8p, u8p, vp, vp, vp, C.POINTER(i32)]),   # see verifier.py
         "h2agg_verify_aggregation_ex": (i32, [ctxp, vp, sz, u8p, u8p, vp, vp, vp, C.POINTER(i32), vp, sz]),
@@ -453,7 +457,8 @@ class H2Agg:
         return (self._lib.h2agg_last_phases(self._ctx) or b"").decode()
 
     def transcript_configure(self, backend: str = "auto"):
-        """which backend runs the Poseidon sponges of this context: "auto" (by batch size), "device", "host" (worker threads)"""
+        """which backend runs the transcripts' hash chains (Poseidon sponges, SHA-256 / Keccak-256) of this context: "auto" (by
+        batch size), "device", "host" (worker threads)"""
         self._check(self._lib.h2agg_transcript_configure(self._ctx, {"auto": 0, "device": 1, "host": 2}[backend]))
 
     def transcript_read_batch(self, proofs: Sequence[bytes], script: str, consts: bytes = b"", ext_points_aff: bytes = b""):
@@ -470,6 +475,16 @@ class H2Agg:
         sb = script.encode()
         self._check(self._lib.h2agg_transcript_read_batch(self._ctx, b"".join(proofs), plen, nproofs, sb, len(sb), consts,
                                                           len(consts) // 32, ext_points_aff, nx, pts, ch))
+        return ([pts.raw[64 * npts * i:64 * npts * (i + 1)] for i in range(nproofs)],
+                [ch.raw[32 * nsq * i:32 * nsq * (i + 1)] for i in range(nproofs)])
+
+    def hash_transcript_read_batch(self, kind: str, proofs: Sequence[bytes], script: str, consts: bytes = b"",
+                                   ext_points_aff: bytes = b""):
+        """ShaRead (transcript/sha.rs) over same-layout proofs, kind "sha256" | "keccak256": points are 64 uncompressed
+        bytes -> (points [proof] bytes, challenges [proof] bytes)"""
+        args, pts, ch, npts, nsq = _hash_transcript_args(kind, proofs, script, consts, ext_points_aff)
+        self._check(self._lib.h2agg_hash_transcript_read_batch(self._ctx, *args, pts, ch))
+        nproofs = len(proofs)
         return ([pts.raw[64 * npts * i:64 * npts * (i + 1)] for i in range(nproofs)],
                 [ch.raw[32 * nsq * i:32 * nsq * (i + 1)] for i in range(nproofs)])
 
@@ -605,6 +620,46 @@ def poseidon_squeeze_batch_host(elems: bytes, nproofs: int, upto: Sequence[int],
     if rc != OK:
         raise H2AggError(rc, "h2agg_poseidon_squeeze_batch_host: " + ("element >= r" if rc == ERR_NONCANONICAL else "invalid arguments"))
     return out.raw[:32 * nproofs * nsq]
+
+
+TRANSCRIPT_KINDS = {"poseidon": 0, "sha256": 1, "keccak256": 2}
+
+
+def _hash_transcript_args(kind, proofs, script, consts, ext_points_aff):
+    nproofs = len(proofs)
+    plen = 64 * script.count("P") + 32 * script.count("S")
+    for p in proofs:
+        _need(p, plen, "proof")
+    npts, nsq, nx = script.count("P"), script.count("Q"), script.count("X")
+    _need(consts, 32 * script.count("C"), "consts")
+    _need(ext_points_aff, 64 * nx * nproofs, "ext_points_aff")
+    pts = C.create_string_buffer(max(64 * npts * nproofs, 1))
+    ch = C.create_string_buffer(max(32 * nsq * nproofs, 1))
+    sb = script.encode()
+    k = TRANSCRIPT_KINDS.get(kind, kind)
+    return (k, b"".join(proofs), plen, nproofs, sb, len(sb), consts, len(consts) // 32, ext_points_aff, nx), pts, ch, npts, nsq
+
+
+def hash_transcript_read_batch_host(kind: str, proofs: Sequence[bytes], script: str, consts: bytes = b"",
+                                    ext_points_aff: bytes = b"", max_threads: int = 0):
+    """the host backend of H2Agg.hash_transcript_read_batch on its own (no context, no device)"""
+    args, pts, ch, npts, nsq = _hash_transcript_args(kind, proofs, script, consts, ext_points_aff)
+    rc = load_library().h2agg_hash_transcript_read_batch_host(*args, pts, ch, max_threads)
+    if rc != OK:
+        what = {ERR_BAD_POINT: "invalid point encoding in proof", ERR_NONCANONICAL: "invalid field element encoding in proof"}
+        raise (BadPoint if rc == ERR_BAD_POINT else H2AggError)(rc, "h2agg_hash_transcript_read_batch_host: " + what.get(rc, "invalid arguments"))
+    nproofs = len(proofs)
+    return ([pts.raw[64 * npts * i:64 * npts * (i + 1)] for i in range(nproofs)],
+            [ch.raw[32 * nsq * i:32 * nsq * (i + 1)] for i in range(nproofs)])
+
+
+def hash_digest_host(kind: str, msg: bytes) -> bytes:
+    """SHA-256 / Keccak-256 of `msg` by the library's own host digests (h2agg_hash_digest_host)"""
+    out = C.create_string_buffer(32)
+    rc = load_library().h2agg_hash_digest_host(TRANSCRIPT_KINDS.get(kind, kind), msg, len(msg), out)
+    if rc != OK:
+        raise H2AggError(rc, "h2agg_hash_digest_host: invalid arguments")
+    return out.raw
 
 
 def host_threads() -> int:

@@ -45,6 +45,8 @@
 #include "poseidon_sponge_host.hpp"
 #include "poseidon_ifma_host.hpp"
 #include "poseidon_kernels.hpp"
+#include "hash_transcript_host.hpp"
+#include "hash_transcript_kernels.hpp"
 
 using namespace h2agg;
 

@@ -507,9 +507,235 @@ int transcript_run(h2agg_ctx* c, const TrLayout& L, const uint8_t* proofs, size_
     return H2AGG_OK;
 }
 
+// ---- the ShaRead family (transcript/sha.rs:23-127): SHA-256 / Keccak-256 over uncompressed points ---------------------------
+// The same scripts, the same TrLayout — with points of 64 bytes (x | y, sha.rs:53-54), items[].dst and upto[] counting 32-bit
+// WORDS of the proof's message stream (a point's block is 24 words, a scalar's 16: sha.rs:94-126) — and the same two device
+// buffers downstream: c->tr_points, c->tr_chal.  c->tr_elems holds the message streams, word-interleaved over groups of 64
+// proofs (csrc/hash_transcript_kernels.hpp).
+bool hash_kind_ok(int kind) { return kind == H2AGG_TRANSCRIPT_KIND_SHA256 || kind == H2AGG_TRANSCRIPT_KIND_KECCAK256; }
+bool parse_script_hash(const char* script, size_t n, TrLayout& L) {
+    for (size_t i = 0; i < n; ++i) {
+        TrItem it{0, 0, L.nelem, 0};
+        switch (script[i]) {
+        case 'P':
+            it.kind = TR_POINT;
+            it.src = (uint32_t)L.proof_len;
+            it.pidx = L.npoints++;
+            L.proof_len += 64;
+            L.nelem += 24;
+            break;
+        case 'S':
+            it.kind = TR_SCALAR;
+            it.src = (uint32_t)L.proof_len;
+            L.nscalars++;
+            L.proof_len += 32;
+            L.nelem += 16;
+            break;
+        case 'C':
+            it.kind = TR_CONST;
+            it.src = L.nconsts++;
+            L.nelem += 16;
+            break;
+        case 'X':
+            it.kind = TR_POINT_EXT;
+            it.src = L.next++;
+            L.nelem += 24;
+            break;
+        case 'Q':
+            L.upto.push_back(L.nelem);
+            continue;
+        default:
+            return false;
+        }
+        L.items.push_back(it);
+    }
+    return true;
+}
+size_t hash_stream_bytes(const TrLayout& L, size_t nproofs) {   // whole groups of 64 proofs: the chain's idle lanes read too
+    const size_t groups = (nproofs + HT_LANES - 1) / HT_LANES;
+    return groups * HT_LANES * (size_t)(L.nelem ? L.nelem : 1) * 4;
+}
+// Which backend runs the chains of `nproofs` hash transcripts: 1 = device, 2 = host threads.  Forced as for Poseidon
+// (h2agg_transcript_configure, H2AGG_TRANSCRIPT).  auto: one lane walks one transcript serially, so the device only pays with
+// thousands of proofs in flight; measured (profiles/hash_transcript.txt) the host pool is ahead up to HASH_DEVICE_FROM proofs.
+constexpr size_t HASH_DEVICE_FROM = (size_t)1 << 62;   // not reached: auto = host (DESIGN.md 5.4)
+int hash_backend(const h2agg_ctx* c, size_t nproofs) {
+    int cfg = c->cfg_transcript;
+    if (cfg == 0) {
+        const char* e = getenv("H2AGG_TRANSCRIPT");
+        cfg = !e ? 0 : !strcmp(e, "device") ? 1 : !strcmp(e, "host") ? 2 : 0;
+    }
+    if (cfg == 1 || cfg == 2) return cfg;
+    return nproofs >= HASH_DEVICE_FROM ? 1 : 2;
+}
+void hash_stream_launch(h2agg_ctx* c, const TrLayout& L, const TrBlock& b, size_t nproofs, const uint8_t* d_ext_points,
+                        hipStream_t st, int which) {
+    uint8_t* d = (uint8_t*)c->tr_in.p;
+    const size_t work = nproofs * L.items.size();
+    if (!work) return;
+    hipLaunchKernelGGL(k_hash_transcript_stream, dim3(grid_for(c, work)), dim3(BLOCK), 0, st, (const uint8_t*)(d + b.hdr3),
+                       L.proof_len, d_ext_points, L.next, (const uint8_t*)(d + b.hdr2), (const TrItem*)d, (uint32_t)L.items.size(),
+                       (uint32_t)nproofs, L.npoints, (uint8_t*)c->tr_points.p, (uint32_t*)c->tr_elems.p, L.nelem, c->d_flags, which);
+}
+// stage + upload layout and proof bytes, then everything that needs the proof bytes only (the early half, on `st`)
+int hash_transcript_begin(h2agg_ctx* c, const TrLayout& L, const TrBlock& b, const uint8_t* const* proofs, const uint8_t* flat,
+                          size_t nproofs, const uint8_t* consts, hipStream_t st) {
+    TRY(ensure(c, c->tr_in, b.total));
+    TRY(ensure(c, c->tr_points, nproofs * (size_t)(L.npoints ? L.npoints : 1) * 64));
+    TRY(ensure(c, c->tr_elems, hash_stream_bytes(L, nproofs)));
+    TRY(ensure(c, c->tr_chal, nproofs * (b.nsq ? b.nsq : 1) * 32));
+    uint8_t* h = c->h_stage;
+    memcpy(h, L.items.data(), L.items.size() * sizeof(TrItem));
+    if (b.nsq) memcpy(h + b.hdr, L.upto.data(), b.nsq * 4);
+    if (L.nconsts) memcpy(h + b.hdr2, consts, (size_t)L.nconsts * 32);
+    if (flat) memcpy(h + b.hdr3, flat, nproofs * L.proof_len);
+    else
+        for (size_t i = 0; i < nproofs; ++i) memcpy(h + b.hdr3 + i * L.proof_len, proofs[i], L.proof_len);
+    HIP_TRY(c, hipMemcpyAsync(c->tr_in.p, h, b.total, hipMemcpyHostToDevice, st));
+    hash_stream_launch(c, L, b, nproofs, nullptr, st, 1);
+    return H2AGG_OK;
+}
+// the chains over the finished message streams, on the context's stream.  Device: challenges to c->tr_chal.  Host
+// (host_chal != nullptr): the streams come down, one proof per job on the pool, challenges [nproofs][nsq][32] to host_chal;
+// the stream is synchronised on return.
+int hash_chain_run(h2agg_ctx* c, int kind, const TrLayout& L, const TrBlock& b, size_t nproofs, uint8_t* host_chal) {
+    if (!b.nsq) return H2AGG_OK;
+    if (!host_chal) {
+        const uint32_t* d_upto = (const uint32_t*)((const uint8_t*)c->tr_in.p + b.hdr);
+        const dim3 grid((unsigned)((nproofs + HT_LANES - 1) / HT_LANES));
+        if (kind == H2AGG_TRANSCRIPT_KIND_SHA256)
+            hipLaunchKernelGGL(k_hash_transcript_chain<HT_SHA256>, grid, dim3(HT_LANES), 0, c->stream, (const uint32_t*)c->tr_elems.p,
+                               L.nelem, d_upto, (uint32_t)b.nsq, (uint32_t)nproofs, (uint8_t*)c->tr_chal.p);
+        else
+            hipLaunchKernelGGL(k_hash_transcript_chain<HT_KECCAK256>, grid, dim3(HT_LANES), 0, c->stream, (const uint32_t*)c->tr_elems.p,
+                               L.nelem, d_upto, (uint32_t)b.nsq, (uint32_t)nproofs, (uint8_t*)c->tr_chal.p);
+        return H2AGG_OK;
+    }
+    std::vector<uint8_t>& he = c->h_elems;
+    he.resize(hash_stream_bytes(L, nproofs));
+    HIP_TRY(c, hipMemcpyAsync(he.data(), c->tr_elems.p, he.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    trace_mark("tr_elements");
+    std::vector<uint32_t> seg_bytes(L.upto);
+    for (uint32_t& v : seg_bytes) v *= 4;
+    const uint32_t* msg = (const uint32_t*)he.data();
+    const uint32_t nwords = L.nelem, nsq = (uint32_t)b.nsq;
+    const int hk = kind == H2AGG_TRANSCRIPT_KIND_SHA256 ? hash_host::KIND_SHA256 : hash_host::KIND_KECCAK256;
+    HostPool::get().run(nproofs, 1 << 30, [&](size_t p) {
+        hash_host::chain_run(hk, msg + ((p / HT_LANES) * nwords) * HT_LANES + p % HT_LANES, HT_LANES, seg_bytes.data(), nsq,
+                             host_chal + 32 * (size_t)nsq * p);
+    });
+    trace_mark("tr_host_chain");
+    return H2AGG_OK;
+}
+
+// the whole of a ShaRead batch on host threads (no device): checks, blocks, chains.  -> FLAG_* bits
+uint32_t hash_transcript_host(int kind, const TrLayout& L, const uint8_t* proofs, size_t nproofs, const uint8_t* consts,
+                              const uint8_t* ext, uint8_t* points_out, uint8_t* chal_out, int max_threads) {
+    std::atomic<uint32_t> flags{0};
+    std::vector<uint32_t> seg_bytes(L.upto);
+    for (uint32_t& v : seg_bytes) v *= 4;
+    const int hk = kind == H2AGG_TRANSCRIPT_KIND_SHA256 ? hash_host::KIND_SHA256 : hash_host::KIND_KECCAK256;
+    HostPool::get().run(nproofs, max_threads, [&](size_t p) {
+        std::vector<uint32_t> msg((size_t)L.nelem + 1);
+        uint8_t* m = (uint8_t*)msg.data();
+        const uint8_t* proof = proofs + p * L.proof_len;
+        uint32_t f = 0;
+        for (const TrItem& it : L.items) {
+            uint8_t* dst = m + 4 * (size_t)it.dst;
+            if (it.kind == TR_CONST || it.kind == TR_SCALAR) {
+                const uint8_t* s = it.kind == TR_CONST ? consts + 32 * (size_t)it.src : proof + it.src;
+                if (!hash_host::scalar_ok(s)) f |= FLAG_NONCANONICAL;
+                hash_host::block_scalar(dst, s);
+            } else {
+                const uint8_t* xy = it.kind == TR_POINT_EXT ? ext + 64 * (p * L.next + it.src) : proof + it.src;
+                const bool good = hash_host::point_ok(xy);
+                if (!good) f |= FLAG_BAD_POINT;
+                if (it.kind == TR_POINT) {
+                    uint8_t* po = points_out + 64 * (p * L.npoints + it.pidx);
+                    if (good) memcpy(po, xy, 64);
+                    else memset(po, 0, 64);
+                }
+                hash_host::block_point(dst, xy);
+            }
+        }
+        if (!L.upto.empty())
+            hash_host::chain_run(hk, msg.data(), 1, seg_bytes.data(), (uint32_t)L.upto.size(), chal_out + 32 * L.upto.size() * p);
+        if (f) flags.fetch_or(f, std::memory_order_relaxed);
+    });
+    return flags.load();
+}
+
 }  // namespace
 
 extern "C" {
+
+int h2agg_hash_transcript_read_batch(h2agg_ctx* c, int kind, const uint8_t* proofs, size_t proof_len, size_t nproofs,
+                                     const char* script, size_t script_len, const uint8_t* consts, size_t nconsts,
+                                     const uint8_t* ext_points_aff, size_t next, uint8_t* points_out, uint8_t* challenges_out) try {
+    TRY(bind(c));
+    if (!hash_kind_ok(kind)) return fail(c, H2AGG_ERR_INVALID, "transcript kind must be H2AGG_TRANSCRIPT_KIND_SHA256 or _KECCAK256");
+    if (!script) return fail(c, H2AGG_ERR_INVALID, "null script");
+    TrLayout L;
+    if (!parse_script_hash(script, script_len, L)) return fail(c, H2AGG_ERR_INVALID, "script: unknown operation (P S Q C X)");
+    if (L.proof_len != proof_len)
+        return fail(c, H2AGG_ERR_INVALID, "proof length does not match the script: 64 bytes per point, 32 per scalar (read_exact would fail: sha.rs:46,65)");
+    if (L.nconsts != nconsts || L.next != next) return fail(c, H2AGG_ERR_INVALID, "script uses a different number of constants / external points");
+    if (nproofs == 0) return H2AGG_OK;
+    if ((proof_len && !proofs) || (nconsts && !consts) || (next && !ext_points_aff) || (L.npoints && !points_out) ||
+        (!L.upto.empty() && !challenges_out))
+        return fail(c, H2AGG_ERR_INVALID, "null buffer");
+    const uint8_t* d_ext = nullptr;
+    if (next) {
+        TRY(ensure(c, c->in_c, nproofs * next * 64));
+        HIP_TRY(c, hipMemcpyAsync(c->in_c.p, ext_points_aff, nproofs * next * 64, hipMemcpyHostToDevice, c->stream));
+        d_ext = (const uint8_t*)c->in_c.p;
+    }
+    TRY(clear_flags(c));
+    const TrBlock b = transcript_block(L, nproofs);
+    TRY(ensure_stage(c, b.total));
+    TRY(hash_transcript_begin(c, L, b, nullptr, proofs, nproofs, consts, c->stream));
+    if (next) hash_stream_launch(c, L, b, nproofs, d_ext, c->stream, 2);
+    const bool host = hash_backend(c, nproofs) == 2;
+    TRY(hash_chain_run(c, kind, L, b, nproofs, host ? challenges_out : nullptr));
+    if (L.npoints)
+        HIP_TRY(c, hipMemcpyAsync(points_out, c->tr_points.p, nproofs * (size_t)L.npoints * 64, hipMemcpyDeviceToHost, c->stream));
+    if (!L.upto.empty() && !host)
+        HIP_TRY(c, hipMemcpyAsync(challenges_out, c->tr_chal.p, nproofs * L.upto.size() * 32, hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+} catch (const std::bad_alloc&) {
+    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
+} catch (...) {
+    return H2AGG_ERR_INVALID;
+}
+
+// the host backend on its own: no context, no device (CPU-testable), like h2agg_poseidon_squeeze_batch_host
+int h2agg_hash_transcript_read_batch_host(int kind, const uint8_t* proofs, size_t proof_len, size_t nproofs, const char* script,
+                                          size_t script_len, const uint8_t* consts, size_t nconsts, const uint8_t* ext_points_aff,
+                                          size_t next, uint8_t* points_out, uint8_t* challenges_out, int max_threads) try {
+    if (!hash_kind_ok(kind) || !script) return H2AGG_ERR_INVALID;
+    TrLayout L;
+    if (!parse_script_hash(script, script_len, L)) return H2AGG_ERR_INVALID;
+    if (L.proof_len != proof_len || L.nconsts != nconsts || L.next != next) return H2AGG_ERR_INVALID;
+    if (nproofs == 0) return H2AGG_OK;
+    if ((proof_len && !proofs) || (nconsts && !consts) || (next && !ext_points_aff) || (L.npoints && !points_out) ||
+        (!L.upto.empty() && !challenges_out))
+        return H2AGG_ERR_INVALID;
+    const uint32_t f = hash_transcript_host(kind, L, proofs, nproofs, consts, ext_points_aff, points_out, challenges_out,
+                                            max_threads > 0 ? max_threads : 1 << 30);
+    // (the order of flags_to_status)
+    return (f & FLAG_NONCANONICAL) ? H2AGG_ERR_NONCANONICAL : (f & FLAG_BAD_POINT) ? H2AGG_ERR_BAD_POINT : H2AGG_OK;
+} catch (const std::bad_alloc&) {
+    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
+} catch (...) {
+    return H2AGG_ERR_INVALID;
+}
+
+int h2agg_hash_digest_host(int kind, const uint8_t* msg, size_t len, uint8_t out[32]) {
+    if (!hash_kind_ok(kind) || (len && !msg) || !out) return H2AGG_ERR_INVALID;
+    return hash_host::digest(kind == H2AGG_TRANSCRIPT_KIND_SHA256 ? hash_host::KIND_SHA256 : hash_host::KIND_KECCAK256, msg, len, out)
+               ? H2AGG_OK : H2AGG_ERR_INVALID;
+}
 
 int h2agg_poseidon_squeeze_batch(h2agg_ctx* c, const uint8_t* elems, size_t nproofs, size_t nelem, const uint32_t* upto,
                                  size_t nsq, uint8_t* out) try {

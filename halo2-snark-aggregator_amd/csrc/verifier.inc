@@ -39,6 +39,7 @@ struct h2agg_vk {
     std::vector<PermCol> perm_cols;
     std::vector<uint8_t> fixed_commitments, perm_commitments;   // 64 B each
     uint8_t vk_scalar[32] = {0};
+    int transcript_kind = H2AGG_TRANSCRIPT_KIND_POSEIDON;   // how the key's proofs are written (h2agg_vk_set_transcript)
     typedef std::vector<uint8_t> Expr;   // postfix bytecode
     std::vector<std::vector<Expr>> gates;
     struct Lookup {
@@ -298,11 +299,20 @@ std::string proof_script(const h2agg_vk& vk, size_t n_w) {
     s += 'Q';                                                                  // the per-proof squeeze of verify.rs:910-913
     return s;
 }
-size_t script_fixed_items(const h2agg_vk& vk) {   // proof items other than the W points
+// bytes of a proof point on the wire: 32 compressed (transcript.rs:63-70), 64 as x | y under ShaRead (sha.rs:53-54)
+size_t proof_point_bytes(const h2agg_vk& vk) { return vk.transcript_kind == H2AGG_TRANSCRIPT_KIND_POSEIDON ? 32 : 64; }
+size_t script_fixed_bytes(const h2agg_vk& vk) {   // proof bytes other than the W points
     const std::string s = proof_script(vk, 0);
     size_t n = 0;
-    for (char ch : s) n += (ch == 'P' || ch == 'S');
+    for (char ch : s) n += ch == 'P' ? proof_point_bytes(vk) : ch == 'S' ? 32 : 0;
     return n;
+}
+// does a proof of `plen` bytes fit the key?  The W points are whatever is left (verify.rs:487-490).
+bool proof_len_fits(const h2agg_vk& vk, size_t plen, size_t* n_w) {
+    const size_t fixed = script_fixed_bytes(vk), pt = proof_point_bytes(vk);
+    if (plen % 32 != 0 || plen < fixed || (plen - fixed) % pt != 0) return false;
+    if (n_w) *n_w = (plen - fixed) / pt;
+    return true;
 }
 
 }  // namespace
@@ -436,6 +446,14 @@ int h2agg_vk_create(h2agg_ctx* c, const uint8_t* blob, size_t len, h2agg_vk** ou
 }
 
 void h2agg_vk_destroy(h2agg_vk* vk) { delete vk; }
+
+int h2agg_vk_set_transcript(h2agg_vk* vk, int kind) {
+    if (!vk) return H2AGG_ERR_INVALID;
+    if (kind != H2AGG_TRANSCRIPT_KIND_POSEIDON && kind != H2AGG_TRANSCRIPT_KIND_SHA256 && kind != H2AGG_TRANSCRIPT_KIND_KECCAK256)
+        return fail(vk->ctx, H2AGG_ERR_INVALID, "unknown transcript kind (H2AGG_TRANSCRIPT_KIND_*)");
+    vk->transcript_kind = kind;
+    return H2AGG_OK;
+}
 
 }  // extern "C"
 
@@ -791,6 +809,10 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
     if (pairing_ok) *pairing_ok = 0;
     memset(left_aff, 0, 64);
     memset(right_aff, 0, 64);
+    if (!each)   // the reference never folds ShaRead proofs under an aggregation transcript (include/h2agg.h)
+        for (size_t ci = 0; ci < ncircuits; ++ci)
+            if (circuits[ci].vk && circuits[ci].vk->transcript_kind != H2AGG_TRANSCRIPT_KIND_POSEIDON)
+                return fail(c, H2AGG_ERR_INVALID, "aggregation of proofs written with the SHA-256 / Keccak-256 transcript is not supported: verify them with h2agg_verify_proofs");
     PhaseTrace trace(c->dbg_phases ? &c->last_phases : nullptr);
     struct TraceScope {
         explicit TraceScope(PhaseTrace* t) { g_trace = t; }
@@ -874,6 +896,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         const uint8_t* elems_p = nullptr;              // ... where they are (the vector, or the context's page-locked block)
         std::vector<uint32_t> upto;                    // squeeze positions of the layout
         size_t npoints = 0, nsq = 0, n_w = 0, elem_stride = 0, first_proof = 0;
+        bool hashed = false;                           // a ShaRead circuit: its challenges are in `chal` when its turn ends
         std::string script;
     };
     std::vector<CircuitHost> H(ncircuits);
@@ -911,14 +934,14 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         for (size_t i = 0; i < cp.nproofs; ++i)
             if (cp.transcript_lens[i] != plen || !cp.transcripts[i])
                 return fail(c, H2AGG_ERR_INVALID, "proofs of one circuit must have one length");
-        const size_t fixed_items = script_fixed_items(vk);
-        if (plen % 32 != 0 || plen / 32 < fixed_items)
-            return fail(c, H2AGG_ERR_INVALID, "proof too short for this verifying key (read_exact fails: transcript.rs:63,101)");
         CircuitHost& h = H[ci];
-        h.n_w = plen / 32 - fixed_items;
+        if (!proof_len_fits(vk, plen, &h.n_w))
+            return fail(c, H2AGG_ERR_INVALID, "proof too short for this verifying key (read_exact fails: transcript.rs:63,101; sha.rs:46,65)");
+        h.hashed = vk.transcript_kind != H2AGG_TRANSCRIPT_KIND_POSEIDON;
         h.script = proof_script(vk, h.n_w);
         TrLayout L;
-        parse_script(h.script.data(), h.script.size(), L);
+        if (h.hashed) parse_script_hash(h.script.data(), h.script.size(), L);
+        else parse_script(h.script.data(), h.script.size(), L);
         h.npoints = L.npoints;
         h.nsq = L.upto.size();
         h.upto = L.upto;
@@ -954,7 +977,8 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         HIP_TRY(c, hipEventRecord(c->ev_aux_go, c->stream));                 // (the previous users of tr_* are behind us)
         HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_aux_go, 0));
         chaos_wait(8, c->aux_stream);
-        TRY(transcript_begin(c, L, tb, cp.transcripts, cp.nproofs, vk.vk_scalar, c->aux_stream, 0));
+        if (h.hashed) TRY(hash_transcript_begin(c, L, tb, cp.transcripts, nullptr, cp.nproofs, vk.vk_scalar, c->aux_stream));
+        else TRY(transcript_begin(c, L, tb, cp.transcripts, cp.nproofs, vk.vk_scalar, c->aux_stream, 0));
         HIP_TRY(c, hipEventRecord(c->ev_aux, c->aux_stream));
         trace.mark("tr_begin");
         if (ncol) {
@@ -1010,6 +1034,20 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         h.chal.resize(cp.nproofs * h.nsq * 32);
         h.inst_aff.resize(cp.nproofs * ncol * 64 + 1);
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_aux, 0));
+        if (h.hashed) {
+            // ShaRead: no square roots and no sponge — the on-curve checks and the message streams are done; the chains run now
+            // (device or host threads, csrc/transcript.inc hash_backend) and this circuit's challenges are complete when its
+            // turn ends
+            if (L.next) hash_stream_launch(c, L, tb, cp.nproofs, (const uint8_t*)c->inst_aff.p, c->stream, 2);
+            const bool chain_host = hash_backend(c, cp.nproofs) == 2;
+            TRY(hash_chain_run(c, vk.transcript_kind, L, tb, cp.nproofs, chain_host ? h.chal.data() : nullptr));
+            if (!chain_host && !h.chal.empty())
+                HIP_TRY(c, hipMemcpyAsync(h.chal.data(), c->tr_chal.p, h.chal.size(), hipMemcpyDeviceToHost, c->stream));
+            if (!h.points.empty()) HIP_TRY(c, hipMemcpyAsync(h.points.data(), c->tr_points.p, h.points.size(), hipMemcpyDeviceToHost, c->stream));
+            if (ncol) HIP_TRY(c, hipMemcpyAsync(h.inst_aff.data(), c->inst_aff.p, cp.nproofs * ncol * 64, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));   // tr_* and the staging block are reused by the next circuit
+            trace.mark("hash_transcripts");
+        } else {
         if (L.next) transcript_elements_launch(c, L, tb, cp.nproofs, (const uint8_t*)c->inst_aff.p, c->stream, 2);
         // host backend: only the element streams are made on the device (point decompression + PoseidonEncode); the sponges run
         // on worker threads further down, UNDER the recording of the schema their challenges feed
@@ -1048,6 +1086,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // tr_* and the staging block are reused by the next circuit
         trace.mark(host_sponge ? "tr_elements" : "transcripts");
+        }   // (Poseidon)
         if (advice_out) {   // the proof's advice commitments = its first num_advice 'P' items, column order restored
             size_t pi = 0;
             std::vector<uint32_t> advice_pt(vk.num_advice);
@@ -1074,7 +1113,7 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
     } pool_scope;
     if (host_sponge) {
         for (size_t ci = 0; ci < ncircuits; ++ci)
-            for (size_t i = 0; i < circuits[ci].nproofs; ++i) job_of.push_back({ci, i});
+            for (size_t i = 0; i < circuits[ci].nproofs && !H[ci].hashed; ++i) job_of.push_back({ci, i});
         const poseidon_host::FastSpec* fs = &poseidon_fast_spec();
         const void* ic_any = nullptr;   // (captured by VALUE: the workers run after this block is left)
 #ifdef H2AGG_HAVE_IFMA_BUILD
@@ -1192,12 +1231,12 @@ static int verify_aggregation_impl(h2agg_ctx* c, const h2agg_circuit_proofs* cir
             // scalars of the proof, in reading order
             size_t soff = 0;
             {
-                size_t before = 0;   // byte offset of the first scalar = 32 * (#P before the evals)
+                size_t before = 0;   // byte offset of the first scalar = point bytes * (#P before the evals)
                 for (char ch : h.script) {
                     if (ch == 'S') break;
                     if (ch == 'P') ++before;
                 }
-                soff = 32 * before;
+                soff = proof_point_bytes(vk) * before;
             }
             auto next_scalar = [&] {   // (a register of its own, whatever its value: see AggPlan)
                 const uint32_t r = S.tape.add_const_placeholder();
@@ -1516,12 +1555,11 @@ int h2agg_verify_proofs(h2agg_ctx* c, const h2agg_circuit_proofs* circuits, size
             const h2agg_circuit_proofs& cp = circuits[ci];
             if (cp.nproofs == 0) continue;
             const h2agg_vk& vk = *cp.vk;
-            const size_t fixed_items = script_fixed_items(vk);
             const uint64_t max_len = ((uint64_t)1 << vk.k) - (vk.blinding_factors + 1);
             const size_t table_n = vk.num_instance ? c->tables.find(cp.g_lagrange)->second.n : 0;
             for (size_t i = 0; i < cp.nproofs; ++i, ++g) {
                 const size_t plen = cp.transcript_lens[i];
-                bool bad = plen % 32 != 0 || plen / 32 < fixed_items;
+                bool bad = !proof_len_fits(vk, plen, nullptr);
                 for (size_t col = 0; col < vk.num_instance; ++col) {
                     const uint32_t l = cp.instance_lens[i * vk.num_instance + col];
                     if (l > max_len || l > table_n) bad = true;

@@ -170,3 +170,30 @@ def pairing_g2(eng, params: KzgParams):
     """(s_g2, g2) in the 128-byte affine form of h2agg_final_pair_check / h2agg_verify_aggregation"""
     both = eng.g2_batch_decompress(params.s_g2 + params.g2)
     return both[:128], both[128:]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The OUTER proof (halo2-snark-aggregator-circuit/src/fs.rs:110-135, verify_circuit.rs:985, :1032-1055): written with
+# ShaWrite<_, _, _, sha2::Sha256> next to verify_circuit_instance.data; `verify_check` reads both and verifies the proof.
+
+def load_verify_circuit_proof(folder: str) -> bytes:
+    """verify_circuit_proof.data: the outer proof's transcript bytes (points as 64 uncompressed bytes, transcript/sha.rs)"""
+    return open(os.path.join(folder, "verify_circuit_proof.data"), "rb").read()
+
+
+def load_verify_circuit_instance(folder: str) -> List[List[bytes]]:
+    return load_instances(open(os.path.join(folder, "verify_circuit_instance.data"), "rb").read())
+
+
+def verify_check(eng, folder: str, vk, g_lagrange_handle: int, s_g2: bytes, g2: bytes, transcript: str = "sha256") -> bool:
+    """VerifyCheck::call (verify_circuit.rs:1032-1055): read verify_circuit_instance.data (one column) and
+    verify_circuit_proof.data, verify that one proof (one verify_proofs call), return the verdict.  `vk`: the outer circuit's
+    VerifyingKey made with the same `transcript`; s_g2 / g2 as pairing_g2() returns them."""
+    from . import verifier
+    if vk.transcript != transcript:
+        raise ValueError("the verifying key reads %s proofs, not %s" % (vk.transcript, transcript))
+    columns = load_verify_circuit_instance(folder)
+    proof = load_verify_circuit_proof(folder)
+    rec = verifier.verify_proofs(eng, [(vk, "verify_circuit", g_lagrange_handle, [([b"".join(col) for col in columns], proof)])],
+                                 s_g2, g2)[0]
+    return rec[2] == 0 and rec[3] is True

@@ -278,6 +278,8 @@ pub mod aggregate {
         fn h2agg_instance_commitment(ctx: *mut h2agg_ctx, g_lagrange: u64, instance: *const u8, len: usize, max_len: usize, out_jac: *mut u8) -> c_int;
         fn h2agg_vk_create(ctx: *mut h2agg_ctx, blob: *const u8, len: usize, out: *mut *mut h2agg_vk) -> c_int;
         fn h2agg_vk_destroy(vk: *mut h2agg_vk);
+        /// 0 = Poseidon (default), 1 = ShaRead over SHA-256 (the outer proof), 2 = over Keccak-256; h2agg_verify_proofs only
+        pub fn h2agg_vk_set_transcript(vk: *mut h2agg_vk, kind: c_int) -> c_int;
         fn h2agg_verify_aggregation(
             ctx: *mut h2agg_ctx, circuits: *const h2agg_circuit_proofs, ncircuits: usize, s_g2: *const u8, g2: *const u8,
             left_aff: *mut u8, right_aff: *mut u8, lambda_out: *mut u8, pairing_ok: *mut c_int,

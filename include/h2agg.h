@@ -297,6 +297,39 @@ int h2agg_host_sponge_kind(void);
 int h2agg_transcript_read_batch(h2agg_ctx* ctx, const uint8_t* proofs, size_t proof_len, size_t nproofs, const char* script,
                                 size_t script_len, const uint8_t* consts, size_t nconsts, const uint8_t* ext_points_aff,
                                 size_t next, uint8_t* points_out, uint8_t* challenges_out);
+/* The second transcript family: ShaRead (halo2-snark-aggregator-api/src/transcript/sha.rs:23-127) over a digest D — SHA-256,
+ * with which the OUTER proof of an aggregation is written and checked (ShaWrite at halo2-snark-aggregator-circuit/src/
+ * verify_circuit.rs:985, VerifyCheck::call :1032-1055), or Keccak-256 (original padding 0x01 .. 0x80, rate 136; NOT SHA3-256),
+ * from which the solidity code generator takes its challenges (halo2-snark-aggregator-solidity/src/transcript/codegen.rs:34,
+ * 196-214).  A key's proofs are written with one transcript: its kind. */
+#define H2AGG_TRANSCRIPT_KIND_POSEIDON 0
+#define H2AGG_TRANSCRIPT_KIND_SHA256 1
+#define H2AGG_TRANSCRIPT_KIND_KECCAK256 2
+/* The ShaRead twin of h2agg_transcript_read_batch: the same scripts (P S Q C X) over `nproofs` proofs of one layout, kind =
+ * H2AGG_TRANSCRIPT_KIND_SHA256 or _KECCAK256 (anything else -> H2AGG_ERR_INVALID).
+ *   'P' read_point (sha.rs:43-61): 64 bytes, x then y, 32-byte little-endian each, uncompressed (no square root); a coordinate
+ *       >= p ("invalid base encoding in proof"), a point off y^2 = x^3 + 3 — (0, 0) included — ("invalid point encoding in
+ *       proof") -> H2AGG_ERR_BAD_POINT;
+ *   'S' read_scalar (sha.rs:63-75): 32 bytes little-endian; >= r -> H2AGG_ERR_NONCANONICAL;
+ *   'X' / 'C' common_point / common_scalar (sha.rs:94-126): absorb 31 zero bytes, 0x01, x and y big-endian (96 bytes) / 31 zero
+ *       bytes, 0x02, the scalar big-endian (64 bytes); an external point that is the identity or not a canonical point of the
+ *       curve ("cannot write points at infinity to the transcript") -> H2AGG_ERR_BAD_POINT;
+ *   'Q' squeeze_challenge (sha.rs:81-92): absorb 0x00, digest = finalize(clone), the state restarts as D(digest), the
+ *       challenge is the digest read as a little-endian integer mod r (Challenge255::new(digest | 32 zero bytes) = Fr::
+ *       from_bytes_wide; halo2_proofs is unvendored in the reference: recalled).
+ * proof_len must equal 64 x #P + 32 x #S (H2AGG_ERR_INVALID otherwise).  points_out: [nproofs][#P] canonical affine (zeros for
+ * a point that was refused); challenges_out: [nproofs][#Q] canonical.  Backend as h2agg_transcript_configure / H2AGG_TRANSCRIPT
+ * say (device: one lane per proof, state in registers; host: one proof per pool thread, portable SHA-256 / Keccak-256 inside
+ * the library) — bit-identical; auto = host.
+ * h2agg_hash_transcript_read_batch_host: the host backend on its own (no context, no device); max_threads 0 = all usable.
+ * h2agg_hash_digest_host: D(msg) of the library's own host digests (what the tests pin against published vectors). */
+int h2agg_hash_transcript_read_batch(h2agg_ctx* ctx, int kind, const uint8_t* proofs, size_t proof_len, size_t nproofs,
+                                     const char* script, size_t script_len, const uint8_t* consts, size_t nconsts,
+                                     const uint8_t* ext_points_aff, size_t next, uint8_t* points_out, uint8_t* challenges_out);
+int h2agg_hash_transcript_read_batch_host(int kind, const uint8_t* proofs, size_t proof_len, size_t nproofs, const char* script,
+                                          size_t script_len, const uint8_t* consts, size_t nconsts, const uint8_t* ext_points_aff,
+                                          size_t next, uint8_t* points_out, uint8_t* challenges_out, int max_threads);
+int h2agg_hash_digest_host(int kind, const uint8_t* msg, size_t len, uint8_t out[32]);
 
 /* ---- verifier-params pipeline + aggregation driver (SURVEY.md 8(f) row 1 and the caller of the hot path) ----------
  * replaces, for the pure-calculation context: VerifierParamsBuilder::build_params (halo2-snark-aggregator-api/src/systems/
@@ -333,6 +366,16 @@ int h2agg_transcript_read_batch(h2agg_ctx* ctx, const uint8_t* proofs, size_t pr
 typedef struct h2agg_vk h2agg_vk;
 int h2agg_vk_create(h2agg_ctx* ctx, const uint8_t* blob, size_t len, h2agg_vk** out);
 void h2agg_vk_destroy(h2agg_vk* vk);
+/* The transcript the key's proofs are written with: H2AGG_TRANSCRIPT_KIND_POSEIDON (the default: every existing caller is
+ * unchanged), _SHA256 or _KECCAK256 (ShaRead, sha.rs:23-127; above).  h2agg_verify_proofs honours it per circuit — one call
+ * may mix kinds: proof points are 64 uncompressed bytes (sha.rs:53-54), so the length checks and the W count use 64-byte
+ * points, the on-curve check replaces point decompression, and status / pairing_ok / advice_out work as for Poseidon (a
+ * Poseidon-written proof under a SHA key does not fit the key's length: H2AGG_ERR_INVALID for that proof; an instance column
+ * without values commits to the identity, which ShaRead refuses: H2AGG_ERR_BAD_POINT for that proof).
+ * h2agg_verify_aggregation, _ex and _sharded return H2AGG_ERR_INVALID before any work when a key's kind is not Poseidon:
+ * the reference never folds ShaRead proofs under an aggregation transcript (the outer proof is checked on its own,
+ * verify_circuit.rs:1032-1055) — out of scope here. */
+int h2agg_vk_set_transcript(h2agg_vk* vk, int kind);
 typedef struct {
     const h2agg_vk* vk;
     const char* name;

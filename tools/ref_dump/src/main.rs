@@ -188,7 +188,27 @@ fn dump_primitives(out_dir: &PathBuf) {
     // encodings
     let g = G1::generator();
     let samples: Vec<(String, G1Affine)> = vec![("1".into(), g.to_affine()), ("2".into(), (g + g).to_affine()), ("r-1".into(), (g * (-Fr::one())).to_affine()), ("identity".into(), G1Affine::identity())];
+    // ShaWrite over SHA-256 / Keccak-256 (transcript/sha.rs:129-232), the outer proof's transcript family: common_scalar(5),
+    // common_point(G), two squeezes each — pins Challenge255::new(digest | 32 zero bytes), which lives in halo2_proofs
+    // (the expected values are tests/hash_transcript_ref.py's for the script "CXQQ")
+    let sha_chal = |keccak: bool| -> Vec<String> {
+        use halo2_proofs::transcript::{EncodedChallenge, Transcript};
+        use halo2_snark_aggregator_api::transcript::sha::ShaWrite;
+        if keccak {
+            let mut t = ShaWrite::<_, G1Affine, Challenge255<_>, sha3::Keccak256>::init(vec![]);
+            t.common_scalar(Fr::from(5)).unwrap();
+            t.common_point(g.to_affine()).unwrap();
+            (0..2).map(|_| hex_fe(&t.squeeze_challenge().get_scalar())).collect()
+        } else {
+            let mut t = ShaWrite::<_, G1Affine, Challenge255<_>, sha2::Sha256>::init(vec![]);
+            t.common_scalar(Fr::from(5)).unwrap();
+            t.common_point(g.to_affine()).unwrap();
+            (0..2).map(|_| hex_fe(&t.squeeze_challenge().get_scalar())).collect()
+        }
+    };
     let mut o = String::from("{\n");
+    o += &format!("  \"sha256_transcript_challenges\": {},\n", json_list(&sha_chal(false)));
+    o += &format!("  \"keccak256_transcript_challenges\": {},\n", json_list(&sha_chal(true)));
     o += &format!("  \"poseidon_state_default\": {},\n", json_list(&state0.words().iter().map(hex_fe).collect::<Vec<_>>()));
     o += &format!("  \"poseidon_squeezes\": {},\n", json_list(&outs));
     o += &format!("  \"poseidon_mds_row0\": {},\n", json_list(&mds[0].iter().map(hex_fe).collect::<Vec<_>>()));
