@@ -147,6 +147,10 @@ def load_library():
         "h2agg_allgather_add_points": (i32, [C.POINTER(ctxp), i32, u8p, sz, vp]),
         "h2agg_pairing_check": (i32, [ctxp, u8p, u8p, sz, C.POINTER(i32)]),
         "h2agg_g2_batch_decompress": (i32, [ctxp, u8p, sz, vp]),
+        "h2agg_bases_fft": (i32, [ctxp, u64, C.c_uint, i32, C.POINTER(u64)]),
+        "h2agg_params_setup": (i32, [ctxp, C.c_uint, u8p, C.POINTER(u64), C.POINTER(u64)]),
+        "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
+        "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
         "h2agg_final_pair_check": (i32, [ctxp, u8p, u8p, u8p, u8p, C.POINTER(i32)]),
         "h2agg_msm_configure": (i32, [ctxp, i32, i32, i32]),
@@ -177,6 +181,31 @@ def _need(buf, nbytes: int, what: str):
     """the C side trusts the lengths it is given: a short Python buffer would be read past its end"""
     if buf is None or len(buf) != nbytes:
         raise ValueError("%s must be exactly %d bytes (got %s)" % (what, nbytes, "None" if buf is None else len(buf)))
+
+
+def _check_host(rc: int, what: str):
+    if rc == ERR_BAD_POINT:
+        raise BadPoint(rc, what + ": invalid G2 point")
+    if rc != OK:
+        raise H2AggError(rc, what + (": input integer >= modulus" if rc == ERR_NONCANONICAL else " failed"))
+
+
+def g2_scalar_mul(g2_aff: bytes, s: bytes) -> bytes:
+    """h2agg_g2_scalar_mul: host arithmetic, no context"""
+    _need(g2_aff, 128, "g2_aff")
+    _need(s, 32, "s")
+    out = C.create_string_buffer(128)
+    _check_host(load_library().h2agg_g2_scalar_mul(g2_aff, s, out), "g2_scalar_mul")
+    return out.raw
+
+
+def g2_batch_compress(aff: bytes) -> bytes:
+    """h2agg_g2_batch_compress: host arithmetic, no context"""
+    n = len(aff) // 128
+    _need(aff, 128 * n, "aff")
+    out = C.create_string_buffer(max(64 * n, 1))
+    _check_host(load_library().h2agg_g2_batch_compress(aff, n, out), "g2_batch_compress")
+    return out.raw[:64 * n]
 
 
 class H2Agg:
@@ -413,6 +442,30 @@ class H2Agg:
 
     def bases_free(self, handle: int):
         self._check(self._lib.h2agg_bases_free(self._ctx, handle))
+
+    def bases_fft(self, handle: int, k: int, inverse: bool = False) -> int:
+        """the G1 Fourier transform of the first 2^k points of a resident table, as a new table; inverse=True is halo2's
+        g_to_lagrange (ParamsKZG::downsize): out[i] = (1/n) sum_j w^(-ij) in[j]"""
+        h = C.c_uint64()
+        self._check(self._lib.h2agg_bases_fft(self._ctx, handle, k, int(bool(inverse)), C.byref(h)))
+        return h.value
+
+    def params_setup(self, k: int, s: bytes):
+        """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""
+        _need(s, 32, "s")
+        g, gl = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.h2agg_params_setup(self._ctx, k, s, C.byref(g), C.byref(gl)))
+        return g.value, gl.value
+
+    def g2_scalar_mul(self, g2_aff: bytes, s: bytes) -> bytes:
+        """s * Q for a 128-byte affine G2 point (host arithmetic)"""
+        _need(g2_aff, 128, "g2_aff")
+        _need(s, 32, "s")
+        return g2_scalar_mul(g2_aff, s)
+
+    def g2_batch_compress(self, aff: bytes) -> bytes:
+        """128-byte affine G2 points -> the 64-byte form ParamsKZG::write stores (inverse of g2_batch_decompress)"""
+        return g2_batch_compress(aff)
 
     def g1_msm_preloaded(self, handle: int, scalars: bytes) -> bytes:
         _need(scalars, 32 * (len(scalars) // 32), "scalars")

@@ -29,6 +29,7 @@
 #include "scalar_mul_kernels.hpp"
 #include "lp_kernels.hpp"
 #include "seg_msm_kernels.hpp"
+#include "g1_fft_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -172,6 +173,11 @@ struct h2agg_ctx {
     int dbg_pcie_slices = 0, dbg_pcie_glv = 0, dbg_pcie_chain = 1, dbg_comb_msm = 1, dbg_plan_cache = 1, dbg_small_sort = 1, dbg_eval_split = 1, dbg_pre_big = 0, dbg_lean_acc = 1, dbg_shard_fail = 0, dbg_shard_calls = 0, dbg_phases = 0, dbg_tape_lds = 1, dbg_prewake = 1;
     int dbg_seg_chunk = 0, dbg_seg_c = 0;   // segmented multi_exp: points per set of launches (0 = automatic), window bits (0 = default)
     DevBuf seg_wsum, seg_dev, seg_out;      // segmented multi_exp: window sums, segment offsets, results (csrc/seg_msm.inc)
+    // G1 FFT (csrc/params.inc): ladder records of w_K^t, t < 2^(K-1), per direction (0 forward, 1 inverse) for the largest K asked
+    // for so far (a smaller k reads them with a stride), and of 1 / 2^k for k <= 24
+    DevBuf fft_tw[2], fft_scale;
+    int fft_tw_k[2] = {-1, -1};
+    bool fft_scale_ready = false;
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -1333,7 +1339,7 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->r2d_ticket[0], &c->r2d_ticket[1], &c->r2d_ticket[2], &c->buckets[0], &c->buckets[1], &c->buckets[2], &c->segsum[0], &c->segsum[1], &c->segsum[2],
                       &c->wsum[0], &c->wsum[1], &c->wsum[2], &c->big_list[0], &c->big_list[1], &c->big_keys[0], &c->big_keys[1], &c->big_part[0], &c->big_part[1], &c->fix_list[0], &c->fix_list[1], &c->glv_buf, &c->parts, &c->small, &c->endo_buf, &c->tile_counts, &c->fb_long,
                       &c->sch_regs, &c->sch_in, &c->sch_scalars[0], &c->sch_scalars[1], &c->sch_bases[0], &c->sch_bases[1], &c->sch_endo,
-                      &c->seg_wsum, &c->seg_dev, &c->seg_out};
+                      &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -1677,6 +1683,25 @@ int h2agg_bases_upload(h2agg_ctx* c, const uint8_t* bases, size_t n, uint64_t* h
     return H2AGG_ERR_INVALID;
 }
 
+}  // extern "C"
+namespace {
+// out[i] = k_i * G (Montgomery affine) through the fixed-base comb: d * 2^(8w) * G for every byte position, built once per
+// context (32 x 255 points, 510 KiB).  Queued on the context's stream.
+int comb_generate_launch(h2agg_ctx* c, const uint8_t* d_k, size_t n, uint8_t* out) {
+    if (!c->comb_ready) {
+        TRY(ensure(c, c->comb, (size_t)COMB_WINDOWS * COMB_ROW * 64));
+        hipLaunchKernelGGL(k_comb_table_build, dim3((COMB_WINDOWS * COMB_ROW + SM_GROUPS - 1) / SM_GROUPS), dim3(SM_THREADS), 0,
+                           c->stream, (uint8_t*)c->comb.p, c->d_flags);
+        c->comb_ready = true;
+    }
+    size_t blocks = (n + BLOCK - 1) / BLOCK;
+    if (blocks > 65535 * 16) blocks = 65535 * 16;
+    hipLaunchKernelGGL(k_bases_generate_comb, dim3((unsigned)blocks), dim3(BLOCK), 0, c->stream, d_k, n, (const uint8_t*)c->comb.p,
+                       out, c->d_flags);
+    return H2AGG_OK;
+}
+}  // namespace
+extern "C" {
 int h2agg_bases_generate(h2agg_ctx* c, const void* d_k, size_t n, uint64_t* handle_out) try {
     TRY(bind(c));
     if (!d_k || !handle_out || n == 0) return fail(c, H2AGG_ERR_INVALID, "null buffer or n == 0");
@@ -1686,24 +1711,13 @@ int h2agg_bases_generate(h2agg_ctx* c, const void* d_k, size_t n, uint64_t* hand
     int rc = clear_flags(c);
     if (rc == H2AGG_OK) {
         static const bool ladder = knob("H2AGG_SCALAR_MUL") && !strcmp(knob("H2AGG_SCALAR_MUL"), "ladder");
-        size_t blocks = (n + BLOCK - 1) / BLOCK;
-        if (blocks > 65535 * 16) blocks = 65535 * 16;
         if (ladder) {
+            size_t blocks = (n + BLOCK - 1) / BLOCK;
+            if (blocks > 65535 * 16) blocks = 65535 * 16;
             hipLaunchKernelGGL(k_bases_generate, dim3((unsigned)blocks), dim3(BLOCK), 0, c->stream, (const uint8_t*)d_k, n, t.d,
                                c->d_flags);
         } else {
-            // fixed-base comb: d * 2^(8w) * G for every byte position, built once per context (32 x 255 points, 510 KiB)
-            if (!c->comb_ready) {
-                rc = ensure(c, c->comb, (size_t)COMB_WINDOWS * COMB_ROW * 64);
-                if (rc == H2AGG_OK) {
-                    hipLaunchKernelGGL(k_comb_table_build, dim3((COMB_WINDOWS * COMB_ROW + SM_GROUPS - 1) / SM_GROUPS),
-                                       dim3(SM_THREADS), 0, c->stream, (uint8_t*)c->comb.p, c->d_flags);
-                    c->comb_ready = true;
-                }
-            }
-            if (rc == H2AGG_OK)
-                hipLaunchKernelGGL(k_bases_generate_comb, dim3((unsigned)blocks), dim3(BLOCK), 0, c->stream, (const uint8_t*)d_k, n,
-                                   (const uint8_t*)c->comb.p, t.d, c->d_flags);
+            rc = comb_generate_launch(c, (const uint8_t*)d_k, n, t.d);
         }
         if (rc == H2AGG_OK) rc = finish(c);
     }
@@ -2527,3 +2541,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "seg_msm.inc"
 #include "comm.inc"
 #include "verifier.inc"
+#include "params.inc"

@@ -166,6 +166,52 @@ def upload_g_lagrange(eng, params: KzgParams, precompute: bool = True) -> int:
     return h
 
 
+# halo2curves' G2::generator() (EIP-197's P2): x.c0, x.c1, y.c0, y.c1
+_G2_GENERATOR = (10857046999023057135944570762232829481370756359578518086990519993285655852781,
+                 11559732032986387107991004021392285783925812861821192530917403151452391805634,
+                 8495653923123431417604973247489272438418190587263600148770280649306958101930,
+                 4082367875863433681332203403145435568316851327593401208105741076214120093531)
+
+
+def _table_compressed(eng, handle: int, n: int) -> bytes:
+    """a resident table as ParamsKZG::write stores it: n compressed G1 points (compressed on the device)"""
+    return eng.g1_batch_compress(eng.bases_download(handle, 0, n))
+
+
+def setup_params(eng, k: int, s: bytes) -> KzgParams:
+    """ParamsKZG::setup with the trapdoor `s` (32-byte LE canonical scalar; halo2_proofs draws it from an rng, unsafe_setup
+    from a fixed seed — recalled from upstream): what verify_circuit.rs:701-731 `get_params_cached` makes on the CPU when the
+    params file is missing.  Both tables are built on the device (h2agg_params_setup); g2 is the generator, s_g2 = s * g2."""
+    g2 = b"".join(v.to_bytes(32, "little") for v in _G2_GENERATOR)
+    hg, hl = eng.params_setup(k, s)
+    try:
+        g, gl = _table_compressed(eng, hg, 1 << k), _table_compressed(eng, hl, 1 << k)
+    finally:
+        eng.bases_free(hg)
+        eng.bases_free(hl)
+    return KzgParams(k, g, gl, eng.g2_batch_compress(g2), eng.g2_batch_compress(eng.g2_scalar_mul(g2, s)))
+
+
+def downsize_params(eng, params: KzgParams, k: int) -> KzgParams:
+    """ParamsKZG::downsize (recalled from upstream): the parameters of a smaller circuit from one ceremony file, without the
+    trapdoor.  g keeps its first 2^k points; g_lagrange = g_to_lagrange(g[:2^k]) is the inverse G1 Fourier transform on the
+    device (h2agg_bases_fft); g2 and s_g2 are unchanged."""
+    if k > params.k:
+        raise ValueError("downsize: k = %d is larger than the parameters' k = %d" % (k, params.k))
+    n = 1 << k
+    g = params.g[:32 * n]
+    hg = eng.bases_upload(eng.g1_batch_decompress(g))
+    try:
+        hl = eng.bases_fft(hg, k, inverse=True)
+        try:
+            gl = _table_compressed(eng, hl, n)
+        finally:
+            eng.bases_free(hl)
+    finally:
+        eng.bases_free(hg)
+    return KzgParams(k, g, gl, params.g2, params.s_g2)
+
+
 def pairing_g2(eng, params: KzgParams):
     """(s_g2, g2) in the 128-byte affine form of h2agg_final_pair_check / h2agg_verify_aggregation"""
     both = eng.g2_batch_decompress(params.s_g2 + params.g2)

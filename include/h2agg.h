@@ -509,6 +509,36 @@ int h2agg_pairing_product(h2agg_ctx* ctx, const uint8_t* g1_aff, const uint8_t* 
 int h2agg_final_pair_check(h2agg_ctx* ctx, const uint8_t left_aff[64], const uint8_t right_aff[64],
                            const uint8_t s_g2[128], const uint8_t g2[128], int* ok);
 
+/* ---- KZG parameters (what the reference's workflow does before verify_run: ParamsKZG::setup / downsize) ----------
+ * halo2_proofs is an unvendored git dependency of the reference: the functions named below are recalled from upstream
+ * (DESIGN.md section 2); what the entry points compute is the definition written next to each.
+ *
+ * h2agg_bases_fft — stands for: g_to_lagrange / ParamsKZG::downsize (inverse != 0) and the G1 best_fft it runs (inverse == 0).
+ *   out[i] = sum_j w^(i*j) * in[j]                 (inverse == 0)
+ *   out[i] = (1/n) * sum_j w^(-i*j) * in[j]        (inverse != 0; this is g_to_lagrange)
+ *   n = 2^k, w = FR_ROOT_OF_UNITY^(2^(28-k)) (EvaluationDomain::get_omega).
+ *   Reads the FIRST 2^k points of the table (a longer table is "downsized"); the table is not modified.  The result is a new
+ *   resident base table of 2^k canonical affine points (identity = (0,0)), like any other: h2agg_bases_download / _free /
+ *   _precompute, the MSM entry points and h2agg_instance_commitment accept it.
+ *   k > 24, or 2^k longer than the input table: H2AGG_ERR_INVALID.  Out of memory: H2AGG_ERR_NOMEM, nothing is registered. */
+int h2agg_bases_fft(h2agg_ctx* ctx, uint64_t in_handle, unsigned k, int inverse, uint64_t* out_handle);
+
+/* stands for: ParamsKZG::setup with the trapdoor given by the caller (unsafe_setup / setup(k, rng) draw it themselves):
+ *   g[i] = s^i * G,   g_lagrange[i] = L_i(s) * G with L_i(s) = w^i * (s^n - 1) / (n * (s - w^i)),   i < n = 2^k.
+ * Either handle pointer may be NULL (that table is not built).  s: 32-byte little-endian, canonical (>= r:
+ * H2AGG_ERR_NONCANONICAL).  k > 24: H2AGG_ERR_INVALID.
+ * Two deviations from halo2_proofs, both H2AGG_ERR_INVALID here: s^n == 1 (there `(s - w^i).invert().unwrap()` panics), and
+ * s == 0 (there every g[i] with i > 0 is the identity and the parameters are useless). */
+int h2agg_params_setup(h2agg_ctx* ctx, unsigned k, const uint8_t s[32], uint64_t* g_handle_out, uint64_t* g_lagrange_handle_out);
+
+/* Host-only, no context (like h2agg_hash_digest_host): what a params file needs beside the G1 tables.
+ * h2agg_g2_scalar_mul — stands for: `s_g2 = g2 * s` of ParamsKZG::setup.  128-byte affine in and out (the form of
+ *   h2agg_final_pair_check); the point must be canonical, on the twist and in the order-r subgroup, s canonical.
+ * h2agg_g2_batch_compress — stands for: G2Affine::to_bytes as ParamsKZG::write uses it; the inverse of
+ *   h2agg_g2_batch_decompress (128-byte affine -> 64 bytes: x.c0 || x.c1, bit 7 of byte 63 = parity of y.c0, identity = zeros). */
+int h2agg_g2_scalar_mul(const uint8_t g2_aff[128], const uint8_t s[32], uint8_t out_aff[128]);
+int h2agg_g2_batch_compress(const uint8_t* aff, size_t n, uint8_t* out);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
