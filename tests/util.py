@@ -30,3 +30,19 @@ def to_jac_bytes(aff_bytes, zs):
 def norm(eng_or_none, jac):
     """normalise Jacobian bytes with the ORACLE (checker-side normalisation)"""
     return cref.g1_batch_to_affine(jac, len(jac) // 96)
+
+
+def bases_from_coefficients(gs):
+    """affine bytes of g_i * G for integer coefficients g_i (0 mod r: the identity, 64 zero bytes), each distinct value
+    multiplied once by the C oracle: dependent bases (small multiples of one point) cost a handful of scalar multiplications"""
+    distinct = sorted({g % O.R for g in gs} - {0})
+    pts = points_from_scalars(distinct)
+    table = {g: pts[64 * i:64 * i + 64] for i, g in enumerate(distinct)}
+    table[0] = bytes(64)
+    return b"".join(table[g % O.R] for g in gs)
+
+
+def msm_want(gs, ss):
+    """canonical affine bytes of sum_i s_i * (g_i * G) = ((sum_i g_i s_i) mod r) * G: Python integers and one scalar
+    multiplication by the oracle"""
+    return O.aff_to_bytes(O.scalar_mul(sum(g * s for g, s in zip(gs, ss)) % O.R, O.G1))
