@@ -19,6 +19,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "h2agg.h")
 
 OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, ERR_BAD_POINT, ERR_PEER = range(9)
 OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
+FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
+FR_FFT_MAX_K = 24
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
@@ -149,6 +151,8 @@ def load_library():
         "h2agg_g2_batch_decompress": (i32, [ctxp, u8p, sz, vp]),
         "h2agg_bases_fft": (i32, [ctxp, u64, C.c_uint, i32, C.POINTER(u64)]),
         "h2agg_params_setup": (i32, [ctxp, C.c_uint, u8p, C.POINTER(u64), C.POINTER(u64)]),
+        "h2agg_fr_fft": (i32, [ctxp, vp, C.c_uint, i32, u8p, vp]),
+        "h2agg_fr_fft_device": (i32, [ctxp, vp, C.c_uint, i32, u8p, vp]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -449,6 +453,29 @@ class H2Agg:
         h = C.c_uint64()
         self._check(self._lib.h2agg_bases_fft(self._ctx, handle, k, int(bool(inverse)), C.byref(h)))
         return h.value
+
+    def fr_fft(self, data, k: int, inverse: bool = False, shift: Optional[bytes] = None) -> bytes:
+        """the Fourier transform over Fr of 2^k canonical 32-byte elements (h2agg_fr_fft): best_fft, or with inverse=True the
+        inverse transform with its 1/n; shift=s transforms s^j * in[j] (forward) / multiplies out[j] by s^-j (inverse).  A
+        bytearray is transformed in place and returned; bytes give a new bytes object."""
+        if 0 <= k <= FR_FFT_MAX_K:   # (a larger k is refused by the library before it touches a buffer)
+            _need(data, 32 << k, "data")
+        if shift is not None:
+            _need(shift, 32, "shift")
+        if isinstance(data, bytearray):
+            buf = (C.c_char * len(data)).from_buffer(data)
+            self._check(self._lib.h2agg_fr_fft(self._ctx, C.addressof(buf), k, int(bool(inverse)), shift, C.addressof(buf)))
+            return data
+        out = C.create_string_buffer(len(data))
+        self._check(self._lib.h2agg_fr_fft(self._ctx, C.cast(C.c_char_p(bytes(data)), C.c_void_p), k, int(bool(inverse)), shift, out))
+        return out.raw
+
+    def fr_fft_device(self, d_in_ptr: int, k: int, inverse: bool, shift: Optional[bytes], d_out_ptr: int):
+        """h2agg_fr_fft_device: 2^k elements in device memory, queued on the context's stream (no synchronisation);
+        d_out_ptr == d_in_ptr is allowed"""
+        if shift is not None:
+            _need(shift, 32, "shift")
+        self._check(self._lib.h2agg_fr_fft_device(self._ctx, d_in_ptr, k, int(bool(inverse)), shift, d_out_ptr))
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

@@ -1,0 +1,159 @@
+// Fourier transform over Fr, host side (included into h2agg.hip: shares the context internals; kernels and the pass plan in
+// fr_fft_kernels.hpp): h2agg_fr_fft, h2agg_fr_fft_device.  They stand for halo2_proofs' best_fft and
+// EvaluationDomain::{lagrange_to_coeff, coeff_to_lagrange, coeff_to_extended, extended_to_coeff} — an unvendored git
+// dependency of the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.
+
+namespace {
+
+// the value 2^261 (the device's Montgomery radix) as a host field element: x * fr_radix() is what the device holds for x
+const ph::HFr& fr_radix() {
+    static const ph::HFr r = [] {
+        ph::HFr x = ph::one();
+        for (int i = 0; i < 29 * NL; ++i) x = ph::add(x, x);
+        return x;
+    }();
+    return r;
+}
+
+void hfr_words(const ph::HFr& a, uint32_t out[8]) {
+    uint8_t b[32];
+    hfr_bytes(a, b);
+    memcpy(out, b, 32);
+}
+
+// d_out[i] = (base^i in the device's Montgomery form), i < n <= 2^12; queued on the context's stream, constants by value
+void fr_powers_launch(h2agg_ctx* c, ph::HFr base, uint32_t n, uint8_t* d_out) {
+    FrPowersArgs args;
+    for (int j = 0; j < FRW_TABLE; ++j) {
+        hfr_words(base, args.pw[j]);
+        base = ph::mul(base, base);
+    }
+    hfr_words(fr_radix(), args.a);
+    const uint32_t threads = (n + FRP_CHUNK - 1) / FRP_CHUNK;
+    hipLaunchKernelGGL(k_fr_powers, dim3((threads + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, args, n, d_out);
+}
+
+// the two-level table of base^e, e < 2^bits: lo[i] = base^i, i < 2^T, then hi[i] = base^(i * 2^T), i < 2^(bits - T), T = ceil(bits / 2)
+unsigned fr_table_split(unsigned bits) { return (bits + 1) / 2; }
+size_t fr_table_bytes(unsigned bits) { return 32 * (((size_t)1 << fr_table_split(bits)) + ((size_t)1 << (bits - fr_table_split(bits)))); }
+void fr_table_launch(h2agg_ctx* c, const ph::HFr& base, unsigned bits, uint8_t* d_tab) {
+    const unsigned T = fr_table_split(bits);
+    fr_powers_launch(c, base, 1u << T, d_tab);
+    ph::HFr hb = base;
+    for (unsigned i = 0; i < T; ++i) hb = ph::mul(hb, hb);
+    fr_powers_launch(c, hb, 1u << (bits - T), d_tab + ((size_t)32 << T));
+}
+
+// twiddle tables of w_K (inverse: w_K^-1) for the largest K asked for so far, resident in the context
+int fr_fft_ensure_twiddles(h2agg_ctx* c, unsigned k, int inv) {
+    if (c->frfft_tw_k[inv] >= (int)k) return H2AGG_OK;
+    c->frfft_tw_k[inv] = -1;
+    TRY(ensure(c, c->frfft_tw[inv], fr_table_bytes(k)));   // (a replaced buffer: ensure() drains the device first)
+    const ph::HFr w = fft_omega(k);
+    fr_table_launch(c, inv ? ph::inv(w) : w, k, (uint8_t*)c->frfft_tw[inv].p);
+    c->frfft_tw_k[inv] = (int)k;
+    return H2AGG_OK;
+}
+
+// Queues the transform of d_in into d_out on the context's stream (no synchronisation unless a workspace has to grow).
+// shift: null, or the checked non-zero shift.
+int fr_fft_queue(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, const ph::HFr* shift, uint8_t* d_out) {
+    const unsigned L = c->dbg_fr_fft_local ? (unsigned)c->dbg_fr_fft_local : FR_FFT_LOCAL;
+    const unsigned P = k ? (k + L - 1) / L : 1;
+    if (P > 1) TRY(ensure(c, c->frfft_work, (size_t)32 << k));
+    if (k) TRY(fr_fft_ensure_twiddles(c, k, inv));
+    if (shift) {
+        TRY(ensure(c, c->frfft_shift, fr_table_bytes(k)));
+        fr_table_launch(c, inv ? ph::inv(*shift) : *shift, k, (uint8_t*)c->frfft_shift.p);
+    }
+    FrFftPass p = {};
+    const unsigned K = k ? (unsigned)c->frfft_tw_k[inv] : 0;
+    p.tw_T = fr_table_split(K);
+    p.tw_lo = (const uint8_t*)c->frfft_tw[inv].p;
+    p.tw_hi = p.tw_lo + ((size_t)32 << p.tw_T);
+    p.tw_up = K - k;
+    if (shift) {
+        p.sh_T = fr_table_split(k);
+        p.sh_lo = (const uint8_t*)c->frfft_shift.p;
+        p.sh_hi = p.sh_lo + ((size_t)32 << p.sh_T);
+    }
+    p.flags = c->d_flags;
+    p.k = k;
+    p.local = L;
+    p.digits = P - 1;
+    {   // x -> x R [/ n]: the first pass multiplies by R^2 [/ n]
+        ph::HFr cv = ph::mul(fr_radix(), fr_radix());
+        if (inv) cv = ph::mul(cv, ph::inv(hfr_u64((uint64_t)1 << k)));
+        uint32_t w[8];
+        hfr_words(cv, w);
+        for (int i = 0; i < NL; ++i) {
+            const int bit = 29 * i;
+            uint64_t v = w[bit / 32];
+            if (bit / 32 + 1 < 8) v |= (uint64_t)w[bit / 32 + 1] << 32;
+            p.cvt[i] = (uint32_t)(v >> (bit % 32)) & ((1u << 29) - 1u);
+        }
+    }
+    for (unsigned q = 0; q < P; ++q) {
+        p.first = q == 0;
+        p.last = q + 1 == P;
+        p.width = p.last ? k - (P - 1) * L : L;
+        p.hb = q * L;
+        p.lb = k - p.hb - p.width;
+        p.src = p.first ? d_in : (const uint8_t*)c->frfft_work.p;
+        p.dst = p.last ? d_out : (uint8_t*)c->frfft_work.p;
+        p.sh_first = shift && !inv && p.first;
+        p.sh_last = shift && inv && p.last;
+        const size_t tiles = (size_t)1 << (k - p.width), per = FR_FFT_TILE >> p.width;
+        hipLaunchKernelGGL(k_fr_fft_pass, dim3((unsigned)((tiles + per - 1) / per)), dim3(FR_FFT_THREADS), 0, c->stream, p);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return H2AGG_OK;
+}
+
+// k, shift -> refusals; *has: a shift other than null
+int fr_fft_check(h2agg_ctx* c, unsigned k, const uint8_t* shift, ph::HFr* s) {
+    if (k > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "k must be <= 24");
+    if (!shift) return H2AGG_OK;
+    if (!fr_bytes_canonical(shift)) return fail(c, H2AGG_ERR_NONCANONICAL, "input integer >= modulus");
+    uint64_t sw[4];
+    memcpy(sw, shift, 32);
+    *s = ph::from_words(sw);
+    if (ph::is_zero(*s)) return fail(c, H2AGG_ERR_INVALID, "fr_fft: shift == 0 (the inverse transform divides by shift^j)");
+    return H2AGG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int h2agg_fr_fft_device(h2agg_ctx* c, const void* d_in, unsigned k, int inverse, const uint8_t shift[32], void* d_out) try {
+    TRY(bind(c));
+    if (!d_in || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
+    ph::HFr s;
+    TRY(fr_fft_check(c, k, shift, &s));
+    return fr_fft_queue(c, (const uint8_t*)d_in, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)d_out);
+} catch (const std::bad_alloc&) {
+    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
+} catch (...) {
+    return H2AGG_ERR_INVALID;
+}
+
+int h2agg_fr_fft(h2agg_ctx* c, const uint8_t* in, unsigned k, int inverse, const uint8_t shift[32], uint8_t* out) try {
+    TRY(bind(c));
+    if (!in || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
+    ph::HFr s;
+    TRY(fr_fft_check(c, k, shift, &s));
+    const size_t bytes = (size_t)32 << k;
+    TRY(ensure(c, c->in_a, bytes));
+    HIP_TRY(c, hipMemcpyAsync(c->in_a.p, in, bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(clear_flags(c));
+    TRY(fr_fft_queue(c, (const uint8_t*)c->in_a.p, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)c->in_a.p));
+    HIP_TRY(c, hipMemcpyAsync(out, c->in_a.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+} catch (const std::bad_alloc&) {
+    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
+} catch (...) {
+    return H2AGG_ERR_INVALID;
+}
+
+}  // extern "C"

@@ -30,6 +30,7 @@
 #include "lp_kernels.hpp"
 #include "seg_msm_kernels.hpp"
 #include "g1_fft_kernels.hpp"
+#include "fr_fft_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -178,6 +179,11 @@ struct h2agg_ctx {
     DevBuf fft_tw[2], fft_scale;
     int fft_tw_k[2] = {-1, -1};
     bool fft_scale_ready = false;
+    // Fr FFT (csrc/fr_fft.inc): the two-level twiddle tables of w_K per direction for the largest K asked for so far, the
+    // shift table of the last shifted call, the work array of a multi-pass transform
+    DevBuf frfft_tw[2], frfft_shift, frfft_work;
+    int frfft_tw_k[2] = {-1, -1};
+    int dbg_fr_fft_local = 0;   // debug key fr_fft_local: radix-2 stages fused per pass (0 = FR_FFT_LOCAL)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -1339,7 +1345,8 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->r2d_ticket[0], &c->r2d_ticket[1], &c->r2d_ticket[2], &c->buckets[0], &c->buckets[1], &c->buckets[2], &c->segsum[0], &c->segsum[1], &c->segsum[2],
                       &c->wsum[0], &c->wsum[1], &c->wsum[2], &c->big_list[0], &c->big_list[1], &c->big_keys[0], &c->big_keys[1], &c->big_part[0], &c->big_part[1], &c->fix_list[0], &c->fix_list[1], &c->glv_buf, &c->parts, &c->small, &c->endo_buf, &c->tile_counts, &c->fb_long,
                       &c->sch_regs, &c->sch_in, &c->sch_scalars[0], &c->sch_scalars[1], &c->sch_bases[0], &c->sch_bases[1], &c->sch_endo,
-                      &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale};
+                      &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale,
+                      &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -2330,6 +2337,10 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         if (value != 0 && (value < 4 || value > 8)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: seg_c must be 0 or 4 .. 8");
         c->dbg_seg_c = value;
     }
+    else if (k == "fr_fft_local") {                          // Fr FFT: radix-2 stages fused per pass, 1 .. 11 (0 = the default, 10)
+        if (value < 0 || value > (int)FR_FFT_TILE_LOG) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_fft_local must be 0 or 1 .. 11");
+        c->dbg_fr_fft_local = value;
+    }
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
     return H2AGG_OK;
@@ -2542,3 +2553,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "comm.inc"
 #include "verifier.inc"
 #include "params.inc"
+#include "fr_fft.inc"

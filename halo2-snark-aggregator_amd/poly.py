@@ -1,0 +1,58 @@
+"""EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), and the two ways to commit to a polynomial.
+
+halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
+(poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
+polynomials are 2^k canonical 32-byte little-endian Fr elements, coefficients low degree first, evaluations in the natural
+order of the domain {w^i}.  The transform runs on the device; nothing here computes in Python but the padding."""
+from __future__ import annotations
+
+from .wire import R_MOD
+
+# The cube root of unity halo2curves calls bn256::Fr::ZETA is the eigenvalue lambda of the GLV endomorphism
+# (phi(P) = lambda * P, csrc/sort_kernels.hpp): no second literal, it comes from the reduced lattice basis the MSM's scalar
+# decomposition already uses (GlvConst::A1, GlvConst::B1N: a1 + b1 * lambda = 0 mod r, b1 = -B1N).
+_GLV_A1 = 0x6f4d8248eeb859fc8211bbeb7d4f1128
+_GLV_B1N = 0x89d3256894d213e3
+ZETA_INT = _GLV_A1 * pow(_GLV_B1N, R_MOD - 2, R_MOD) % R_MOD
+assert pow(ZETA_INT, 3, R_MOD) == 1 and ZETA_INT != 1
+ZETA = ZETA_INT.to_bytes(32, "little")
+
+
+def _poly(data, k: int, what: str):
+    if data is None or len(data) != 32 << k:
+        raise ValueError("%s must be 2^%d elements of 32 bytes (got %s bytes)" % (what, k, "no" if data is None else len(data)))
+    return data
+
+
+def lagrange_to_coeff(eng, evals: bytes, k: int) -> bytes:
+    """evaluations over {w^i} -> coefficients (the inverse transform, with its 1/n)"""
+    return eng.fr_fft(_poly(evals, k, "evals"), k, inverse=True)
+
+
+def coeff_to_lagrange(eng, coeffs: bytes, k: int) -> bytes:
+    """coefficients -> evaluations over {w^i} (best_fft)"""
+    return eng.fr_fft(_poly(coeffs, k, "coeffs"), k)
+
+
+def coeff_to_extended(eng, coeffs: bytes, k: int, extended_k: int, shift: bytes = ZETA) -> bytes:
+    """2^k coefficients -> evaluations over the coset {shift * w_ext^i} of the 2^extended_k domain: zero-padded, then a shifted
+    forward transform (halo2 multiplies coefficient j by zeta^(j mod 3) = zeta^j first)"""
+    if extended_k < k:
+        raise ValueError("extended_k must be >= k")
+    return eng.fr_fft(bytes(_poly(coeffs, k, "coeffs")) + bytes((32 << extended_k) - (32 << k)), extended_k, shift=shift)
+
+
+def extended_to_coeff(eng, evals: bytes, extended_k: int, shift: bytes = ZETA) -> bytes:
+    """evaluations over the coset {shift * w_ext^i} -> all 2^extended_k coefficients (the caller truncates to its degree)"""
+    return eng.fr_fft(_poly(evals, extended_k, "evals"), extended_k, inverse=True, shift=shift)
+
+
+def commit_coeff(eng, g_handle: int, coeffs: bytes) -> bytes:
+    """sum_j coeffs[j] * g[j] against the monomial table (ParamsKZG.g), as a 96-byte Jacobian point"""
+    return eng.g1_msm_preloaded(g_handle, coeffs)
+
+
+def commit_lagrange(eng, gl_handle: int, evals: bytes) -> bytes:
+    """sum_i evals[i] * g_lagrange[i] against the Lagrange table (ParamsKZG.g_lagrange): the same point as commit_coeff of
+    lagrange_to_coeff(evals)"""
+    return eng.g1_msm_preloaded(gl_handle, evals)

@@ -28,6 +28,7 @@ extern "C" {
     pub fn h2agg_g1_batch_scalar_mul(ctx: *mut h2agg_ctx, bases_aff: *const u8, scalars: *const u8, n: usize, out_jac: *mut u8) -> c_int;
     pub fn h2agg_host_alloc(ctx: *mut h2agg_ctx, bytes: usize, out: *mut *mut u8) -> c_int;
     pub fn h2agg_host_free(ctx: *mut h2agg_ctx, p: *mut u8) -> c_int;
+    pub fn h2agg_fr_fft(ctx: *mut h2agg_ctx, input: *const u8, k: std::os::raw::c_uint, inverse: c_int, shift: *const u8, out: *mut u8) -> c_int;
 }
 
 /// One context per thread (the chips are used single-threaded, verify_circuit.rs:114-201; the SDK's rayon workers each get
@@ -156,6 +157,46 @@ pub fn multi_exp<C: CurveAffine>(points: &[C::CurveExt], scalars: &[C::ScalarExt
         marshal_range::<C>(points, scalars, 0, n, SendPtr(g.points), SendPtr(g.scalars));
         run_msm::<C>(g, n)
     })
+}
+
+/// halo2_proofs' `best_fft(a, omega, log_n)` over the scalar field (arithmetic.rs; an unvendored git dependency of the
+/// reference, recalled: DESIGN.md section 2) through h2agg_fr_fft: a[i] <- sum_j a[j] * omega^(i*j), natural order, in place.
+/// UNCOMPILED like the rest of this file.  The library derives the root from `log_n` (ROOT_OF_UNITY^(2^(S - log_n)), what
+/// EvaluationDomain::get_omega returns) or its inverse, so `omega` is only checked: halo2 calls best_fft with the domain's
+/// omega (coeff_to_lagrange, coeff_to_extended) or with omega_inv (ifft, which then multiplies by 1/n itself — the library's
+/// inverse direction includes that factor, so it is taken out again here to keep best_fft's contract).  Any other root panics.
+pub fn best_fft<F: FieldExt>(a: &mut [F], omega: F, log_n: u32) {
+    assert_eq!(a.len(), 1usize << log_n, "best_fft: a.len() != 2^log_n");
+    assert!(log_n <= 24, "best_fft through h2agg_fr_fft: log_n <= 24 (include/h2agg.h)");
+    let mut root = F::root_of_unity();
+    for _ in log_n..F::S {
+        root = root.square();
+    }
+    let inverse = if omega == root {
+        false
+    } else if omega * root == F::one() {
+        true
+    } else {
+        panic!("best_fft: omega is not the 2^log_n domain's root of unity or its inverse");
+    };
+    let mut buf = Vec::with_capacity(32 * a.len());
+    for x in a.iter() {
+        put_fe(&mut buf, x);
+    }
+    with_gpu(|g| {
+        let rc = unsafe { h2agg_fr_fft(g.ctx, buf.as_ptr(), log_n, inverse as c_int, std::ptr::null(), buf.as_mut_ptr()) };
+        if rc != 0 {
+            let msg = unsafe { std::ffi::CStr::from_ptr(h2agg_last_error(g.ctx)) };
+            panic!("h2agg_fr_fft failed ({}): {:?}", rc, msg);
+        }
+    });
+    let n = F::from(a.len() as u64);
+    for (x, b) in a.iter_mut().zip(buf.chunks_exact(32)) {
+        *x = fe_from(b);
+        if inverse {
+            *x *= n; // best_fft itself does not scale
+        }
+    }
 }
 
 /// `multi_exp` plus the reference's observable side effect: `ctx.point_list = points.map(|x| format!("{:?}", x))`

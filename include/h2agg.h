@@ -539,6 +539,31 @@ int h2agg_params_setup(h2agg_ctx* ctx, unsigned k, const uint8_t s[32], uint64_t
 int h2agg_g2_scalar_mul(const uint8_t g2_aff[128], const uint8_t s[32], uint8_t out_aff[128]);
 int h2agg_g2_batch_compress(const uint8_t* aff, size_t n, uint8_t* out);
 
+/* ---- Fourier transform over Fr (the other primitive of halo2_proofs' create_proof beside best_multiexp) -------------
+ * h2agg_fr_fft — stands for: best_fft and EvaluationDomain::{lagrange_to_coeff, coeff_to_lagrange, coeff_to_extended,
+ * extended_to_coeff}.  halo2_proofs is an unvendored git dependency of the reference: these are recalled from upstream, not
+ * pinned; what the entry points compute is this definition.  n = 2^k, w = FR_ROOT_OF_UNITY^(2^(28-k))
+ * (the w of h2agg_bases_fft), natural order in and out:
+ *   out[i] = sum_j (shift^j * in[j]) * w^(i*j)                  (inverse == 0)
+ *   out[j] = shift^(-j) * (1/n) * sum_i in[i] * w^(-i*j)        (inverse != 0)
+ * shift == NULL means 1: the plain best_fft / ifft.  shift = ZETA (the cube root of unity that is also the GLV eigenvalue)
+ * gives coeff_to_extended / extended_to_coeff on input already padded to the extended size; any non-zero canonical shift is
+ * accepted, and the inverse with a shift undoes the forward transform with the same shift exactly.
+ * Elements are 32-byte canonical little-endian.  k == 0 copies the element (shift^0 = 1).
+ * k > 24: H2AGG_ERR_INVALID (larger domains are out of scope: the passes index with 32 bits and the work array is one
+ * allocation).  shift >= r: H2AGG_ERR_NONCANONICAL.  shift == 0: H2AGG_ERR_INVALID.  Out of memory: H2AGG_ERR_NOMEM.  The
+ * context stays usable after any of them.
+ * h2agg_fr_fft: host buffers, pageable or from h2agg_host_alloc; out == in is allowed; synchronous.  An element >= r:
+ *   H2AGG_ERR_NONCANONICAL from the call; `out` is then unspecified.
+ * h2agg_fr_fft_device: 2^k elements in DEVICE memory in and out, d_out == d_in allowed (otherwise the two must not overlap);
+ *   queued on the context's stream, no synchronisation (a workspace that has to grow for a larger k than any before drains
+ *   the device first).  The buffer rules of h2agg_set_stream / h2agg_g1_msm_device_async hold: d_in complete on that stream
+ *   before the call, neither buffer touched until the stream has passed the transform.  An element >= r raises the
+ *   context's device status: H2AGG_ERR_NONCANONICAL at h2agg_synchronize or at the next synchronous entry point, once; d_out
+ *   is then unspecified. */
+int h2agg_fr_fft(h2agg_ctx* ctx, const uint8_t* in, unsigned k, int inverse, const uint8_t shift[32], uint8_t* out);
+int h2agg_fr_fft_device(h2agg_ctx* ctx, const void* d_in, unsigned k, int inverse, const uint8_t shift[32], void* d_out);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
@@ -599,6 +624,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         for the pairing's second Miller loop, and waits only for the element streams in front of the sponges
  *                         (default 1; 0: the three latency measures of round 6 off, for an A/B)
  *       "phases" 0|1      keep every aggregation call's wall-clock split for h2agg_last_phases
+ *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
+ *                         1024 elements then run the multi-pass paths
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
  *       "seg_chunk" n     h2agg_g1_msm_segmented / h2agg_verify_proofs: at most n points per set of launches of the segmented
  *                         multi_exp (0 = automatic, 16384); a segment longer than that is an ordinary multi_exp of its own
