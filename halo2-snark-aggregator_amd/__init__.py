@@ -21,6 +21,7 @@ OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, 
 OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
 FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
 FR_FFT_MAX_K = 24
+FR_POLY_CHUNK = 11   # log2 of the coefficients per workgroup of the KZG opening kernels by default (csrc/poly_kernels.hpp)
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
@@ -153,6 +154,14 @@ def load_library():
         "h2agg_params_setup": (i32, [ctxp, C.c_uint, u8p, C.POINTER(u64), C.POINTER(u64)]),
         "h2agg_fr_fft": (i32, [ctxp, vp, C.c_uint, i32, u8p, vp]),
         "h2agg_fr_fft_device": (i32, [ctxp, vp, C.c_uint, i32, u8p, vp]),
+        "h2agg_fr_poly_eval": (i32, [ctxp, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, vp]),
+        "h2agg_fr_poly_eval_device": (i32, [ctxp, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, vp]),
+        "h2agg_fr_poly_divide": (i32, [ctxp, vp, C.c_uint, u8p, vp, vp]),
+        "h2agg_fr_poly_divide_device": (i32, [ctxp, vp, C.c_uint, u8p, vp, vp]),
+        "h2agg_kzg_multiopen": (i32, [ctxp, u64, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, vp,
+                                      C.POINTER(C.c_uint32), C.POINTER(sz)]),
+        "h2agg_kzg_multiopen_device": (i32, [ctxp, u64, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, vp,
+                                             C.POINTER(C.c_uint32), C.POINTER(sz)]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -477,6 +486,79 @@ class H2Agg:
             _need(shift, 32, "shift")
         self._check(self._lib.h2agg_fr_fft_device(self._ctx, d_in_ptr, k, int(bool(inverse)), shift, d_out_ptr))
 
+    # ------------------------------------------------------------------ KZG openings
+    @staticmethod
+    def _queries(queries, points: bytes):
+        """[(poly, point), ...] -> the uint32 pairs of the C ABI; points: npoints x 32 bytes"""
+        _need(points, 32 * (len(points) // 32), "points")
+        flat = [int(x) for q in queries for x in q]
+        if len(flat) != 2 * len(queries) or any(x < 0 or x >= 1 << 32 for x in flat):
+            raise ValueError("queries must be (polynomial index, point index) pairs of 32-bit values")
+        return (C.c_uint32 * max(len(flat), 1))(*flat), len(queries), len(points) // 32
+
+    def _slab(self, polys, k: int):
+        if not 0 <= k <= FR_FFT_MAX_K:   # (refused by the library before it touches a buffer)
+            return 1
+        _need(polys, (32 << k) * (len(polys) // (32 << k)), "polys")
+        return len(polys) // (32 << k)
+
+    def fr_poly_eval(self, polys: bytes, k: int, queries, points: bytes) -> bytes:
+        """h2agg_fr_poly_eval: polys = a slab [npoly][2^k] of canonical coefficients, queries = [(poly, point), ...] into it
+        and into points (npoints x 32 bytes) -> the nq values, 32 bytes each, in query order"""
+        npoly = self._slab(polys, k)
+        qs, nq, npoints = self._queries(queries, points)
+        out = C.create_string_buffer(max(32 * nq, 1))
+        self._check(self._lib.h2agg_fr_poly_eval(self._ctx, C.cast(C.c_char_p(bytes(polys)), C.c_void_p), npoly, k, qs, nq,
+                                                 points, npoints, out))
+        return out.raw[:32 * nq]
+
+    def fr_poly_eval_device(self, d_polys_ptr: int, npoly: int, k: int, queries, points: bytes) -> bytes:
+        """h2agg_fr_poly_eval_device: as fr_poly_eval over a slab already in device memory; synchronous"""
+        qs, nq, npoints = self._queries(queries, points)
+        out = C.create_string_buffer(max(32 * nq, 1))
+        self._check(self._lib.h2agg_fr_poly_eval_device(self._ctx, d_polys_ptr, npoly, k, qs, nq, points, npoints, out))
+        return out.raw[:32 * nq]
+
+    def fr_poly_divide(self, coeffs, k: int, z: bytes):
+        """h2agg_fr_poly_divide: 2^k coefficients -> (the 2^k coefficients of the quotient by (X - z), zero on top; a(z)).
+        A bytearray is divided in place and returned; bytes give a new bytes object."""
+        if 0 <= k <= FR_FFT_MAX_K:
+            _need(coeffs, 32 << k, "coeffs")
+        _need(z, 32, "z")
+        rem = C.create_string_buffer(32)
+        if isinstance(coeffs, bytearray):
+            buf = (C.c_char * len(coeffs)).from_buffer(coeffs)
+            self._check(self._lib.h2agg_fr_poly_divide(self._ctx, C.addressof(buf), k, z, C.addressof(buf), rem))
+            return coeffs, rem.raw
+        out = C.create_string_buffer(len(coeffs))
+        self._check(self._lib.h2agg_fr_poly_divide(self._ctx, C.cast(C.c_char_p(bytes(coeffs)), C.c_void_p), k, z, out, rem))
+        return out.raw, rem.raw
+
+    def fr_poly_divide_device(self, d_poly_ptr: int, k: int, z: bytes, d_quot_ptr: int, d_rem_ptr: Optional[int] = None):
+        """h2agg_fr_poly_divide_device: device memory in and out, queued on the context's stream (no synchronisation);
+        d_quot_ptr == d_poly_ptr is allowed; d_rem_ptr: 32 bytes of device memory, or None"""
+        _need(z, 32, "z")
+        self._check(self._lib.h2agg_fr_poly_divide_device(self._ctx, d_poly_ptr, k, z, d_quot_ptr, d_rem_ptr))
+
+    def _multiopen(self, fn, g_handle: int, polys_arg, npoly: int, k: int, queries, points: bytes, v: bytes):
+        _need(v, 32, "v")
+        qs, nq, npoints = self._queries(queries, points)
+        cap = max(min(nq, npoints), 1)
+        w, gp, ng = C.create_string_buffer(64 * cap), (C.c_uint32 * cap)(), C.c_size_t()
+        self._check(fn(self._ctx, g_handle, polys_arg, npoly, k, qs, nq, points, npoints, v, w, gp, C.byref(ng)))
+        return list(gp[:ng.value]), [w.raw[64 * g:64 * g + 64] for g in range(ng.value)]
+
+    def kzg_multiopen(self, g_handle: int, polys: bytes, k: int, queries, points: bytes, v: bytes):
+        """h2agg_kzg_multiopen: the GWC opening of queries [(poly, point), ...] over a host slab [npoly][2^k] -> (the point
+        index of every group in first-seen order, the canonical affine W of every group)"""
+        npoly = self._slab(polys, k)
+        return self._multiopen(self._lib.h2agg_kzg_multiopen, g_handle, C.cast(C.c_char_p(bytes(polys)), C.c_void_p), npoly, k,
+                               queries, points, v)
+
+    def kzg_multiopen_device(self, g_handle: int, d_polys_ptr: int, npoly: int, k: int, queries, points: bytes, v: bytes):
+        """h2agg_kzg_multiopen_device: as kzg_multiopen over a slab already in device memory"""
+        return self._multiopen(self._lib.h2agg_kzg_multiopen_device, g_handle, d_polys_ptr, npoly, k, queries, points, v)
+
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""
         _need(s, 32, "s")
@@ -533,7 +615,8 @@ class H2Agg:
         return h.value, m.value, k.value
 
     def last_phases(self) -> str:
-        """wall-clock split of the last verify_aggregation call (after debug_configure("phases", 1)): h2agg_last_phases"""
+        """wall-clock split of the last verify_aggregation call, or the combine / divide / commit split of the last
+        kzg_multiopen call (after debug_configure("phases", 1)): h2agg_last_phases"""
         return (self._lib.h2agg_last_phases(self._ctx) or b"").decode()
 
     def transcript_configure(self, backend: str = "auto"):

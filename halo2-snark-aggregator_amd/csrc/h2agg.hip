@@ -31,6 +31,7 @@
 #include "seg_msm_kernels.hpp"
 #include "g1_fft_kernels.hpp"
 #include "fr_fft_kernels.hpp"
+#include "poly_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -184,6 +185,10 @@ struct h2agg_ctx {
     DevBuf frfft_tw[2], frfft_shift, frfft_work;
     int frfft_tw_k[2] = {-1, -1};
     int dbg_fr_fft_local = 0;   // debug key fr_fft_local: radix-2 stages fused per pass (0 = FR_FFT_LOCAL)
+    // KZG openings (csrc/poly_open.inc): the chunk values of every level above the coefficients, the queries / group lists of
+    // the call in progress, the combined polynomials (then their quotients) of a multiopen, its Jacobian commitments
+    DevBuf poly_work, poly_desc, poly_slab, poly_jac;
+    int dbg_fr_poly_chunk = 0;   // debug key fr_poly_chunk: log2 of the coefficients per workgroup (0 = FR_POLY_CHUNK_LOG)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -1346,7 +1351,8 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->wsum[0], &c->wsum[1], &c->wsum[2], &c->big_list[0], &c->big_list[1], &c->big_keys[0], &c->big_keys[1], &c->big_part[0], &c->big_part[1], &c->fix_list[0], &c->fix_list[1], &c->glv_buf, &c->parts, &c->small, &c->endo_buf, &c->tile_counts, &c->fb_long,
                       &c->sch_regs, &c->sch_in, &c->sch_scalars[0], &c->sch_scalars[1], &c->sch_bases[0], &c->sch_bases[1], &c->sch_endo,
                       &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale,
-                      &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work};
+                      &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work,
+                      &c->poly_work, &c->poly_desc, &c->poly_slab, &c->poly_jac};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -2341,6 +2347,10 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         if (value < 0 || value > (int)FR_FFT_TILE_LOG) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_fft_local must be 0 or 1 .. 11");
         c->dbg_fr_fft_local = value;
     }
+    else if (k == "fr_poly_chunk") {                         // KZG openings: log2 of the coefficients per workgroup, 3 .. 11 (0 = the default, 11)
+        if (value != 0 && (value < (int)FR_POLY_PER_LOG || value > (int)FR_POLY_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_poly_chunk must be 0 or 3 .. 11");
+        c->dbg_fr_poly_chunk = value;
+    }
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
     return H2AGG_OK;
@@ -2554,3 +2564,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "verifier.inc"
 #include "params.inc"
 #include "fr_fft.inc"
+#include "poly_open.inc"

@@ -1,4 +1,5 @@
-"""EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), and the two ways to commit to a polynomial.
+"""EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), the two ways to commit to a polynomial, and
+the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -56,3 +57,43 @@ def commit_lagrange(eng, gl_handle: int, evals: bytes) -> bytes:
     """sum_i evals[i] * g_lagrange[i] against the Lagrange table (ParamsKZG.g_lagrange): the same point as commit_coeff of
     lagrange_to_coeff(evals)"""
     return eng.g1_msm_preloaded(gl_handle, evals)
+
+
+def eval_polynomial(eng, coeffs: bytes, z: bytes) -> bytes:
+    """a(z) for 2^k coefficients (eval_polynomial of arithmetic.rs), 32 bytes"""
+    k = (len(coeffs) // 32).bit_length() - 1
+    return eng.fr_poly_eval(_poly(coeffs, k, "coeffs"), k, [(0, 0)], z)
+
+
+def kate_division(eng, coeffs: bytes, z: bytes) -> bytes:
+    """the quotient of a(X) by (X - z): the n - 1 coefficients halo2's kate_division returns (the engine writes n, the top
+    one zero; the remainder a(z) is dropped, as halo2 drops it)"""
+    k = (len(coeffs) // 32).bit_length() - 1
+    quot, _ = eng.fr_poly_divide(bytes(_poly(coeffs, k, "coeffs")), k, z)
+    return quot[:len(quot) - 32]
+
+
+def group_queries(queries):
+    """[(poly, point), ...] -> [(point, [poly, ...]), ...]: one group per distinct point, in the order the points are first
+    seen, every group's polynomials in query order (multiopen.rs:31-43 with the point index in the rotation's role)"""
+    groups = []
+    for poly, point in queries:
+        for pt, members in groups:
+            if pt == point:
+                members.append(poly)
+                break
+        else:
+            groups.append((point, [poly]))
+    return groups
+
+
+def multiopen_prove(eng, g_handle: int, polys: bytes, k: int, queries, points: bytes, v: bytes):
+    """the prover half of the GWC multiopen over a slab [npoly][2^k] of coefficients: -> (evals, groups, ws) with evals[q]
+    the 32-byte value of query q, groups = group_queries(queries), ws[g] the canonical affine W of group g (64 bytes)"""
+    queries = [(int(p), int(z)) for p, z in queries]
+    evals = eng.fr_poly_eval(polys, k, queries, points)
+    group_points, ws = eng.kzg_multiopen(g_handle, polys, k, queries, points, v)
+    groups = group_queries(queries)
+    if [pt for pt, _ in groups] != group_points:
+        raise RuntimeError("the library grouped the queries differently from group_queries")
+    return [evals[32 * q:32 * q + 32] for q in range(len(queries))], groups, ws

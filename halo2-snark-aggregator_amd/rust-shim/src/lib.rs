@@ -29,6 +29,9 @@ extern "C" {
     pub fn h2agg_host_alloc(ctx: *mut h2agg_ctx, bytes: usize, out: *mut *mut u8) -> c_int;
     pub fn h2agg_host_free(ctx: *mut h2agg_ctx, p: *mut u8) -> c_int;
     pub fn h2agg_fr_fft(ctx: *mut h2agg_ctx, input: *const u8, k: std::os::raw::c_uint, inverse: c_int, shift: *const u8, out: *mut u8) -> c_int;
+    pub fn h2agg_fr_poly_eval(ctx: *mut h2agg_ctx, polys: *const u8, npoly: usize, k: std::os::raw::c_uint, queries: *const u32, nq: usize, points: *const u8, npoints: usize, out: *mut u8) -> c_int;
+    pub fn h2agg_fr_poly_divide(ctx: *mut h2agg_ctx, input: *const u8, k: std::os::raw::c_uint, z: *const u8, out: *mut u8, rem: *mut u8) -> c_int;
+    pub fn h2agg_kzg_multiopen(ctx: *mut h2agg_ctx, g_handle: u64, polys: *const u8, npoly: usize, k: std::os::raw::c_uint, queries: *const u32, nq: usize, points: *const u8, npoints: usize, v: *const u8, w_aff: *mut u8, group_points: *mut u32, ngroups: *mut usize) -> c_int;
 }
 
 /// One context per thread (the chips are used single-threaded, verify_circuit.rs:114-201; the SDK's rayon workers each get
@@ -197,6 +200,86 @@ pub fn best_fft<F: FieldExt>(a: &mut [F], omega: F, log_n: u32) {
             *x *= n; // best_fft itself does not scale
         }
     }
+}
+
+fn check(g: &Gpu, rc: c_int, what: &str) {
+    if rc != 0 {
+        let msg = unsafe { std::ffi::CStr::from_ptr(h2agg_last_error(g.ctx)) };
+        panic!("{} failed ({}): {:?}", what, rc, msg);
+    }
+}
+
+/// halo2_proofs' `eval_polynomial(poly, point)` (arithmetic.rs, recalled like best_fft) through h2agg_fr_poly_eval.
+/// UNCOMPILED like the rest of this file.  The library takes 2^k coefficients: a shorter slice is zero-padded.
+pub fn eval_polynomial<F: FieldExt>(poly: &[F], point: F) -> F {
+    let k = poly.len().max(1).next_power_of_two().trailing_zeros();
+    let mut buf = Vec::with_capacity(32usize << k);
+    for x in poly.iter() {
+        put_fe(&mut buf, x);
+    }
+    buf.resize(32usize << k, 0);
+    let mut z = Vec::with_capacity(32);
+    put_fe(&mut z, &point);
+    let mut out = [0u8; 32];
+    let query = [0u32, 0u32];
+    with_gpu(|g| {
+        let rc = unsafe { h2agg_fr_poly_eval(g.ctx, buf.as_ptr(), 1, k, query.as_ptr(), 1, z.as_ptr(), 1, out.as_mut_ptr()) };
+        check(g, rc, "h2agg_fr_poly_eval");
+    });
+    fe_from(&out)
+}
+
+/// halo2_proofs' `kate_division(a, b)`: the quotient of a(X) by (X - b), `a.len() - 1` coefficients, the remainder dropped.
+/// The library writes 2^k coefficients with the zero on top; the tail is cut off here.
+pub fn kate_division<F: FieldExt>(a: &[F], b: F) -> Vec<F> {
+    let k = a.len().max(1).next_power_of_two().trailing_zeros();
+    let mut buf = Vec::with_capacity(32usize << k);
+    for x in a.iter() {
+        put_fe(&mut buf, x);
+    }
+    buf.resize(32usize << k, 0);
+    let mut z = Vec::with_capacity(32);
+    put_fe(&mut z, &b);
+    let mut rem = [0u8; 32];
+    with_gpu(|g| {
+        let rc = unsafe { h2agg_fr_poly_divide(g.ctx, buf.as_ptr(), k, z.as_ptr(), buf.as_mut_ptr(), rem.as_mut_ptr()) };
+        check(g, rc, "h2agg_fr_poly_divide");
+    });
+    buf.chunks_exact(32).take(a.len().saturating_sub(1)).map(fe_from).collect()
+}
+
+/// The prover half of the GWC multiopen (poly/kzg/multiopen/gwc/prover.rs, recalled) over `polys` of one length 2^k:
+/// `queries` are (polynomial index, point index) pairs; returns one affine W (64 bytes, x || y) per distinct point in
+/// first-seen order — the order batch_multi_open_proofs expects them in (multiopen.rs:31-48).  `g_handle` is a resident
+/// monomial table (h2agg_params_setup / h2agg_bases_upload) of at least 2^k points.
+pub fn multiopen<F: FieldExt>(g_handle: u64, polys: &[Vec<F>], queries: &[(u32, u32)], points: &[F], v: F) -> Vec<[u8; 64]> {
+    let k = polys[0].len().trailing_zeros();
+    let mut slab = Vec::with_capacity((32usize << k) * polys.len());
+    for p in polys.iter() {
+        assert_eq!(p.len(), 1usize << k, "multiopen: polynomials of one length 2^k");
+        for x in p.iter() {
+            put_fe(&mut slab, x);
+        }
+    }
+    let mut zs = Vec::with_capacity(32 * points.len());
+    for z in points.iter() {
+        put_fe(&mut zs, z);
+    }
+    let mut vb = Vec::with_capacity(32);
+    put_fe(&mut vb, &v);
+    let flat: Vec<u32> = queries.iter().flat_map(|&(p, z)| [p, z]).collect();
+    let cap = queries.len().min(points.len());
+    let mut w = vec![0u8; 64 * cap];
+    let mut group_points = vec![0u32; cap];
+    let mut ngroups = 0usize;
+    with_gpu(|g| {
+        let rc = unsafe {
+            h2agg_kzg_multiopen(g.ctx, g_handle, slab.as_ptr(), polys.len(), k, flat.as_ptr(), queries.len(), zs.as_ptr(),
+                                points.len(), vb.as_ptr(), w.as_mut_ptr(), group_points.as_mut_ptr(), &mut ngroups)
+        };
+        check(g, rc, "h2agg_kzg_multiopen");
+    });
+    w.chunks_exact(64).take(ngroups).map(|c| c.try_into().unwrap()).collect()
 }
 
 /// `multi_exp` plus the reference's observable side effect: `ctx.point_list = points.map(|x| format!("{:?}", x))`

@@ -461,7 +461,10 @@ int h2agg_verify_proofs(h2agg_ctx* ctx, const h2agg_circuit_proofs* circuits, si
  * h2agg_verify_proofs) call as
  * one line — " name=milliseconds" per phase in order, then the CPU the calling thread started and ended on and how often it was
  * preempted, then every host sponge chain's start offset, run time (microseconds) and CPU.  For latency reports (which phase a
- * slow call spent its time in); costs a few clock reads per call.  Owned by the context, valid until its next call. */
+ * slow call spent its time in); costs a few clock reads per call.  Owned by the context, valid until its next call.
+ * After an h2agg_kzg_multiopen* call it is that call's split instead, from events on the context's stream:
+ * " combine=ms divide=ms commit=ms" — the linear combinations, the up- and down-sweep over all groups, and the batch MSM with
+ * the conversion to affine (this one includes the host's wait between the two). */
 const char* h2agg_last_phases(h2agg_ctx* ctx);
 
 /* ---- multi-GPU exchange -----------------------------------------------------------
@@ -564,6 +567,58 @@ int h2agg_g2_batch_compress(const uint8_t* aff, size_t n, uint8_t* out);
 int h2agg_fr_fft(h2agg_ctx* ctx, const uint8_t* in, unsigned k, int inverse, const uint8_t shift[32], uint8_t* out);
 int h2agg_fr_fft_device(h2agg_ctx* ctx, const void* d_in, unsigned k, int inverse, const uint8_t shift[32], void* d_out);
 
+/* ---- KZG openings: evaluation, division by (X - z), the GWC multiopen prover -------------------------------------------
+ * Stand for: eval_polynomial and kate_division (halo2_proofs arithmetic.rs) and the prover of poly/kzg/multiopen/gwc
+ * (prover.rs).  halo2_proofs is an unvendored git dependency of the reference: recalled from upstream, not pinned (DESIGN.md
+ * section 2); what the entry points compute is this definition.  Which W a verifier accepts IS pinned:
+ * halo2-snark-aggregator-api/src/systems/halo2/multiopen.rs:23-69 (one W per distinct point in first-seen order, the queries of
+ * a point folded with v^0 for the first), the verifier half being h2agg_schema_batch_multi_open above.
+ *
+ * A polynomial is n = 2^k canonical 32-byte little-endian Fr coefficients a[0..n), low degree first, k <= 24.
+ *   eval      a(z) = sum_i a[i] z^i
+ *   divide    q[j] = sum_{i>j} a[i] z^(i-j-1) for j < n, so q[n-1] = 0;  rem = a(z).  Then a(X) = q(X) (X - z) + rem.
+ *             q is written as n elements with the zero on top, so it goes straight into an MSM over 2^k bases (halo2's
+ *             kate_division returns the first n - 1).  q does not depend on a[0]: dividing a and dividing a - a(z) give the
+ *             same quotient.
+ *   multiopen npoly polynomials of one k, npoints points, nq queries, a challenge v.  A query is a pair of uint32_t
+ *             {polynomial index, point index}; `queries` holds nq such pairs.  Queries are grouped by point index in
+ *             first-seen order (multiopen.rs:31-43 with the point index in the rotation's role).  Group g with queries
+ *             p_0, p_1, ... (in query order) at point z_g gives c_g(X) = sum_m v^m p_m(X) and
+ *             W_g = sum_j quot(c_g, z_g)[j] * g[j] against the monomial table (ParamsKZG.g, e.g. from h2agg_params_setup).
+ *             A polynomial may appear in several groups and more than once in one; points that no query names are ignored.
+ * z == 0 (and v == 0) are legal everywhere.
+ *
+ * h2agg_fr_poly_eval / _device: `polys` is a slab [npoly][2^k] in host (pageable or h2agg_host_alloc) / DEVICE memory;
+ *   queries and points (npoints x 32 bytes) are host memory; out = nq x 32 bytes to the host, out[q] = the value of query q;
+ *   synchronous.  All queries go through one set of launches.
+ * h2agg_fr_poly_divide: host buffers, out = 2^k elements, out == in allowed, rem = 32 bytes; synchronous.
+ * h2agg_fr_poly_divide_device: 2^k elements in DEVICE memory in and out, d_quot == d_poly allowed (otherwise the two must not
+ *   overlap); d_rem is 32 bytes of device memory or NULL; queued on the context's stream, no synchronisation.  The buffer
+ *   rules are those of h2agg_fr_fft_device (complete on that stream before the call, untouched until the stream has passed
+ *   the call; a workspace that has to grow drains the device first).
+ * h2agg_kzg_multiopen_device / h2agg_kzg_multiopen: the slab in DEVICE / host memory; g_handle a resident base table of at
+ *   least 2^k points.  Writes, to the host: *ngroups, one canonical affine W per group (64 bytes each, identity = zeros) to
+ *   w_aff and each group's point index to group_points — both with room for min(nq, npoints) entries; synchronous.  The work
+ *   memory is one quotient slab [groups][2^k] kept in the context (128 MiB per group at k = 22), committed by
+ *   h2agg_g1_msm_device_batch_async.  With the debug key "phases", h2agg_last_phases gives the call's split.
+ * Refusals, the context stays usable after each: k > 24, a null buffer, nq == 0 or nq > 65535, a polynomial index >= npoly,
+ *   a point index >= npoints, a table shorter than 2^k or an unknown handle: H2AGG_ERR_INVALID.  A point, z or v >= r:
+ *   H2AGG_ERR_NONCANONICAL.  A coefficient >= r: H2AGG_ERR_NONCANONICAL through the context's device status — from the call for
+ *   the synchronous entry points, at h2agg_synchronize (or the next synchronous entry point), once, for
+ *   h2agg_fr_poly_divide_device; outputs are then unspecified.  Out of memory: H2AGG_ERR_NOMEM. */
+int h2agg_fr_poly_eval(h2agg_ctx* ctx, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries, size_t nq,
+                       const uint8_t* points, size_t npoints, uint8_t* out);
+int h2agg_fr_poly_eval_device(h2agg_ctx* ctx, const void* d_polys, size_t npoly, unsigned k, const uint32_t* queries, size_t nq,
+                              const uint8_t* points, size_t npoints, uint8_t* out);
+int h2agg_fr_poly_divide(h2agg_ctx* ctx, const uint8_t* in, unsigned k, const uint8_t z[32], uint8_t* out, uint8_t rem[32]);
+int h2agg_fr_poly_divide_device(h2agg_ctx* ctx, const void* d_poly, unsigned k, const uint8_t z[32], void* d_quot, void* d_rem);
+int h2agg_kzg_multiopen(h2agg_ctx* ctx, uint64_t g_handle, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries,
+                        size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32], uint8_t* w_aff,
+                        uint32_t* group_points, size_t* ngroups);
+int h2agg_kzg_multiopen_device(h2agg_ctx* ctx, uint64_t g_handle, const void* d_polys, size_t npoly, unsigned k,
+                               const uint32_t* queries, size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32],
+                               uint8_t* w_aff, uint32_t* group_points, size_t* ngroups);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
@@ -623,9 +678,12 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *       "prewake" 0|1     a from-bytes call wakes its sponge workers at entry (they spin until the chains are posted), one more
  *                         for the pairing's second Miller loop, and waits only for the element streams in front of the sponges
  *                         (default 1; 0: the three latency measures of round 6 off, for an A/B)
- *       "phases" 0|1      keep every aggregation call's wall-clock split for h2agg_last_phases
+ *       "phases" 0|1      keep every aggregation call's wall-clock split, and every h2agg_kzg_multiopen* call's split by events
+ *                         (combine / divide / commit), for h2agg_last_phases
  *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
  *                         1024 elements then run the multi-pass paths
+ *       "fr_poly_chunk" t the KZG opening kernels cut a polynomial into chunks of 2^t coefficients per workgroup, 3 .. 11 (0 = the
+ *                         default, 11): inputs of 64 to 1024 coefficients then run the three- and four-level plans
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
  *       "seg_chunk" n     h2agg_g1_msm_segmented / h2agg_verify_proofs: at most n points per set of launches of the segmented
  *                         multi_exp (0 = automatic, 16384); a segment longer than that is an ordinary multi_exp of its own
