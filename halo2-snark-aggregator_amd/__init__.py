@@ -22,6 +22,8 @@ OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
 FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
 FR_FFT_MAX_K = 24
 FR_POLY_CHUNK = 11   # log2 of the coefficients per workgroup of the KZG opening kernels by default (csrc/poly_kernels.hpp)
+FR_SCAN_CHUNK = 11   # log2 of the elements per workgroup of the grand-product kernels by default (csrc/prod_kernels.hpp)
+FR_PROD_MAX_COLUMNS = 16
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
@@ -162,6 +164,14 @@ def load_library():
                                       C.POINTER(C.c_uint32), C.POINTER(sz)]),
         "h2agg_kzg_multiopen_device": (i32, [ctxp, u64, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, vp,
                                              C.POINTER(C.c_uint32), C.POINTER(sz)]),
+        "h2agg_fr_batch_invert": (i32, [ctxp, vp, sz, vp]),
+        "h2agg_fr_batch_invert_device": (i32, [ctxp, vp, sz, vp]),
+        "h2agg_fr_grand_product": (i32, [ctxp, vp, vp, C.c_uint, sz, u8p, vp, vp]),
+        "h2agg_fr_grand_product_device": (i32, [ctxp, vp, vp, C.c_uint, sz, u8p, vp, vp]),
+        "h2agg_permutation_product": (i32, [ctxp, vp, vp, sz, C.c_uint, sz, u8p, u8p, u8p, u8p, u8p, vp, vp]),
+        "h2agg_permutation_product_device": (i32, [ctxp, vp, vp, sz, C.c_uint, sz, u8p, u8p, u8p, u8p, u8p, vp, vp]),
+        "h2agg_lookup_product": (i32, [ctxp, vp, vp, vp, vp, C.c_uint, sz, u8p, u8p, vp, vp]),
+        "h2agg_lookup_product_device": (i32, [ctxp, vp, vp, vp, vp, C.c_uint, sz, u8p, u8p, vp, vp]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -558,6 +568,91 @@ class H2Agg:
     def kzg_multiopen_device(self, g_handle: int, d_polys_ptr: int, npoly: int, k: int, queries, points: bytes, v: bytes):
         """h2agg_kzg_multiopen_device: as kzg_multiopen over a slab already in device memory"""
         return self._multiopen(self._lib.h2agg_kzg_multiopen_device, g_handle, d_polys_ptr, npoly, k, queries, points, v)
+
+    # ------------------------------------------------------------------ grand products
+    @staticmethod
+    def _hostptr(data):
+        return C.cast(C.c_char_p(bytes(data)), C.c_void_p)
+
+    def _column(self, data, k: int, u: int, what: str, cols: int = 1):
+        """a column slab [cols][2^k]; sizes are checked only where the library would go on to read the buffer"""
+        if 0 <= k <= FR_FFT_MAX_K and 0 <= u < (1 << k) and 1 <= cols <= FR_PROD_MAX_COLUMNS:
+            _need(data, (32 << k) * cols, what)
+        return self._hostptr(data)
+
+    def fr_batch_invert(self, data):
+        """h2agg_fr_batch_invert: n canonical elements -> their inverses, 0 for 0 (ff::BatchInvert).  A bytearray is inverted
+        in place and returned; bytes give a new bytes object."""
+        n = len(data) // 32
+        _need(data, 32 * n, "data")
+        if isinstance(data, bytearray):
+            if n:
+                buf = (C.c_char * len(data)).from_buffer(data)
+                self._check(self._lib.h2agg_fr_batch_invert(self._ctx, C.addressof(buf), n, C.addressof(buf)))
+            return data
+        out = C.create_string_buffer(max(32 * n, 1))
+        self._check(self._lib.h2agg_fr_batch_invert(self._ctx, self._hostptr(data), n, out))
+        return out.raw[:32 * n]
+
+    def fr_batch_invert_device(self, d_in_ptr: int, n: int, d_out_ptr: int):
+        """h2agg_fr_batch_invert_device: n elements in device memory, queued on the context's stream (no synchronisation);
+        d_out_ptr == d_in_ptr is allowed"""
+        self._check(self._lib.h2agg_fr_batch_invert_device(self._ctx, d_in_ptr, n, d_out_ptr))
+
+    def fr_grand_product(self, num: bytes, den: Optional[bytes], k: int, u: int, init: bytes):
+        """h2agg_fr_grand_product: -> (out[0 .. u] as 32 * (u + 1) bytes, out[u]); num (and den, or None) hold u elements"""
+        _need(init, 32, "init")
+        if 0 <= k <= FR_FFT_MAX_K and 0 <= u < (1 << k):
+            _need(num, 32 * u, "num")
+            if den is not None:
+                _need(den, 32 * u, "den")
+        out, last = C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+        self._check(self._lib.h2agg_fr_grand_product(self._ctx, self._hostptr(num), None if den is None else self._hostptr(den),
+                                                     k, u, init, out, last))
+        return out.raw, last.raw
+
+    def fr_grand_product_device(self, d_num_ptr: int, d_den_ptr: Optional[int], k: int, u: int, init: bytes, d_out_ptr: int,
+                                d_last_ptr: Optional[int] = None):
+        """h2agg_fr_grand_product_device: device memory in and out, queued on the context's stream (no synchronisation);
+        d_out_ptr may alias d_num_ptr; d_den_ptr and d_last_ptr may be None"""
+        _need(init, 32, "init")
+        self._check(self._lib.h2agg_fr_grand_product_device(self._ctx, d_num_ptr, d_den_ptr, k, u, init, d_out_ptr, d_last_ptr))
+
+    def permutation_product(self, values: bytes, sigmas: bytes, m: int, k: int, u: int, beta: bytes, gamma: bytes, delta: bytes,
+                            delta_first: bytes, init: bytes):
+        """h2agg_permutation_product: one permutation set of m columns (slabs [m][2^k]) -> (z[0 .. u], z[u])"""
+        for name, v in (("beta", beta), ("gamma", gamma), ("delta", delta), ("delta_first", delta_first), ("init", init)):
+            _need(v, 32, name)
+        out, last = C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+        self._check(self._lib.h2agg_permutation_product(self._ctx, self._column(values, k, u, "values", m),
+                                                        self._column(sigmas, k, u, "sigmas", m), m, k, u, beta, gamma, delta,
+                                                        delta_first, init, out, last))
+        return out.raw, last.raw
+
+    def permutation_product_device(self, d_values_ptr: int, d_sigmas_ptr: int, m: int, k: int, u: int, beta: bytes, gamma: bytes,
+                                   delta: bytes, delta_first: bytes, init: bytes, d_out_ptr: int, d_last_ptr: Optional[int] = None):
+        """h2agg_permutation_product_device: slabs and z in device memory, queued on the context's stream (no synchronisation)"""
+        for name, v in (("beta", beta), ("gamma", gamma), ("delta", delta), ("delta_first", delta_first), ("init", init)):
+            _need(v, 32, name)
+        self._check(self._lib.h2agg_permutation_product_device(self._ctx, d_values_ptr, d_sigmas_ptr, m, k, u, beta, gamma, delta,
+                                                               delta_first, init, d_out_ptr, d_last_ptr))
+
+    def lookup_product(self, a: bytes, s: bytes, ap: bytes, sp: bytes, k: int, u: int, beta: bytes, gamma: bytes):
+        """h2agg_lookup_product: compressed input, table and their permuted forms (2^k rows each) -> (z[0 .. u], z[u])"""
+        _need(beta, 32, "beta")
+        _need(gamma, 32, "gamma")
+        out, last = C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+        cols = [self._column(x, k, u, what) for x, what in ((a, "a"), (s, "s"), (ap, "ap"), (sp, "sp"))]
+        self._check(self._lib.h2agg_lookup_product(self._ctx, *cols, k, u, beta, gamma, out, last))
+        return out.raw, last.raw
+
+    def lookup_product_device(self, d_a_ptr: int, d_s_ptr: int, d_ap_ptr: int, d_sp_ptr: int, k: int, u: int, beta: bytes,
+                              gamma: bytes, d_out_ptr: int, d_last_ptr: Optional[int] = None):
+        """h2agg_lookup_product_device: columns and z in device memory, queued on the context's stream (no synchronisation)"""
+        _need(beta, 32, "beta")
+        _need(gamma, 32, "gamma")
+        self._check(self._lib.h2agg_lookup_product_device(self._ctx, d_a_ptr, d_s_ptr, d_ap_ptr, d_sp_ptr, k, u, beta, gamma,
+                                                          d_out_ptr, d_last_ptr))
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

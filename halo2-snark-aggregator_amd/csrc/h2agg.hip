@@ -32,6 +32,7 @@
 #include "g1_fft_kernels.hpp"
 #include "fr_fft_kernels.hpp"
 #include "poly_kernels.hpp"
+#include "prod_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -189,6 +190,10 @@ struct h2agg_ctx {
     // the call in progress, the combined polynomials (then their quotients) of a multiopen, its Jacobian commitments
     DevBuf poly_work, poly_desc, poly_slab, poly_jac;
     int dbg_fr_poly_chunk = 0;   // debug key fr_poly_chunk: log2 of the coefficients per workgroup (0 = FR_POLY_CHUNK_LOG)
+    // grand products (csrc/prod.inc): the num and den columns of a permutation / lookup call (den: then R^2 / den, also for
+    // h2agg_fr_grand_product), the chunk products of every level above the elements, the two-level table of w^i
+    DevBuf prod_num, prod_den, prod_lvl, prod_tab;
+    int dbg_fr_scan_chunk = 0;   // debug key fr_scan_chunk: log2 of the elements per workgroup (0 = FR_PROD_CHUNK_LOG)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -1352,7 +1357,8 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->sch_regs, &c->sch_in, &c->sch_scalars[0], &c->sch_scalars[1], &c->sch_bases[0], &c->sch_bases[1], &c->sch_endo,
                       &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale,
                       &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work,
-                      &c->poly_work, &c->poly_desc, &c->poly_slab, &c->poly_jac};
+                      &c->poly_work, &c->poly_desc, &c->poly_slab, &c->poly_jac,
+                      &c->prod_num, &c->prod_den, &c->prod_lvl, &c->prod_tab};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -2351,6 +2357,10 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         if (value != 0 && (value < (int)FR_POLY_PER_LOG || value > (int)FR_POLY_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_poly_chunk must be 0 or 3 .. 11");
         c->dbg_fr_poly_chunk = value;
     }
+    else if (k == "fr_scan_chunk") {                         // grand products: log2 of the elements per workgroup, 3 .. 11 (0 = the default, 11)
+        if (value != 0 && (value < (int)FR_PROD_PER_LOG || value > (int)FR_PROD_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_scan_chunk must be 0 or 3 .. 11");
+        c->dbg_fr_scan_chunk = value;
+    }
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
     return H2AGG_OK;
@@ -2565,3 +2575,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "params.inc"
 #include "fr_fft.inc"
 #include "poly_open.inc"
+#include "prod.inc"

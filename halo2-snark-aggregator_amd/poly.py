@@ -1,5 +1,7 @@
 """EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), the two ways to commit to a polynomial, and
-the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen).
+the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen);
+and the grand products of the permutation and lookup arguments (h2agg_fr_batch_invert, h2agg_permutation_product,
+h2agg_lookup_product).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -97,3 +99,47 @@ def multiopen_prove(eng, g_handle: int, polys: bytes, k: int, queries, points: b
     if [pt for pt, _ in groups] != group_points:
         raise RuntimeError("the library grouped the queries differently from group_queries")
     return [evals[32 * q:32 * q + 32] for q in range(len(queries))], groups, ws
+
+
+# ---------------------------------------------------------------------------------------------- grand products
+def batch_invert(eng, xs: bytes) -> bytes:
+    """ff::BatchInvert: the inverse of every element, zeros left alone"""
+    return eng.fr_batch_invert(xs)
+
+
+def _z_column(z: bytes, k: int, usable: int, blinding):
+    """z[0 .. usable] -> a column of 2^k rows: the n - usable - 1 top rows from `blinding` (32 bytes each), or zero"""
+    top = (1 << k) - usable - 1
+    if blinding is None:
+        return z + bytes(32 * top)
+    if len(blinding) != 32 * top:
+        raise ValueError("blinding must be %d elements of 32 bytes" % top)
+    return z + bytes(blinding)
+
+
+def permutation_products(eng, values, sigmas, k: int, usable: int, beta: bytes, gamma: bytes, delta: bytes, chunk_len: int,
+                         blinding=None):
+    """permutation::prover::commit over m columns: values and sigmas are lists of m Lagrange columns (2^k elements each).
+    The columns are cut into sets of chunk_len; set s starts at the previous set's z[usable] (1 for the first) and at
+    delta_first = delta^(s * chunk_len).  -> one column of 2^k rows per set.  blinding: None, or one block of
+    2^k - usable - 1 elements per set for the rows above `usable`."""
+    if len(values) != len(sigmas) or not values or chunk_len < 1:
+        raise ValueError("values and sigmas must be the same non-zero number of columns, chunk_len >= 1")
+    for col in list(values) + list(sigmas):
+        _poly(col, k, "column")
+    d = int.from_bytes(delta, "little")
+    init = (1).to_bytes(32, "little")
+    out = []
+    for s, lo in enumerate(range(0, len(values), chunk_len)):
+        vs, ss = values[lo:lo + chunk_len], sigmas[lo:lo + chunk_len]
+        delta_first = pow(d, lo, R_MOD).to_bytes(32, "little")
+        z, init = eng.permutation_product(b"".join(vs), b"".join(ss), len(vs), k, usable, beta, gamma, delta, delta_first, init)
+        out.append(_z_column(z, k, usable, None if blinding is None else blinding[s]))
+    return out
+
+
+def lookup_product(eng, a: bytes, s: bytes, ap: bytes, sp: bytes, k: int, usable: int, beta: bytes, gamma: bytes, blinding=None):
+    """lookup::prover::commit_product: the Z column of one lookup from the compressed input a, the compressed table s and
+    their permuted forms (permute_expression_pair, a sort, is the caller's).  -> one column of 2^k rows."""
+    z, _last = eng.lookup_product(_poly(a, k, "a"), _poly(s, k, "s"), _poly(ap, k, "ap"), _poly(sp, k, "sp"), k, usable, beta, gamma)
+    return _z_column(z, k, usable, blinding)

@@ -619,6 +619,62 @@ int h2agg_kzg_multiopen_device(h2agg_ctx* ctx, uint64_t g_handle, const void* d_
                                const uint32_t* queries, size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32],
                                uint8_t* w_aff, uint32_t* group_points, size_t* ngroups);
 
+/* ---- Grand products: batch inversion, the permutation and lookup Z columns ------------------------------------------------
+ * Stand for: ff::BatchInvert, permutation::prover::commit and lookup::prover::commit_product of halo2_proofs — an unvendored
+ * git dependency of the reference: recalled from upstream, not pinned; what the entry points compute
+ * is this definition.  Which Z a verifier accepts IS pinned: halo2-snark-aggregator-api/src/systems/halo2/permutation.rs:70-133
+ * (l_0 (1 - z_0); l_last (z^2 - z) on the last set; l_0 (z_i - z_{i-1}(w^last X)) between sets; the row identity
+ * z(wX) prod(p + beta s + gamma) = z(X) prod(p + delta^j beta X + gamma)) and lookup.rs:98-113
+ * (z(wX)(a' + beta)(s' + gamma) = z(X)(a + beta)(s + gamma)).
+ *
+ * All elements are canonical 32-byte little-endian Fr.  Row i of a column of n = 2^k rows sits at w^i, w the root
+ * h2agg_fr_fft uses for k, k <= 24.  u is the number of usable rows (n - (blinding_factors + 1) in halo2), 0 <= u <= n - 1.
+ *   batch_invert         out[i] = in[i]^-1, and out[i] = 0 where in[i] = 0 (ff::BatchInvert: zeros are skipped, a zero is not
+ *                        an error — h2agg_fr_batch_op(INV) answers H2AGG_ERR_DIV_ZERO).  Any 0 <= n <= 2^24, not only powers
+ *                        of two; n == 0 is a no-op.
+ *   grand_product        out[0] = init, out[i+1] = out[i] * num[i] * inv(den[i]) for i < u, with inv(0) = 0 as above.  den may
+ *                        be NULL: a plain running product.  num and den have at least u elements; exactly u + 1 elements of
+ *                        out are written (in halo2 the rows above u belong to the caller's blinding).  last[32] is optional
+ *                        and receives out[u].
+ *   permutation_product  one permutation set of m columns, 1 <= m <= 16; values and sigmas are slabs [m][n] in Lagrange form.
+ *                          num[i] = prod_j (values[j][i] + beta * dj * w^i + gamma),  dj = delta_first * delta^j
+ *                          den[i] = prod_j (values[j][i] + beta * sigmas[j][i] + gamma)
+ *                        The result is grand_product(num, den, u, init).  delta, delta_first (delta^(set_index * chunk_len))
+ *                        and init (the previous set's z[u], or 1) are arguments: the library holds no literal for them.
+ *   lookup_product       compressed input a, compressed table s, their permuted forms ap and sp, n rows each.
+ *                          num[i] = (a[i] + beta)(s[i] + gamma),  den[i] = (ap[i] + beta)(sp[i] + gamma)
+ *                        The result is grand_product(num, den, u, 1).  The theta-compression of the expressions (a linear
+ *                        combination) and permute_expression_pair (a sort) are the caller's job.
+ * Only rows i < u of a column are read.
+ *
+ * Every entry point is synchronous over host buffers (pageable or h2agg_host_alloc) and has a _device twin over DEVICE
+ * memory that is queued on the context's stream with no synchronisation; the buffer rules are those of h2agg_fr_fft_device
+ * (inputs complete on that stream before the call, nothing touched until the stream has passed the call; a workspace that
+ * has to grow drains the device first).  Outputs must not overlap inputs, except: d_out == d_in for batch_invert (and
+ * out == in for the host form), and d_out may alias d_num for grand_product.  d_last is 32 bytes of device memory or NULL.
+ * The work memory — the num and den columns and the chunk products — is kept in the context.
+ * Refusals, the context stays usable after each: k > 24, n > 2^24, u >= 2^k, m == 0 or m > 16, a null required buffer:
+ *   H2AGG_ERR_INVALID.  beta, gamma, delta, delta_first or init >= r: H2AGG_ERR_NONCANONICAL from the call.  A column element
+ *   >= r: H2AGG_ERR_NONCANONICAL through the context's device status — from the call for the synchronous entry points, at
+ *   h2agg_synchronize (or the next synchronous entry point), once, for the _device twins; outputs are then unspecified.  Out
+ *   of memory: H2AGG_ERR_NOMEM. */
+int h2agg_fr_batch_invert(h2agg_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out);
+int h2agg_fr_batch_invert_device(h2agg_ctx* ctx, const void* d_in, size_t n, void* d_out);
+int h2agg_fr_grand_product(h2agg_ctx* ctx, const uint8_t* num, const uint8_t* den, unsigned k, size_t u, const uint8_t init[32],
+                           uint8_t* out, uint8_t last[32]);
+int h2agg_fr_grand_product_device(h2agg_ctx* ctx, const void* d_num, const void* d_den, unsigned k, size_t u, const uint8_t init[32],
+                                  void* d_out, void* d_last);
+int h2agg_permutation_product(h2agg_ctx* ctx, const uint8_t* values, const uint8_t* sigmas, size_t m, unsigned k, size_t u,
+                              const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta[32],
+                              const uint8_t delta_first[32], const uint8_t init[32], uint8_t* out, uint8_t last[32]);
+int h2agg_permutation_product_device(h2agg_ctx* ctx, const void* d_values, const void* d_sigmas, size_t m, unsigned k, size_t u,
+                                     const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta[32],
+                                     const uint8_t delta_first[32], const uint8_t init[32], void* d_out, void* d_last);
+int h2agg_lookup_product(h2agg_ctx* ctx, const uint8_t* a, const uint8_t* s, const uint8_t* ap, const uint8_t* sp, unsigned k,
+                         size_t u, const uint8_t beta[32], const uint8_t gamma[32], uint8_t* out, uint8_t last[32]);
+int h2agg_lookup_product_device(h2agg_ctx* ctx, const void* d_a, const void* d_s, const void* d_ap, const void* d_sp, unsigned k,
+                                size_t u, const uint8_t beta[32], const uint8_t gamma[32], void* d_out, void* d_last);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
@@ -684,6 +740,9 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         1024 elements then run the multi-pass paths
  *       "fr_poly_chunk" t the KZG opening kernels cut a polynomial into chunks of 2^t coefficients per workgroup, 3 .. 11 (0 = the
  *                         default, 11): inputs of 64 to 1024 coefficients then run the three- and four-level plans
+ *       "fr_scan_chunk" t the grand-product kernels (batch inversion, running product) cut an array into chunks of 2^t elements
+ *                         per workgroup, 3 .. 11 (0 = the default, 11): inputs of 64 to 1024 rows then run the three- and
+ *                         four-level plans
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
  *       "seg_chunk" n     h2agg_g1_msm_segmented / h2agg_verify_proofs: at most n points per set of launches of the segmented
  *                         multi_exp (0 = automatic, 16384); a segment longer than that is an ordinary multi_exp of its own
