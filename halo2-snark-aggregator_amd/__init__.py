@@ -21,8 +21,8 @@ OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, 
 OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
 FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
 FR_FFT_MAX_K = 24
-FR_POLY_CHUNK = 11   # log2 of the coefficients per workgroup of the KZG opening kernels by default (csrc/poly_kernels.hpp)
-FR_SCAN_CHUNK = 11   # log2 of the elements per workgroup of the grand-product kernels by default (csrc/prod_kernels.hpp)
+FR_POLY_CHUNK = 11   # log2 of the coefficients per workgroup of the KZG opening kernels by default (csrc/fr_chunk.hpp)
+FR_SCAN_CHUNK = 11   # log2 of the elements per workgroup of the grand-product kernels by default (csrc/fr_chunk.hpp)
 FR_PROD_MAX_COLUMNS = 16
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
@@ -473,6 +473,32 @@ class H2Agg:
         self._check(self._lib.h2agg_bases_fft(self._ctx, handle, k, int(bool(inverse)), C.byref(h)))
         return h.value
 
+    # ------------------------------------------------------------------ Fr prover steps: shared argument handling
+    @staticmethod
+    def _hostptr(data):
+        return C.cast(C.c_char_p(bytes(data)), C.c_void_p)
+
+    def _in_place_or_new(self, data, call):
+        """call(src, dst) -> the library's status.  A bytearray is transformed in place and returned; anything else is read
+        as bytes and gives a new bytes object."""
+        if isinstance(data, bytearray):
+            buf = (C.c_char * len(data)).from_buffer(data)
+            self._check(call(C.addressof(buf), C.addressof(buf)))
+            return data
+        out = C.create_string_buffer(max(len(data), 1))
+        self._check(call(self._hostptr(data), out))
+        return out.raw[:len(data)]
+
+    @staticmethod
+    def _need32(**named):
+        for name, v in named.items():
+            _need(v, 32, name)
+
+    @staticmethod
+    def _z_buffers(u: int):
+        """(out, last) of a synchronous product call: z[0 .. u] and z[u]"""
+        return C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+
     def fr_fft(self, data, k: int, inverse: bool = False, shift: Optional[bytes] = None) -> bytes:
         """the Fourier transform over Fr of 2^k canonical 32-byte elements (h2agg_fr_fft): best_fft, or with inverse=True the
         inverse transform with its 1/n; shift=s transforms s^j * in[j] (forward) / multiplies out[j] by s^-j (inverse).  A
@@ -481,13 +507,8 @@ class H2Agg:
             _need(data, 32 << k, "data")
         if shift is not None:
             _need(shift, 32, "shift")
-        if isinstance(data, bytearray):
-            buf = (C.c_char * len(data)).from_buffer(data)
-            self._check(self._lib.h2agg_fr_fft(self._ctx, C.addressof(buf), k, int(bool(inverse)), shift, C.addressof(buf)))
-            return data
-        out = C.create_string_buffer(len(data))
-        self._check(self._lib.h2agg_fr_fft(self._ctx, C.cast(C.c_char_p(bytes(data)), C.c_void_p), k, int(bool(inverse)), shift, out))
-        return out.raw
+        return self._in_place_or_new(
+            data, lambda src, dst: self._lib.h2agg_fr_fft(self._ctx, src, k, int(bool(inverse)), shift, dst))
 
     def fr_fft_device(self, d_in_ptr: int, k: int, inverse: bool, shift: Optional[bytes], d_out_ptr: int):
         """h2agg_fr_fft_device: 2^k elements in device memory, queued on the context's stream (no synchronisation);
@@ -518,8 +539,7 @@ class H2Agg:
         npoly = self._slab(polys, k)
         qs, nq, npoints = self._queries(queries, points)
         out = C.create_string_buffer(max(32 * nq, 1))
-        self._check(self._lib.h2agg_fr_poly_eval(self._ctx, C.cast(C.c_char_p(bytes(polys)), C.c_void_p), npoly, k, qs, nq,
-                                                 points, npoints, out))
+        self._check(self._lib.h2agg_fr_poly_eval(self._ctx, self._hostptr(polys), npoly, k, qs, nq, points, npoints, out))
         return out.raw[:32 * nq]
 
     def fr_poly_eval_device(self, d_polys_ptr: int, npoly: int, k: int, queries, points: bytes) -> bytes:
@@ -536,13 +556,8 @@ class H2Agg:
             _need(coeffs, 32 << k, "coeffs")
         _need(z, 32, "z")
         rem = C.create_string_buffer(32)
-        if isinstance(coeffs, bytearray):
-            buf = (C.c_char * len(coeffs)).from_buffer(coeffs)
-            self._check(self._lib.h2agg_fr_poly_divide(self._ctx, C.addressof(buf), k, z, C.addressof(buf), rem))
-            return coeffs, rem.raw
-        out = C.create_string_buffer(len(coeffs))
-        self._check(self._lib.h2agg_fr_poly_divide(self._ctx, C.cast(C.c_char_p(bytes(coeffs)), C.c_void_p), k, z, out, rem))
-        return out.raw, rem.raw
+        quot = self._in_place_or_new(coeffs, lambda src, dst: self._lib.h2agg_fr_poly_divide(self._ctx, src, k, z, dst, rem))
+        return quot, rem.raw
 
     def fr_poly_divide_device(self, d_poly_ptr: int, k: int, z: bytes, d_quot_ptr: int, d_rem_ptr: Optional[int] = None):
         """h2agg_fr_poly_divide_device: device memory in and out, queued on the context's stream (no synchronisation);
@@ -562,18 +577,13 @@ class H2Agg:
         """h2agg_kzg_multiopen: the GWC opening of queries [(poly, point), ...] over a host slab [npoly][2^k] -> (the point
         index of every group in first-seen order, the canonical affine W of every group)"""
         npoly = self._slab(polys, k)
-        return self._multiopen(self._lib.h2agg_kzg_multiopen, g_handle, C.cast(C.c_char_p(bytes(polys)), C.c_void_p), npoly, k,
-                               queries, points, v)
+        return self._multiopen(self._lib.h2agg_kzg_multiopen, g_handle, self._hostptr(polys), npoly, k, queries, points, v)
 
     def kzg_multiopen_device(self, g_handle: int, d_polys_ptr: int, npoly: int, k: int, queries, points: bytes, v: bytes):
         """h2agg_kzg_multiopen_device: as kzg_multiopen over a slab already in device memory"""
         return self._multiopen(self._lib.h2agg_kzg_multiopen_device, g_handle, d_polys_ptr, npoly, k, queries, points, v)
 
     # ------------------------------------------------------------------ grand products
-    @staticmethod
-    def _hostptr(data):
-        return C.cast(C.c_char_p(bytes(data)), C.c_void_p)
-
     def _column(self, data, k: int, u: int, what: str, cols: int = 1):
         """a column slab [cols][2^k]; sizes are checked only where the library would go on to read the buffer"""
         if 0 <= k <= FR_FFT_MAX_K and 0 <= u < (1 << k) and 1 <= cols <= FR_PROD_MAX_COLUMNS:
@@ -585,14 +595,7 @@ class H2Agg:
         in place and returned; bytes give a new bytes object."""
         n = len(data) // 32
         _need(data, 32 * n, "data")
-        if isinstance(data, bytearray):
-            if n:
-                buf = (C.c_char * len(data)).from_buffer(data)
-                self._check(self._lib.h2agg_fr_batch_invert(self._ctx, C.addressof(buf), n, C.addressof(buf)))
-            return data
-        out = C.create_string_buffer(max(32 * n, 1))
-        self._check(self._lib.h2agg_fr_batch_invert(self._ctx, self._hostptr(data), n, out))
-        return out.raw[:32 * n]
+        return self._in_place_or_new(data, lambda src, dst: self._lib.h2agg_fr_batch_invert(self._ctx, src, n, dst))
 
     def fr_batch_invert_device(self, d_in_ptr: int, n: int, d_out_ptr: int):
         """h2agg_fr_batch_invert_device: n elements in device memory, queued on the context's stream (no synchronisation);
@@ -606,7 +609,7 @@ class H2Agg:
             _need(num, 32 * u, "num")
             if den is not None:
                 _need(den, 32 * u, "den")
-        out, last = C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+        out, last = self._z_buffers(u)
         self._check(self._lib.h2agg_fr_grand_product(self._ctx, self._hostptr(num), None if den is None else self._hostptr(den),
                                                      k, u, init, out, last))
         return out.raw, last.raw
@@ -621,9 +624,8 @@ class H2Agg:
     def permutation_product(self, values: bytes, sigmas: bytes, m: int, k: int, u: int, beta: bytes, gamma: bytes, delta: bytes,
                             delta_first: bytes, init: bytes):
         """h2agg_permutation_product: one permutation set of m columns (slabs [m][2^k]) -> (z[0 .. u], z[u])"""
-        for name, v in (("beta", beta), ("gamma", gamma), ("delta", delta), ("delta_first", delta_first), ("init", init)):
-            _need(v, 32, name)
-        out, last = C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+        self._need32(beta=beta, gamma=gamma, delta=delta, delta_first=delta_first, init=init)
+        out, last = self._z_buffers(u)
         self._check(self._lib.h2agg_permutation_product(self._ctx, self._column(values, k, u, "values", m),
                                                         self._column(sigmas, k, u, "sigmas", m), m, k, u, beta, gamma, delta,
                                                         delta_first, init, out, last))
@@ -632,16 +634,14 @@ class H2Agg:
     def permutation_product_device(self, d_values_ptr: int, d_sigmas_ptr: int, m: int, k: int, u: int, beta: bytes, gamma: bytes,
                                    delta: bytes, delta_first: bytes, init: bytes, d_out_ptr: int, d_last_ptr: Optional[int] = None):
         """h2agg_permutation_product_device: slabs and z in device memory, queued on the context's stream (no synchronisation)"""
-        for name, v in (("beta", beta), ("gamma", gamma), ("delta", delta), ("delta_first", delta_first), ("init", init)):
-            _need(v, 32, name)
+        self._need32(beta=beta, gamma=gamma, delta=delta, delta_first=delta_first, init=init)
         self._check(self._lib.h2agg_permutation_product_device(self._ctx, d_values_ptr, d_sigmas_ptr, m, k, u, beta, gamma, delta,
                                                                delta_first, init, d_out_ptr, d_last_ptr))
 
     def lookup_product(self, a: bytes, s: bytes, ap: bytes, sp: bytes, k: int, u: int, beta: bytes, gamma: bytes):
         """h2agg_lookup_product: compressed input, table and their permuted forms (2^k rows each) -> (z[0 .. u], z[u])"""
-        _need(beta, 32, "beta")
-        _need(gamma, 32, "gamma")
-        out, last = C.create_string_buffer(32 * (max(u, 0) + 1)), C.create_string_buffer(32)
+        self._need32(beta=beta, gamma=gamma)
+        out, last = self._z_buffers(u)
         cols = [self._column(x, k, u, what) for x, what in ((a, "a"), (s, "s"), (ap, "ap"), (sp, "sp"))]
         self._check(self._lib.h2agg_lookup_product(self._ctx, *cols, k, u, beta, gamma, out, last))
         return out.raw, last.raw
@@ -649,8 +649,7 @@ class H2Agg:
     def lookup_product_device(self, d_a_ptr: int, d_s_ptr: int, d_ap_ptr: int, d_sp_ptr: int, k: int, u: int, beta: bytes,
                               gamma: bytes, d_out_ptr: int, d_last_ptr: Optional[int] = None):
         """h2agg_lookup_product_device: columns and z in device memory, queued on the context's stream (no synchronisation)"""
-        _need(beta, 32, "beta")
-        _need(gamma, 32, "gamma")
+        self._need32(beta=beta, gamma=gamma)
         self._check(self._lib.h2agg_lookup_product_device(self._ctx, d_a_ptr, d_s_ptr, d_ap_ptr, d_sp_ptr, k, u, beta, gamma,
                                                           d_out_ptr, d_last_ptr))
 

@@ -1,25 +1,10 @@
 // Fourier transform over Fr, host side (included into h2agg.hip: shares the context internals; kernels and the pass plan in
-// fr_fft_kernels.hpp): h2agg_fr_fft, h2agg_fr_fft_device.  They stand for halo2_proofs' best_fft and
-// EvaluationDomain::{lagrange_to_coeff, coeff_to_lagrange, coeff_to_extended, extended_to_coeff} — an unvendored git
-// dependency of the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.
+// fr_fft_kernels.hpp, field constants, checks and staging in fr_host.inc): h2agg_fr_fft, h2agg_fr_fft_device.  They stand for
+// halo2_proofs' best_fft and EvaluationDomain::{lagrange_to_coeff, coeff_to_lagrange, coeff_to_extended, extended_to_coeff} —
+// an unvendored git dependency of the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition
+// in include/h2agg.h.
 
 namespace {
-
-// the value 2^261 (the device's Montgomery radix) as a host field element: x * fr_radix() is what the device holds for x
-const ph::HFr& fr_radix() {
-    static const ph::HFr r = [] {
-        ph::HFr x = ph::one();
-        for (int i = 0; i < 29 * NL; ++i) x = ph::add(x, x);
-        return x;
-    }();
-    return r;
-}
-
-void hfr_words(const ph::HFr& a, uint32_t out[8]) {
-    uint8_t b[32];
-    hfr_bytes(a, b);
-    memcpy(out, b, 32);
-}
 
 // d_out[i] = (base^i in the device's Montgomery form), i < n <= 2^12; queued on the context's stream, constants by value
 void fr_powers_launch(h2agg_ctx* c, ph::HFr base, uint32_t n, uint8_t* d_out) {
@@ -48,7 +33,7 @@ void fr_table_launch(h2agg_ctx* c, const ph::HFr& base, unsigned bits, uint8_t* 
 int fr_fft_ensure_twiddles(h2agg_ctx* c, unsigned k, int inv) {
     if (c->frfft_tw_k[inv] >= (int)k) return H2AGG_OK;
     c->frfft_tw_k[inv] = -1;
-    TRY(ensure(c, c->frfft_tw[inv], fr_table_bytes(k)));   // (a replaced buffer: ensure() drains the device first)
+    TRY(fr_ensure(c, c->frfft_tw[inv], fr_table_bytes(k)));   // (a replaced buffer: ensure() drains the device first)
     const ph::HFr w = fft_omega(k);
     fr_table_launch(c, inv ? ph::inv(w) : w, k, (uint8_t*)c->frfft_tw[inv].p);
     c->frfft_tw_k[inv] = (int)k;
@@ -60,10 +45,10 @@ int fr_fft_ensure_twiddles(h2agg_ctx* c, unsigned k, int inv) {
 int fr_fft_queue(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, const ph::HFr* shift, uint8_t* d_out) {
     const unsigned L = c->dbg_fr_fft_local ? (unsigned)c->dbg_fr_fft_local : FR_FFT_LOCAL;
     const unsigned P = k ? (k + L - 1) / L : 1;
-    if (P > 1) TRY(ensure(c, c->frfft_work, (size_t)32 << k));
+    if (P > 1) TRY(fr_ensure(c, c->frfft_work, (size_t)32 << k));
     if (k) TRY(fr_fft_ensure_twiddles(c, k, inv));
     if (shift) {
-        TRY(ensure(c, c->frfft_shift, fr_table_bytes(k)));
+        TRY(fr_ensure(c, c->frfft_shift, fr_table_bytes(k)));
         fr_table_launch(c, inv ? ph::inv(*shift) : *shift, k, (uint8_t*)c->frfft_shift.p);
     }
     FrFftPass p = {};
@@ -112,12 +97,9 @@ int fr_fft_queue(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, const p
 
 // k, shift -> refusals; *has: a shift other than null
 int fr_fft_check(h2agg_ctx* c, unsigned k, const uint8_t* shift, ph::HFr* s) {
-    if (k > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "k must be <= 24");
+    TRY(fr_check_k(c, k));
     if (!shift) return H2AGG_OK;
-    if (!fr_bytes_canonical(shift)) return fail(c, H2AGG_ERR_NONCANONICAL, "input integer >= modulus");
-    uint64_t sw[4];
-    memcpy(sw, shift, 32);
-    *s = ph::from_words(sw);
+    TRY(fr_parse(c, shift, s));
     if (ph::is_zero(*s)) return fail(c, H2AGG_ERR_INVALID, "fr_fft: shift == 0 (the inverse transform divides by shift^j)");
     return H2AGG_OK;
 }
@@ -132,11 +114,7 @@ int h2agg_fr_fft_device(h2agg_ctx* c, const void* d_in, unsigned k, int inverse,
     ph::HFr s;
     TRY(fr_fft_check(c, k, shift, &s));
     return fr_fft_queue(c, (const uint8_t*)d_in, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)d_out);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} FR_API_CATCH
 
 int h2agg_fr_fft(h2agg_ctx* c, const uint8_t* in, unsigned k, int inverse, const uint8_t shift[32], uint8_t* out) try {
     TRY(bind(c));
@@ -144,16 +122,11 @@ int h2agg_fr_fft(h2agg_ctx* c, const uint8_t* in, unsigned k, int inverse, const
     ph::HFr s;
     TRY(fr_fft_check(c, k, shift, &s));
     const size_t bytes = (size_t)32 << k;
-    TRY(ensure(c, c->in_a, bytes));
-    HIP_TRY(c, hipMemcpyAsync(c->in_a.p, in, bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(fr_ensure(c, c->in_a, bytes));
+    TRY(fr_stage_in(c, c->in_a, in, bytes));
     TRY(clear_flags(c));
     TRY(fr_fft_queue(c, (const uint8_t*)c->in_a.p, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)c->in_a.p));
-    HIP_TRY(c, hipMemcpyAsync(out, c->in_a.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    return finish(c);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+    return fr_stage_out(c, out, c->in_a.p, bytes);
+} FR_API_CATCH
 
 }  // extern "C"

@@ -189,11 +189,11 @@ struct h2agg_ctx {
     // KZG openings (csrc/poly_open.inc): the chunk values of every level above the coefficients, the queries / group lists of
     // the call in progress, the combined polynomials (then their quotients) of a multiopen, its Jacobian commitments
     DevBuf poly_work, poly_desc, poly_slab, poly_jac;
-    int dbg_fr_poly_chunk = 0;   // debug key fr_poly_chunk: log2 of the coefficients per workgroup (0 = FR_POLY_CHUNK_LOG)
+    int dbg_fr_poly_chunk = 0;   // debug key fr_poly_chunk: log2 of the coefficients per workgroup (0 = FR_CHUNK_LOG)
     // grand products (csrc/prod.inc): the num and den columns of a permutation / lookup call (den: then R^2 / den, also for
     // h2agg_fr_grand_product), the chunk products of every level above the elements, the two-level table of w^i
     DevBuf prod_num, prod_den, prod_lvl, prod_tab;
-    int dbg_fr_scan_chunk = 0;   // debug key fr_scan_chunk: log2 of the elements per workgroup (0 = FR_PROD_CHUNK_LOG)
+    int dbg_fr_scan_chunk = 0;   // debug key fr_scan_chunk: log2 of the elements per workgroup (0 = FR_CHUNK_LOG)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -2354,11 +2354,11 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         c->dbg_fr_fft_local = value;
     }
     else if (k == "fr_poly_chunk") {                         // KZG openings: log2 of the coefficients per workgroup, 3 .. 11 (0 = the default, 11)
-        if (value != 0 && (value < (int)FR_POLY_PER_LOG || value > (int)FR_POLY_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_poly_chunk must be 0 or 3 .. 11");
+        if (value != 0 && (value < (int)FR_CHUNK_PER_LOG || value > (int)FR_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_poly_chunk must be 0 or 3 .. 11");
         c->dbg_fr_poly_chunk = value;
     }
     else if (k == "fr_scan_chunk") {                         // grand products: log2 of the elements per workgroup, 3 .. 11 (0 = the default, 11)
-        if (value != 0 && (value < (int)FR_PROD_PER_LOG || value > (int)FR_PROD_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_scan_chunk must be 0 or 3 .. 11");
+        if (value != 0 && (value < (int)FR_CHUNK_PER_LOG || value > (int)FR_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_scan_chunk must be 0 or 3 .. 11");
         c->dbg_fr_scan_chunk = value;
     }
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
@@ -2572,6 +2572,7 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "seg_msm.inc"
 #include "comm.inc"
 #include "verifier.inc"
+#include "fr_host.inc"
 #include "params.inc"
 #include "fr_fft.inc"
 #include "poly_open.inc"

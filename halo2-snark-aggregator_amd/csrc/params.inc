@@ -1,4 +1,5 @@
-// KZG parameters, host side (included into h2agg.hip: shares the context internals; kernels in g1_fft_kernels.hpp):
+// KZG parameters, host side (included into h2agg.hip: shares the context internals; kernels in g1_fft_kernels.hpp; fft_omega
+// in fr_host.inc):
 // h2agg_bases_fft, h2agg_params_setup, h2agg_g2_scalar_mul, h2agg_g2_batch_compress.  They stand for halo2_proofs'
 // g_to_lagrange / ParamsKZG::downsize, ParamsKZG::setup and the G2 half of ParamsKZG::write — an unvendored git dependency of
 // the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.
@@ -20,13 +21,6 @@ struct DevTmp {   // a device allocation that lives for one call
 };
 
 constexpr size_t FRP_CST_BYTES = 32 * (FRP_TABLE + 2);
-
-// EvaluationDomain::get_omega: ROOT_OF_UNITY^(2^(S - k))
-ph::HFr fft_omega(unsigned k) {
-    ph::HFr w = ph::from_words(FR_ROOT_OF_UNITY);
-    for (unsigned i = k; i < (unsigned)FR_S; ++i) w = ph::mul(w, w);
-    return w;
-}
 
 // d_out[i] = A * base^i + B, i < n (canonical), queued on the context's stream; d_cst: FRP_CST_BYTES of device memory
 int fr_affine_powers_launch(h2agg_ctx* c, ph::HFr base, const ph::HFr& A, const ph::HFr& B, size_t n, uint8_t* d_cst, uint8_t* d_out) {

@@ -7,8 +7,8 @@
 //   lincomb: c[j] = sum_m v^m p_m[j]
 // n = 2^k coefficients, low degree first, canonical 32-byte little-endian in and out.
 //
-// Plan.  The array is cut into chunks of T = 2^t coefficients (t = FR_POLY_CHUNK_LOG = 11), one workgroup each: 256 threads
-// x FR_POLY_PER = 8 consecutive coefficients (a smaller debug t leaves threads idle).
+// Plan.  The array is cut into chunks of T = 2^t coefficients, one workgroup each, 8 consecutive coefficients per thread
+// (the geometry of fr_chunk.hpp; the levels: fr_level_plan, fr_host.inc).
 //   up-sweep   k_fr_poly_chunk_eval:    E[c] = sum_{i in chunk c} a[i] z^(i - cT).  E is a polynomial in z^T with ceil(n / T)
 //              coefficients, so the same kernel evaluates it: 2^24 -> 2^13 -> 2^2 -> 1.  The top value is a(z).
 //   down-sweep k_fr_poly_chunk_divide:  the carry into chunk c, sum_{i >= (c+1)T} a[i] z^(i - (c+1)T), is quot(E, z^T)[c]: the
@@ -30,18 +30,14 @@
 // it (fr_fft_kernels.hpp has the same rule).  A launch handles the queries whose point is one of its FR_POLY_POINTS; the
 // workgroups of other queries return at once.  The host passes only points that a query names (poly_open.inc).
 #pragma once
-#include "fr_fft_kernels.hpp"
+#include "fr_chunk.hpp"
 
 namespace h2agg {
 
-constexpr unsigned FR_POLY_CHUNK_LOG = 11;   // log2 of the coefficients per workgroup (default)
-constexpr unsigned FR_POLY_PER_LOG = 3;      // log2 of the coefficients per thread
-constexpr unsigned FR_POLY_PER = 1u << FR_POLY_PER_LOG;
-constexpr int FR_POLY_THREADS = 1 << (FR_POLY_CHUNK_LOG - FR_POLY_PER_LOG);   // 256
 constexpr unsigned FR_POLY_POINTS = 8;       // points per launch (their power tables fill 2.8 KiB of kernel arguments)
 
 struct FrPolyPoint {
-    uint32_t pw[FR_POLY_CHUNK_LOG][8];   // (b^(2^j)) R mod r, canonical, j <= min(t, 10); b = z^(T^level)
+    uint32_t pw[FR_CHUNK_LOG][8];   // (b^(2^j)) R mod r, canonical, j <= min(t, 10); b = z^(T^level)
 };
 
 struct FrPolyArgs {
@@ -53,7 +49,7 @@ struct FrPolyArgs {
     uint32_t* flags;
     uint32_t n;             // coefficients per query at this level
     uint32_t chunks;        // ceil(n / T)
-    uint32_t t;             // log2 T, FR_POLY_PER_LOG .. FR_POLY_CHUNK_LOG
+    uint32_t t;             // log2 T, FR_CHUNK_PER_LOG .. FR_CHUNK_LOG
     uint32_t pt0;
     uint32_t level0;        // src is the caller's slab: polynomials by desc, coefficients checked for < r
 };
@@ -70,7 +66,7 @@ FP_INLINE Fr fr_poly_step(const Fr& zM, const Fr& h, const Fr& x) {
 // rolled indexes x[] dynamically, which would put it into scratch memory.
 //   fold: s -> (..(s z + x[E]) z + ..) z + x[0]
 template <int E>
-FP_INLINE void fr_poly_fold(const Fr& zM, const Fr (&x)[FR_POLY_PER], Fr& s) {
+FP_INLINE void fr_poly_fold(const Fr& zM, const Fr (&x)[FR_CHUNK_PER], Fr& s) {
     if constexpr (E >= 0) {
         s = fr_poly_step(zM, s, x[E]);
         fr_poly_fold<E - 1>(zM, x, s);
@@ -78,7 +74,7 @@ FP_INLINE void fr_poly_fold(const Fr& zM, const Fr (&x)[FR_POLY_PER], Fr& s) {
 }
 //   emit: q[i0 + e] = h, h -> z h + x[e], for e = E .. 0; stores only below n.  h < 1.1 -> one fp_cond_sub -> canonical
 template <int E>
-FP_INLINE void fr_poly_emit(const Fr& zM, const Fr (&x)[FR_POLY_PER], Fr& h, uint8_t* dst, uint32_t i0, uint32_t n) {
+FP_INLINE void fr_poly_emit(const Fr& zM, const Fr (&x)[FR_CHUNK_PER], Fr& h, uint8_t* dst, uint32_t i0, uint32_t n) {
     if constexpr (E >= 0) {
         if (i0 + E < n) fp_store<FrParams>(dst + 32 * (size_t)(i0 + E), fp_cond_sub<FrParams>(h));
         if constexpr (E > 0) h = fr_poly_step(zM, h, x[E]);
@@ -98,34 +94,33 @@ FP_INLINE bool fr_poly_locate(const FrPolyArgs& a, uint32_t& q, uint32_t& c, uin
 
 // Up-sweep.  Indices: a thread reads src[poly * n + i] for i in [cT + 8 tid, cT + 8 tid + 8) with i < n only (poly < the
 // slab's polynomial count: checked by the host), LDS entries < T / 8 <= 256, and thread 0 stores dst[q * chunks + c].
-__global__ void __launch_bounds__(FR_POLY_THREADS) k_fr_poly_chunk_eval(const FrPolyArgs a) {
-    __shared__ uint32_t lds[NL * FR_POLY_THREADS];
-    uint32_t q, c, slot;
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_poly_chunk_eval(const FrPolyArgs a) {
+    __shared__ uint32_t lds[NL * FR_CHUNK_THREADS];
+    uint32_t q, chunk, slot;
     const uint8_t* src;
-    if (!fr_poly_locate(a, q, c, slot, src)) return;   // uniform over the workgroup: in front of every barrier
-    const uint32_t nthr = 1u << (a.t - FR_POLY_PER_LOG), tid = threadIdx.x;
-    const uint32_t i0 = (c << a.t) + (tid << FR_POLY_PER_LOG);
+    if (!fr_poly_locate(a, q, chunk, slot, src)) return;   // uniform over the workgroup: in front of every barrier
+    const auto [nthr, tid, c, i0] = fr_chunk(a.t, chunk);
     const Fr zM = fr_poly_pw(a, slot, 0);
     Fr h = Fr::zero();
     if (tid < nthr) {
 #pragma unroll
-        for (int e = FR_POLY_PER - 1; e >= 0; --e) {
+        for (int e = FR_CHUNK_PER - 1; e >= 0; --e) {
             Fr x = Fr::zero();
             if (i0 + e < a.n) {
                 x = fp_load<FrParams>(src + 32 * (size_t)(i0 + e));
                 if (a.level0 && !fp_is_canonical<FrParams>(x)) atomicOr(a.flags, FLAG_NONCANONICAL);
             }
-            h = e == (int)FR_POLY_PER - 1 ? x : fr_poly_step(zM, h, x);
+            h = e == (int)FR_CHUNK_PER - 1 ? x : fr_poly_step(zM, h, x);
         }
     }
     fr_fft_lds_put(lds, tid, h);
     __syncthreads();
     // tree: lo + z^(8 * 2^j) * hi; a level writes only entries it does not read from another thread
 #pragma unroll 1
-    for (uint32_t j = 0; j + FR_POLY_PER_LOG < a.t; ++j) {
+    for (uint32_t j = 0; j + FR_CHUNK_PER_LOG < a.t; ++j) {
         const uint32_t stride = 1u << j;
         if ((tid & (2u * stride - 1u)) == 0 && tid + stride < nthr) {
-            h = fr_poly_step(fr_poly_pw(a, slot, j + FR_POLY_PER_LOG), fr_fft_lds_get(lds, tid + stride), h);
+            h = fr_poly_step(fr_poly_pw(a, slot, j + FR_CHUNK_PER_LOG), fr_fft_lds_get(lds, tid + stride), h);
             fr_fft_lds_put(lds, tid, h);
         }
         __syncthreads();
@@ -137,37 +132,36 @@ __global__ void __launch_bounds__(FR_POLY_THREADS) k_fr_poly_chunk_eval(const Fr
 // coefficients, all of them into registers before its first store — plus one element of `carry`, which is another buffer;
 // and it stores only q[j] for j in its own chunk, every thread at the 8 indices it loaded.  No thread reads what another
 // one writes, in this workgroup or any other.  Index bounds as in k_fr_poly_chunk_eval; stores have j < n.
-__global__ void __launch_bounds__(FR_POLY_THREADS) k_fr_poly_chunk_divide(const FrPolyArgs a) {
-    __shared__ uint32_t lds[NL * FR_POLY_THREADS];
-    uint32_t q, c, slot;
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_poly_chunk_divide(const FrPolyArgs a) {
+    __shared__ uint32_t lds[NL * FR_CHUNK_THREADS];
+    uint32_t q, chunk, slot;
     const uint8_t* src;
-    if (!fr_poly_locate(a, q, c, slot, src)) return;
-    const uint32_t nthr = 1u << (a.t - FR_POLY_PER_LOG), tid = threadIdx.x;
-    const uint32_t i0 = (c << a.t) + (tid << FR_POLY_PER_LOG);
+    if (!fr_poly_locate(a, q, chunk, slot, src)) return;
+    const auto [nthr, tid, c, i0] = fr_chunk(a.t, chunk);
     const Fr zM = fr_poly_pw(a, slot, 0);
     const Fr cin = a.carry ? fp_load<FrParams>(a.carry + 32 * ((size_t)q * a.chunks + c)) : Fr::zero();   // canonical: ours
     const bool active = tid < nthr;
-    Fr x[FR_POLY_PER];
+    Fr x[FR_CHUNK_PER];
 #pragma unroll
-    for (int e = 0; e < (int)FR_POLY_PER; ++e) {
+    for (int e = 0; e < (int)FR_CHUNK_PER; ++e) {
         x[e] = Fr::zero();
         if (active && i0 + e < a.n) x[e] = fp_load<FrParams>(src + 32 * (size_t)(i0 + e));
     }
-    Fr s = x[FR_POLY_PER - 1];   // sum_e x[e] z^e, then the inclusive suffix sum over the threads at and above this one
-    fr_poly_fold<(int)FR_POLY_PER - 2>(zM, x, s);
-    if (tid == nthr - 1) s = fr_poly_step(fr_poly_pw(a, slot, FR_POLY_PER_LOG), cin, s);   // + z^8 * carry-in
+    Fr s = x[FR_CHUNK_PER - 1];   // sum_e x[e] z^e, then the inclusive suffix sum over the threads at and above this one
+    fr_poly_fold<(int)FR_CHUNK_PER - 2>(zM, x, s);
+    if (tid == nthr - 1) s = fr_poly_step(fr_poly_pw(a, slot, FR_CHUNK_PER_LOG), cin, s);   // + z^8 * carry-in
     fr_fft_lds_put(lds, tid, s);
     __syncthreads();
     // suffix scan: s[tid] += z^(8 * 2^j) * s[tid + 2^j]; read, barrier, write, barrier
 #pragma unroll 1
-    for (uint32_t j = 0; j + FR_POLY_PER_LOG < a.t; ++j) {
+    for (uint32_t j = 0; j + FR_CHUNK_PER_LOG < a.t; ++j) {
         const uint32_t stride = 1u << j;
         const bool has = tid + stride < nthr;
         Fr o = Fr::zero();
         if (has) o = fr_fft_lds_get(lds, tid + stride);
         __syncthreads();
         if (has) {
-            s = fr_poly_step(fr_poly_pw(a, slot, j + FR_POLY_PER_LOG), o, s);
+            s = fr_poly_step(fr_poly_pw(a, slot, j + FR_CHUNK_PER_LOG), o, s);
             fr_fft_lds_put(lds, tid, s);
         }
         __syncthreads();
@@ -176,7 +170,7 @@ __global__ void __launch_bounds__(FR_POLY_THREADS) k_fr_poly_chunk_divide(const 
     // what is above this thread's coefficients: the next thread's inclusive sum, or the chunk's carry-in
     Fr h = tid == nthr - 1 ? cin : fr_fft_lds_get(lds, tid + 1);
     uint8_t* dst = a.dst + 32 * (size_t)q * a.n;
-    fr_poly_emit<(int)FR_POLY_PER - 1>(zM, x, h, dst, i0, a.n);
+    fr_poly_emit<(int)FR_CHUNK_PER - 1>(zM, x, h, dst, i0, a.n);
 }
 
 struct FrLincombArgs {

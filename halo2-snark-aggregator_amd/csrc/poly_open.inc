@@ -1,40 +1,21 @@
-// KZG openings, host side (included into h2agg.hip: shares the context internals; kernels, plan and bounds in
-// poly_kernels.hpp): h2agg_fr_poly_eval[_device], h2agg_fr_poly_divide[_device], h2agg_kzg_multiopen[_device].  They stand for
-// halo2_proofs' eval_polynomial, kate_division and the GWC multiopen prover — an unvendored git dependency of the reference,
-// recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.  Which W a verifier
-// accepts is pinned by halo2-snark-aggregator-api/src/systems/halo2/multiopen.rs:23-69.
+// KZG openings, host side (included into h2agg.hip: shares the context internals; kernels and bounds in poly_kernels.hpp,
+// level plan, checks and staging in fr_host.inc, power tables in fr_fft.inc): h2agg_fr_poly_eval[_device],
+// h2agg_fr_poly_divide[_device], h2agg_kzg_multiopen[_device].  They stand for halo2_proofs' eval_polynomial, kate_division and
+// the GWC multiopen prover — an unvendored git dependency of the reference, recalled from upstream (DESIGN.md section 2); the
+// yardstick is the definition in include/h2agg.h.  Which W a verifier accepts is pinned by
+// halo2-snark-aggregator-api/src/systems/halo2/multiopen.rs:23-69.
 
 namespace {
 
 constexpr size_t POLY_MAX_QUERIES = 65535;   // a grid dimension of the linear combination; chunks * queries stays < 2^31
 
-// the levels of one call: cnt[0] = 2^k coefficients per query, cnt[l + 1] = ceil(cnt[l] / T), down to 1.  Level l >= 1 is
-// [query][cnt[l]] elements at off[l] of the context's work buffer; the top level is the nq values a(z).
-struct PolyPlan {
-    unsigned t = 0;
-    size_t nq = 0;
-    std::vector<uint32_t> cnt;
-    std::vector<size_t> off;
-    size_t total = 0;
-    size_t launches() const { return cnt.size() - 1; }
-};
-
-PolyPlan poly_plan(const h2agg_ctx* c, unsigned k, size_t nq) {
-    PolyPlan p;
-    p.t = c->dbg_fr_poly_chunk ? (unsigned)c->dbg_fr_poly_chunk : FR_POLY_CHUNK_LOG;
-    p.nq = nq;
-    p.cnt.push_back(1u << k);
-    p.off.push_back(0);
-    do {
-        p.cnt.push_back((p.cnt.back() + (1u << p.t) - 1u) >> p.t);
-        p.off.push_back(p.total);
-        p.total += nq * p.cnt.back();
-    } while (p.cnt.back() > 1);
-    return p;
+// the levels of one call: 2^k coefficients per query; the top level is the nq values a(z)
+FrLevelPlan poly_plan(const h2agg_ctx* c, unsigned k, size_t nq) {
+    return fr_level_plan(c->dbg_fr_poly_chunk ? (unsigned)c->dbg_fr_poly_chunk : FR_CHUNK_LOG, (size_t)1 << k, nq);
 }
 
 // tab[l][p]: the powers (z_p^(T^l))^(2^j), j < t (and j = t where the table has room), as the device's Montgomery form
-void poly_point_tables(const std::vector<ph::HFr>& pts, const PolyPlan& plan, std::vector<std::vector<FrPolyPoint>>& tab) {
+void poly_point_tables(const std::vector<ph::HFr>& pts, const FrLevelPlan& plan, std::vector<std::vector<FrPolyPoint>>& tab) {
     tab.assign(plan.launches(), std::vector<FrPolyPoint>(pts.size()));
     for (size_t p = 0; p < pts.size(); ++p) {
         ph::HFr b = pts[p];
@@ -45,25 +26,9 @@ void poly_point_tables(const std::vector<ph::HFr>& pts, const PolyPlan& plan, st
                 b = ph::mul(b, b);
             }
             // (the carry fold reads z^8 = pw[3]: at t = 3 that is the next level's base)
-            if (plan.t < FR_POLY_CHUNK_LOG) hfr_words(ph::mul(b, fr_radix()), tab[l][p].pw[plan.t]);
+            if (plan.t < FR_CHUNK_LOG) hfr_words(ph::mul(b, fr_radix()), tab[l][p].pw[plan.t]);
         }
     }
-}
-
-// ensure(); a failed allocation also leaves HIP's last-error slot set, which the hipGetLastError() behind the next launches
-// would report as that call's failure: taken out here, so that the context stays usable after H2AGG_ERR_NOMEM
-int poly_ensure(h2agg_ctx* c, DevBuf& b, size_t bytes) {
-    const int rc = ensure(c, b, bytes);
-    if (rc == H2AGG_ERR_NOMEM) (void)hipGetLastError();
-    return rc;
-}
-
-int poly_parse_fr(h2agg_ctx* c, const uint8_t* b, ph::HFr* out) {
-    if (!fr_bytes_canonical(b)) return fail(c, H2AGG_ERR_NONCANONICAL, "input integer >= modulus");
-    uint64_t w[4];
-    memcpy(w, b, 32);
-    *out = ph::from_words(w);
-    return H2AGG_OK;
 }
 
 // one level of either sweep: a launch per FR_POLY_POINTS points of `pts`, every launch over all queries.  `pts` holds only
@@ -74,13 +39,13 @@ void poly_level_launch(h2agg_ctx* c, Kernel kernel, FrPolyArgs& a, const std::ve
         memset(a.pt, 0, sizeof(a.pt));
         for (size_t s = 0; s < FR_POLY_POINTS && p0 + s < pts.size(); ++s) a.pt[s] = pts[p0 + s];
         a.pt0 = (uint32_t)p0;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(nq * a.chunks)), dim3(FR_POLY_THREADS), 0, c->stream, a);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(nq * a.chunks)), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
     }
 }
 
 // Queues the up-sweep: the values a_q(z_q) end up at poly_top(c, plan).  d_desc: null (query q = polynomial q of the slab at
 // point q) or nq x {polynomial, point} in device memory.
-void poly_eval_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc, const PolyPlan& plan,
+void poly_eval_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc, const FrLevelPlan& plan,
                      const std::vector<std::vector<FrPolyPoint>>& tab) {
     uint8_t* work = (uint8_t*)c->poly_work.p;
     for (size_t l = 0; l < plan.launches(); ++l) {
@@ -97,11 +62,11 @@ void poly_eval_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc
         poly_level_launch(c, k_fr_poly_chunk_eval, a, tab[l], plan.nq);
     }
 }
-const uint8_t* poly_top(const h2agg_ctx* c, const PolyPlan& plan) { return (const uint8_t*)c->poly_work.p + 32 * plan.off.back(); }
+const uint8_t* poly_top(const h2agg_ctx* c, const FrLevelPlan& plan) { return (const uint8_t*)c->poly_work.p + 32 * plan.off.back(); }
 
 // Queues the down-sweep behind poly_eval_queue of the same plan: the quotients go to d_quot, [query][2^k] (d_quot == d_slab
 // allowed when query q is polynomial q: poly_kernels.hpp says why).  The levels above the coefficients are divided in place.
-void poly_divide_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc, const PolyPlan& plan,
+void poly_divide_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc, const FrLevelPlan& plan,
                        const std::vector<std::vector<FrPolyPoint>>& tab, uint8_t* d_quot) {
     uint8_t* work = (uint8_t*)c->poly_work.p;
     for (size_t l = plan.launches(); l-- > 0;) {
@@ -122,7 +87,7 @@ void poly_divide_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_de
 // what every entry point with a query list refuses; on success the points as field elements
 int poly_check_queries(h2agg_ctx* c, unsigned k, size_t npoly, const uint32_t* queries, size_t nq, const uint8_t* points,
                        size_t npoints, std::vector<ph::HFr>* pts) {
-    if (k > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "k must be <= 24");
+    TRY(fr_check_k(c, k));
     if (!queries || !points) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     if (nq == 0) return fail(c, H2AGG_ERR_INVALID, "no queries");
     if (nq > POLY_MAX_QUERIES) return fail(c, H2AGG_ERR_INVALID, "more than 65535 queries in one call");
@@ -132,7 +97,7 @@ int poly_check_queries(h2agg_ctx* c, unsigned k, size_t npoly, const uint32_t* q
         if (queries[2 * q + 1] >= npoints) return fail(c, H2AGG_ERR_INVALID, "query names a point index >= npoints");
     }
     pts->resize(npoints);
-    for (size_t p = 0; p < npoints; ++p) TRY(poly_parse_fr(c, points + 32 * p, &(*pts)[p]));
+    for (size_t p = 0; p < npoints; ++p) TRY(fr_parse(c, points + 32 * p, &(*pts)[p]));
     return H2AGG_OK;
 }
 
@@ -151,24 +116,23 @@ int poly_eval_run(h2agg_ctx* c, const uint8_t* d_polys, unsigned k, const uint32
         }
         desc[2 * q + 1] = (uint32_t)r;
     }
-    const PolyPlan plan = poly_plan(c, k, nq);
+    const FrLevelPlan plan = poly_plan(c, k, nq);
     std::vector<std::vector<FrPolyPoint>> tab;
     poly_point_tables(named, plan, tab);
-    TRY(poly_ensure(c, c->poly_work, 32 * plan.total));
-    TRY(poly_ensure(c, c->poly_desc, 8 * nq));
+    TRY(fr_ensure(c, c->poly_work, 32 * plan.total));
+    TRY(fr_ensure(c, c->poly_desc, 8 * nq));
     HIP_TRY(c, hipMemcpyAsync(c->poly_desc.p, desc.data(), 8 * nq, hipMemcpyHostToDevice, c->stream));
     poly_eval_queue(c, d_polys, (const uint32_t*)c->poly_desc.p, plan, tab);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, poly_top(c, plan), 32 * nq, hipMemcpyDeviceToHost, c->stream));
-    return finish(c);
+    return fr_stage_out(c, out, poly_top(c, plan), 32 * nq);
 }
 
 // up-sweep, down-sweep and the remainder of ONE polynomial; nothing synchronises unless the work buffer has to grow
 int poly_divide_queue_one(h2agg_ctx* c, const uint8_t* d_poly, unsigned k, const ph::HFr& z, uint8_t* d_quot, uint8_t* d_rem) {
-    const PolyPlan plan = poly_plan(c, k, 1);
+    const FrLevelPlan plan = poly_plan(c, k, 1);
     std::vector<std::vector<FrPolyPoint>> tab;
     poly_point_tables(std::vector<ph::HFr>(1, z), plan, tab);
-    TRY(poly_ensure(c, c->poly_work, 32 * plan.total));
+    TRY(fr_ensure(c, c->poly_work, 32 * plan.total));
     poly_eval_queue(c, d_poly, nullptr, plan, tab);
     poly_divide_queue(c, d_poly, nullptr, plan, tab, d_quot);
     HIP_TRY(c, hipGetLastError());
@@ -177,9 +141,9 @@ int poly_divide_queue_one(h2agg_ctx* c, const uint8_t* d_poly, unsigned k, const
 }
 
 int poly_divide_check(h2agg_ctx* c, unsigned k, const uint8_t* z, ph::HFr* zf) {
-    if (k > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "k must be <= 24");
+    TRY(fr_check_k(c, k));
     if (!z) return fail(c, H2AGG_ERR_INVALID, "null buffer");
-    return poly_parse_fr(c, z, zf);
+    return fr_parse(c, z, zf);
 }
 
 // debug key phases: events on the context's stream around the three phases of one multiopen, for h2agg_last_phases
@@ -243,13 +207,13 @@ int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsig
         gz[g] = pts[gpoint[g]];
     }
     lists.insert(lists.end(), goff.begin(), goff.end());
-    const PolyPlan plan = poly_plan(c, k, groups);
+    const FrLevelPlan plan = poly_plan(c, k, groups);
     std::vector<std::vector<FrPolyPoint>> tab;
     poly_point_tables(gz, plan, tab);
-    TRY(poly_ensure(c, c->poly_work, 32 * plan.total));
-    TRY(poly_ensure(c, c->poly_desc, 4 * lists.size()));
-    TRY(poly_ensure(c, c->poly_slab, 32 * n * groups));
-    TRY(poly_ensure(c, c->poly_jac, 96 * groups));
+    TRY(fr_ensure(c, c->poly_work, 32 * plan.total));
+    TRY(fr_ensure(c, c->poly_desc, 4 * lists.size()));
+    TRY(fr_ensure(c, c->poly_slab, 32 * n * groups));
+    TRY(fr_ensure(c, c->poly_jac, 96 * groups));
     HIP_TRY(c, hipMemcpyAsync(c->poly_desc.p, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, c->stream));
     PolyPhases phases(c->dbg_phases != 0);
     phases.mark(c, 0);
@@ -282,7 +246,7 @@ int multiopen_check(h2agg_ctx* c, uint64_t g_handle, unsigned k, size_t npoly, c
                     const void* ngroups, std::vector<ph::HFr>* pts, ph::HFr* vf) {
     if (!v || !w_aff || !group_points || !ngroups) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     TRY(poly_check_queries(c, k, npoly, queries, nq, points, npoints, pts));
-    TRY(poly_parse_fr(c, v, vf));
+    TRY(fr_parse(c, v, vf));
     auto it = c->tables.find(g_handle);
     if (it == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown base-table handle");
     if (it->second.n < ((size_t)1 << k)) return fail(c, H2AGG_ERR_INVALID, "the base table is shorter than 2^k");
@@ -301,11 +265,7 @@ int h2agg_fr_poly_eval_device(h2agg_ctx* c, const void* d_polys, size_t npoly, u
     TRY(poly_check_queries(c, k, npoly, queries, nq, points, npoints, &pts));
     TRY(clear_flags(c));
     return poly_eval_run(c, (const uint8_t*)d_polys, k, queries, nq, pts, out);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} FR_API_CATCH
 
 int h2agg_fr_poly_eval(h2agg_ctx* c, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries, size_t nq,
                        const uint8_t* points, size_t npoints, uint8_t* out) try {
@@ -314,15 +274,11 @@ int h2agg_fr_poly_eval(h2agg_ctx* c, const uint8_t* polys, size_t npoly, unsigne
     std::vector<ph::HFr> pts;
     TRY(poly_check_queries(c, k, npoly, queries, nq, points, npoints, &pts));
     const size_t bytes = ((size_t)32 << k) * npoly;
-    TRY(poly_ensure(c, c->in_a, bytes));
-    HIP_TRY(c, hipMemcpyAsync(c->in_a.p, polys, bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(fr_ensure(c, c->in_a, bytes));
+    TRY(fr_stage_in(c, c->in_a, polys, bytes));
     TRY(clear_flags(c));
     return poly_eval_run(c, (const uint8_t*)c->in_a.p, k, queries, nq, pts, out);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} FR_API_CATCH
 
 int h2agg_fr_poly_divide_device(h2agg_ctx* c, const void* d_poly, unsigned k, const uint8_t z[32], void* d_quot, void* d_rem) try {
     TRY(bind(c));
@@ -330,11 +286,7 @@ int h2agg_fr_poly_divide_device(h2agg_ctx* c, const void* d_poly, unsigned k, co
     ph::HFr zf;
     TRY(poly_divide_check(c, k, z, &zf));
     return poly_divide_queue_one(c, (const uint8_t*)d_poly, k, zf, (uint8_t*)d_quot, (uint8_t*)d_rem);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} FR_API_CATCH
 
 int h2agg_fr_poly_divide(h2agg_ctx* c, const uint8_t* in, unsigned k, const uint8_t z[32], uint8_t* out, uint8_t rem[32]) try {
     TRY(bind(c));
@@ -342,19 +294,14 @@ int h2agg_fr_poly_divide(h2agg_ctx* c, const uint8_t* in, unsigned k, const uint
     ph::HFr zf;
     TRY(poly_divide_check(c, k, z, &zf));
     const size_t bytes = (size_t)32 << k;
-    TRY(poly_ensure(c, c->in_a, bytes + 32));
+    TRY(fr_ensure(c, c->in_a, bytes + 32));
     uint8_t* d = (uint8_t*)c->in_a.p;
-    HIP_TRY(c, hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(fr_stage_in(c, c->in_a, in, bytes));
     TRY(clear_flags(c));
     TRY(poly_divide_queue_one(c, d, k, zf, d, d + bytes));
     HIP_TRY(c, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(rem, d + bytes, 32, hipMemcpyDeviceToHost, c->stream));
-    return finish(c);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+    return fr_stage_out(c, rem, d + bytes, 32);
+} FR_API_CATCH
 
 int h2agg_kzg_multiopen_device(h2agg_ctx* c, uint64_t g_handle, const void* d_polys, size_t npoly, unsigned k,
                                const uint32_t* queries, size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32],
@@ -366,11 +313,7 @@ int h2agg_kzg_multiopen_device(h2agg_ctx* c, uint64_t g_handle, const void* d_po
     TRY(multiopen_check(c, g_handle, k, npoly, queries, nq, points, npoints, v, w_aff, group_points, ngroups, &pts, &vf));
     TRY(clear_flags(c));
     return multiopen_run(c, g_handle, (const uint8_t*)d_polys, k, queries, nq, pts, vf, w_aff, group_points, ngroups);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} FR_API_CATCH
 
 int h2agg_kzg_multiopen(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries,
                         size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32], uint8_t* w_aff,
@@ -381,14 +324,10 @@ int h2agg_kzg_multiopen(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, s
     ph::HFr vf;
     TRY(multiopen_check(c, g_handle, k, npoly, queries, nq, points, npoints, v, w_aff, group_points, ngroups, &pts, &vf));
     const size_t bytes = ((size_t)32 << k) * npoly;
-    TRY(poly_ensure(c, c->in_a, bytes));
-    HIP_TRY(c, hipMemcpyAsync(c->in_a.p, polys, bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(fr_ensure(c, c->in_a, bytes));
+    TRY(fr_stage_in(c, c->in_a, polys, bytes));
     TRY(clear_flags(c));
     return multiopen_run(c, g_handle, (const uint8_t*)c->in_a.p, k, queries, nq, pts, vf, w_aff, group_points, ngroups);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} FR_API_CATCH
 
 }  // extern "C"

@@ -1,42 +1,25 @@
-// Grand products, host side (included into h2agg.hip: shares the context internals; kernels, plan and bounds in
-// prod_kernels.hpp): h2agg_fr_batch_invert[_device], h2agg_fr_grand_product[_device], h2agg_permutation_product[_device],
-// h2agg_lookup_product[_device].  They stand for halo2_proofs' ff::BatchInvert, permutation::prover::commit and
-// lookup::prover::commit_product — an unvendored git dependency of the reference, recalled from upstream (DESIGN.md section
-// 2); the yardstick is the definition in include/h2agg.h.  Which Z a verifier accepts is pinned by
-// halo2-snark-aggregator-api/src/systems/halo2/permutation.rs:70-133 and lookup.rs:98-113.
+// Grand products, host side (included into h2agg.hip: shares the context internals; kernels and bounds in prod_kernels.hpp,
+// level plan, checks and staging in fr_host.inc, power tables in fr_fft.inc): h2agg_fr_batch_invert[_device],
+// h2agg_fr_grand_product[_device], h2agg_permutation_product[_device], h2agg_lookup_product[_device].  They stand for
+// halo2_proofs' ff::BatchInvert, permutation::prover::commit and lookup::prover::commit_product — an unvendored git dependency
+// of the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.  Which
+// Z a verifier accepts is pinned by halo2-snark-aggregator-api/src/systems/halo2/permutation.rs:70-133 and lookup.rs:98-113.
 
 namespace {
 
 constexpr size_t PROD_MAX_N = (size_t)1 << FFT_MAX_K;
 
-// the levels of one sweep pair: cnt[0] elements, cnt[l + 1] = ceil(cnt[l] / T), down to 1.  Level l >= 1 is cnt[l] elements
-// at off[l] of the context's level buffer.  (The last level, one element, is never stored: the top chunk keeps its root.)
-struct ProdPlan {
-    unsigned t = 0;
-    std::vector<uint32_t> cnt;
-    std::vector<size_t> off;
-    size_t total = 0;
-    size_t launches() const { return cnt.size() - 1; }
-};
-
-ProdPlan prod_plan(const h2agg_ctx* c, size_t n) {
-    ProdPlan p;
-    p.t = c->dbg_fr_scan_chunk ? (unsigned)c->dbg_fr_scan_chunk : FR_PROD_CHUNK_LOG;
-    p.cnt.push_back((uint32_t)n);
-    p.off.push_back(0);
-    do {
-        p.cnt.push_back((p.cnt.back() + (1u << p.t) - 1u) >> p.t);
-        p.off.push_back(p.total);
-        p.total += p.cnt.back();
-    } while (p.cnt.back() > 1);
-    return p;
+// the levels of one sweep pair over n elements, in the context's level buffer.  (The last level, one element, is never stored:
+// the top chunk keeps its root.)
+FrLevelPlan prod_plan(const h2agg_ctx* c, size_t n) {
+    return fr_level_plan(c->dbg_fr_scan_chunk ? (unsigned)c->dbg_fr_scan_chunk : FR_CHUNK_LOG, n, 1);
 }
 
 // Queues both sweeps of `op` over n >= 1 elements (scan: n = u + 1 positions): up-sweeps of the levels below the top one, then
 // the down-sweeps from the top.  The level buffer must hold prod_plan(c, n).total elements.
 void prod_sweeps_queue(h2agg_ctx* c, uint32_t op, const uint8_t* d_src, const uint8_t* d_aux, size_t n, const ph::HFr& top,
                        bool check, uint8_t* d_dst) {
-    const ProdPlan plan = prod_plan(c, n);
+    const FrLevelPlan plan = prod_plan(c, n);
     uint8_t* lvl = (uint8_t*)c->prod_lvl.p;
     const size_t L = plan.launches();
     FrProdArgs a;
@@ -52,7 +35,7 @@ void prod_sweeps_queue(h2agg_ctx* c, uint32_t op, const uint8_t* d_src, const ui
         a.carry = nullptr;
         a.n = plan.cnt[l];
         a.level0 = l == 0;
-        hipLaunchKernelGGL(k_fr_prod_chunk, dim3(plan.cnt[l + 1]), dim3(FR_PROD_THREADS), 0, c->stream, a);
+        hipLaunchKernelGGL(k_fr_prod_chunk, dim3(plan.cnt[l + 1]), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
     }
     for (size_t l = L; l-- > 0;) {
         a.src = l == 0 ? d_src : lvl + 32 * plan.off[l];
@@ -61,13 +44,13 @@ void prod_sweeps_queue(h2agg_ctx* c, uint32_t op, const uint8_t* d_src, const ui
         a.n = plan.cnt[l];
         a.level0 = l == 0;
         if (op == FR_PROD_INVERT)
-            hipLaunchKernelGGL(k_fr_prod_invert, dim3(plan.cnt[l + 1]), dim3(FR_PROD_THREADS), 0, c->stream, a);
+            hipLaunchKernelGGL(k_fr_prod_invert, dim3(plan.cnt[l + 1]), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
         else
-            hipLaunchKernelGGL(k_fr_prod_scan, dim3(plan.cnt[l + 1]), dim3(FR_PROD_THREADS), 0, c->stream, a);
+            hipLaunchKernelGGL(k_fr_prod_scan, dim3(plan.cnt[l + 1]), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
     }
 }
 
-int prod_ensure_levels(h2agg_ctx* c, size_t n) { return poly_ensure(c, c->prod_lvl, 32 * prod_plan(c, n).total); }
+int prod_ensure_levels(h2agg_ctx* c, size_t n) { return fr_ensure(c, c->prod_lvl, 32 * prod_plan(c, n).total); }
 
 // out[i] = 1 / in[i] (montgomery2 = false) or R^2 / in[i] (true: what the scan multiplies num with), 0 for 0; n >= 1
 int prod_invert_queue(h2agg_ctx* c, const uint8_t* d_in, size_t n, bool montgomery2, bool check, uint8_t* d_out) {
@@ -85,7 +68,7 @@ int prod_grand_queue(h2agg_ctx* c, const uint8_t* d_num, const uint8_t* d_den, s
     if (d_den && u) {
         uint8_t* inv = (uint8_t*)c->prod_den.p;
         if (d_den != inv) {
-            TRY(poly_ensure(c, c->prod_den, 32 * u));
+            TRY(fr_ensure(c, c->prod_den, 32 * u));
             inv = (uint8_t*)c->prod_den.p;
         }
         TRY(prod_invert_queue(c, d_den, u, true, check, inv));
@@ -99,7 +82,7 @@ int prod_grand_queue(h2agg_ctx* c, const uint8_t* d_num, const uint8_t* d_den, s
 }
 
 int prod_check_ku(h2agg_ctx* c, unsigned k, size_t u) {
-    if (k > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "k must be <= 24");
+    TRY(fr_check_k(c, k));
     if (u >= ((size_t)1 << k)) return fail(c, H2AGG_ERR_INVALID, "u must be < 2^k");
     return H2AGG_OK;
 }
@@ -113,20 +96,20 @@ int perm_check(h2agg_ctx* c, size_t m, unsigned k, size_t u, const uint8_t* beta
     TRY(prod_check_ku(c, k, u));
     if (m == 0 || m > FR_PROD_MAX_COLUMNS) return fail(c, H2AGG_ERR_INVALID, "m must be 1 .. 16");
     if (!beta || !gamma || !delta || !delta_first || !init) return fail(c, H2AGG_ERR_INVALID, "null buffer");
-    TRY(poly_parse_fr(c, beta, &pc->beta));
-    TRY(poly_parse_fr(c, gamma, &pc->gamma));
-    TRY(poly_parse_fr(c, delta, &pc->delta));
-    TRY(poly_parse_fr(c, delta_first, &pc->delta_first));
-    return poly_parse_fr(c, init, &pc->init);
+    TRY(fr_parse(c, beta, &pc->beta));
+    TRY(fr_parse(c, gamma, &pc->gamma));
+    TRY(fr_parse(c, delta, &pc->delta));
+    TRY(fr_parse(c, delta_first, &pc->delta_first));
+    return fr_parse(c, init, &pc->init);
 }
 
 // the term kernel into the context's num / den columns, then the grand product of the two
 int perm_queue(h2agg_ctx* c, const uint8_t* d_values, const uint8_t* d_sigmas, size_t m, unsigned k, size_t u, const PermConsts& pc,
                uint8_t* d_out, uint8_t* d_last) {
     if (u) {
-        TRY(poly_ensure(c, c->prod_num, 32 * u));
-        TRY(poly_ensure(c, c->prod_den, 32 * u));
-        TRY(poly_ensure(c, c->prod_tab, fr_table_bytes(k)));
+        TRY(fr_ensure(c, c->prod_num, 32 * u));
+        TRY(fr_ensure(c, c->prod_den, 32 * u));
+        TRY(fr_ensure(c, c->prod_tab, fr_table_bytes(k)));
         fr_table_launch(c, fft_omega(k), k, (uint8_t*)c->prod_tab.p);
         FrPermArgs a;
         hfr_words(ph::mul(pc.beta, fr_radix()), a.beta);
@@ -158,15 +141,15 @@ int perm_queue(h2agg_ctx* c, const uint8_t* d_values, const uint8_t* d_sigmas, s
 int lookup_check(h2agg_ctx* c, unsigned k, size_t u, const uint8_t* beta, const uint8_t* gamma, ph::HFr* bf, ph::HFr* gf) {
     TRY(prod_check_ku(c, k, u));
     if (!beta || !gamma) return fail(c, H2AGG_ERR_INVALID, "null buffer");
-    TRY(poly_parse_fr(c, beta, bf));
-    return poly_parse_fr(c, gamma, gf);
+    TRY(fr_parse(c, beta, bf));
+    return fr_parse(c, gamma, gf);
 }
 
 int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uint8_t* d_ap, const uint8_t* d_sp, size_t u,
                  const ph::HFr& beta, const ph::HFr& gamma, uint8_t* d_out, uint8_t* d_last) {
     if (u) {
-        TRY(poly_ensure(c, c->prod_num, 32 * u));
-        TRY(poly_ensure(c, c->prod_den, 32 * u));
+        TRY(fr_ensure(c, c->prod_num, 32 * u));
+        TRY(fr_ensure(c, c->prod_den, 32 * u));
         FrLookupArgs a;
         hfr_words(beta, a.beta);
         hfr_words(gamma, a.gamma);
@@ -183,25 +166,14 @@ int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uin
     return prod_grand_queue(c, (const uint8_t*)c->prod_num.p, (const uint8_t*)c->prod_den.p, u, ph::one(), false, d_out, d_last);
 }
 
-// host buffers of a synchronous product call: upload `bytes` of `src` into `b`
-int prod_upload(h2agg_ctx* c, DevBuf& b, const uint8_t* src, size_t bytes, size_t at = 0) {
-    if (bytes) HIP_TRY(c, hipMemcpyAsync((uint8_t*)b.p + at, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return H2AGG_OK;
-}
-
 // the tail of every synchronous product call: out[0 .. u] and `last` back to the host
 int prod_download(h2agg_ctx* c, size_t u, uint8_t* out, uint8_t* last) {
-    HIP_TRY(c, hipMemcpyAsync(out, c->out.p, 32 * (u + 1), hipMemcpyDeviceToHost, c->stream));
-    TRY(finish(c));
+    TRY(fr_stage_out(c, out, c->out.p, 32 * (u + 1)));
     if (last) memcpy(last, out + 32 * u, 32);
     return H2AGG_OK;
 }
 
 }  // namespace
-
-#define PROD_CATCH                                                        \
-    catch (const std::bad_alloc&) { return H2AGG_ERR_NOMEM; /* no C++ exception crosses the C ABI */ } \
-    catch (...) { return H2AGG_ERR_INVALID; }
 
 extern "C" {
 
@@ -211,20 +183,19 @@ int h2agg_fr_batch_invert_device(h2agg_ctx* c, const void* d_in, size_t n, void*
     if (n == 0) return H2AGG_OK;
     if (!d_in || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return prod_invert_queue(c, (const uint8_t*)d_in, n, false, true, (uint8_t*)d_out);
-} PROD_CATCH
+} FR_API_CATCH
 
 int h2agg_fr_batch_invert(h2agg_ctx* c, const uint8_t* in, size_t n, uint8_t* out) try {
     TRY(bind(c));
     if (n > PROD_MAX_N) return fail(c, H2AGG_ERR_INVALID, "n must be <= 2^24");
     if (n == 0) return H2AGG_OK;
     if (!in || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
-    TRY(poly_ensure(c, c->in_a, 32 * n));
-    TRY(prod_upload(c, c->in_a, in, 32 * n));
+    TRY(fr_ensure(c, c->in_a, 32 * n));
+    TRY(fr_stage_in(c, c->in_a, in, 32 * n));
     TRY(clear_flags(c));
     TRY(prod_invert_queue(c, (const uint8_t*)c->in_a.p, n, false, true, (uint8_t*)c->in_a.p));
-    HIP_TRY(c, hipMemcpyAsync(out, c->in_a.p, 32 * n, hipMemcpyDeviceToHost, c->stream));
-    return finish(c);
-} PROD_CATCH
+    return fr_stage_out(c, out, c->in_a.p, 32 * n);
+} FR_API_CATCH
 
 int h2agg_fr_grand_product_device(h2agg_ctx* c, const void* d_num, const void* d_den, unsigned k, size_t u, const uint8_t init[32],
                                   void* d_out, void* d_last) try {
@@ -232,9 +203,9 @@ int h2agg_fr_grand_product_device(h2agg_ctx* c, const void* d_num, const void* d
     TRY(prod_check_ku(c, k, u));
     if (!d_num || !d_out || !init) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     ph::HFr initf;
-    TRY(poly_parse_fr(c, init, &initf));
+    TRY(fr_parse(c, init, &initf));
     return prod_grand_queue(c, (const uint8_t*)d_num, (const uint8_t*)d_den, u, initf, true, (uint8_t*)d_out, (uint8_t*)d_last);
-} PROD_CATCH
+} FR_API_CATCH
 
 int h2agg_fr_grand_product(h2agg_ctx* c, const uint8_t* num, const uint8_t* den, unsigned k, size_t u, const uint8_t init[32],
                            uint8_t* out, uint8_t last[32]) try {
@@ -242,17 +213,17 @@ int h2agg_fr_grand_product(h2agg_ctx* c, const uint8_t* num, const uint8_t* den,
     TRY(prod_check_ku(c, k, u));
     if (!num || !out || !init) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     ph::HFr initf;
-    TRY(poly_parse_fr(c, init, &initf));
-    TRY(poly_ensure(c, c->in_a, 32 * u + 32));
-    TRY(poly_ensure(c, c->in_b, 32 * u + 32));
-    TRY(poly_ensure(c, c->out, 32 * (u + 1)));
-    TRY(prod_upload(c, c->in_a, num, 32 * u));
-    if (den) TRY(prod_upload(c, c->in_b, den, 32 * u));
+    TRY(fr_parse(c, init, &initf));
+    TRY(fr_ensure(c, c->in_a, 32 * u + 32));
+    TRY(fr_ensure(c, c->in_b, 32 * u + 32));
+    TRY(fr_ensure(c, c->out, 32 * (u + 1)));
+    TRY(fr_stage_in(c, c->in_a, num, 32 * u));
+    if (den) TRY(fr_stage_in(c, c->in_b, den, 32 * u));
     TRY(clear_flags(c));
     TRY(prod_grand_queue(c, (const uint8_t*)c->in_a.p, den ? (const uint8_t*)c->in_b.p : nullptr, u, initf, true,
                          (uint8_t*)c->out.p, nullptr));
     return prod_download(c, u, out, last);
-} PROD_CATCH
+} FR_API_CATCH
 
 int h2agg_permutation_product_device(h2agg_ctx* c, const void* d_values, const void* d_sigmas, size_t m, unsigned k, size_t u,
                                      const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta[32],
@@ -262,7 +233,7 @@ int h2agg_permutation_product_device(h2agg_ctx* c, const void* d_values, const v
     TRY(perm_check(c, m, k, u, beta, gamma, delta, delta_first, init, &pc));
     if (!d_values || !d_sigmas || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return perm_queue(c, (const uint8_t*)d_values, (const uint8_t*)d_sigmas, m, k, u, pc, (uint8_t*)d_out, (uint8_t*)d_last);
-} PROD_CATCH
+} FR_API_CATCH
 
 int h2agg_permutation_product(h2agg_ctx* c, const uint8_t* values, const uint8_t* sigmas, size_t m, unsigned k, size_t u,
                               const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta[32],
@@ -272,15 +243,15 @@ int h2agg_permutation_product(h2agg_ctx* c, const uint8_t* values, const uint8_t
     TRY(perm_check(c, m, k, u, beta, gamma, delta, delta_first, init, &pc));
     if (!values || !sigmas || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     const size_t bytes = ((size_t)32 << k) * m;
-    TRY(poly_ensure(c, c->in_a, bytes));
-    TRY(poly_ensure(c, c->in_b, bytes));
-    TRY(poly_ensure(c, c->out, 32 * (u + 1)));
-    TRY(prod_upload(c, c->in_a, values, bytes));
-    TRY(prod_upload(c, c->in_b, sigmas, bytes));
+    TRY(fr_ensure(c, c->in_a, bytes));
+    TRY(fr_ensure(c, c->in_b, bytes));
+    TRY(fr_ensure(c, c->out, 32 * (u + 1)));
+    TRY(fr_stage_in(c, c->in_a, values, bytes));
+    TRY(fr_stage_in(c, c->in_b, sigmas, bytes));
     TRY(clear_flags(c));
     TRY(perm_queue(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, m, k, u, pc, (uint8_t*)c->out.p, nullptr));
     return prod_download(c, u, out, last);
-} PROD_CATCH
+} FR_API_CATCH
 
 int h2agg_lookup_product_device(h2agg_ctx* c, const void* d_a, const void* d_s, const void* d_ap, const void* d_sp, unsigned k,
                                 size_t u, const uint8_t beta[32], const uint8_t gamma[32], void* d_out, void* d_last) try {
@@ -290,7 +261,7 @@ int h2agg_lookup_product_device(h2agg_ctx* c, const void* d_a, const void* d_s, 
     if (!d_a || !d_s || !d_ap || !d_sp || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return lookup_queue(c, (const uint8_t*)d_a, (const uint8_t*)d_s, (const uint8_t*)d_ap, (const uint8_t*)d_sp, u, bf, gf,
                         (uint8_t*)d_out, (uint8_t*)d_last);
-} PROD_CATCH
+} FR_API_CATCH
 
 int h2agg_lookup_product(h2agg_ctx* c, const uint8_t* a, const uint8_t* s, const uint8_t* ap, const uint8_t* sp, unsigned k, size_t u,
                          const uint8_t beta[32], const uint8_t gamma[32], uint8_t* out, uint8_t last[32]) try {
@@ -299,14 +270,14 @@ int h2agg_lookup_product(h2agg_ctx* c, const uint8_t* a, const uint8_t* s, const
     TRY(lookup_check(c, k, u, beta, gamma, &bf, &gf));
     if (!a || !s || !ap || !sp || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     const size_t col = (size_t)32 << k;
-    TRY(poly_ensure(c, c->in_a, 4 * col));
-    TRY(poly_ensure(c, c->out, 32 * (u + 1)));
+    TRY(fr_ensure(c, c->in_a, 4 * col));
+    TRY(fr_ensure(c, c->out, 32 * (u + 1)));
     const uint8_t* cols[4] = {a, s, ap, sp};
-    for (int i = 0; i < 4; ++i) TRY(prod_upload(c, c->in_a, cols[i], 32 * u, i * col));
+    for (int i = 0; i < 4; ++i) TRY(fr_stage_in(c, c->in_a, cols[i], 32 * u, i * col));
     TRY(clear_flags(c));
     const uint8_t* d = (const uint8_t*)c->in_a.p;
     TRY(lookup_queue(c, d, d + col, d + 2 * col, d + 3 * col, u, bf, gf, (uint8_t*)c->out.p, nullptr));
     return prod_download(c, u, out, last);
-} PROD_CATCH
+} FR_API_CATCH
 
 }  // extern "C"

@@ -7,8 +7,8 @@
 //   terms:   the num / den columns of one permutation set, or of a lookup
 // Canonical 32-byte little-endian in and out.
 //
-// Plan.  An array is cut into chunks of T = 2^t elements (t = FR_PROD_CHUNK_LOG = 11), one workgroup each: 256 threads x
-// FR_PROD_PER = 8 consecutive elements in registers (a smaller debug t leaves threads idle).  The threads' products are
+// Plan.  An array is cut into chunks of T = 2^t elements, one workgroup each, 8 consecutive elements per thread in registers
+// (the geometry of fr_chunk.hpp; the levels: fr_level_plan, fr_host.inc).  The threads' products are
 // combined by a binary tree in LDS: 2 * 256 slots, slot 1 the root, slots 2v and 2v + 1 the children of v, slot nthr + tid
 // the leaf of thread tid.
 //   up-sweep   k_fr_prod_chunk:   P[c] = the product of chunk c.  The same kernel runs on P, until ONE chunk is left.
@@ -42,14 +42,10 @@
 // a host copy fills could be rewritten by a second queued call before the first one's launch has read it
 // (fr_fft_kernels.hpp, poly_kernels.hpp).  The table of w^i is built by k_fr_powers on the same stream.
 #pragma once
-#include "fr_fft_kernels.hpp"
+#include "fr_chunk.hpp"
 
 namespace h2agg {
 
-constexpr unsigned FR_PROD_CHUNK_LOG = 11;   // log2 of the elements per workgroup (default)
-constexpr unsigned FR_PROD_PER_LOG = 3;      // log2 of the elements per thread
-constexpr unsigned FR_PROD_PER = 1u << FR_PROD_PER_LOG;
-constexpr int FR_PROD_THREADS = 1 << (FR_PROD_CHUNK_LOG - FR_PROD_PER_LOG);   // 256
 constexpr unsigned FR_PROD_MAX_COLUMNS = 16;
 enum : uint32_t { FR_PROD_INVERT = 0, FR_PROD_SCAN = 1 };
 
@@ -61,7 +57,7 @@ struct FrProdArgs {
     const uint8_t* carry;   // down-sweep: the level above after ITS down-sweep, [chunks]; null at the top
     uint32_t* flags;
     uint32_t n;             // elements at this level.  scan, level 0: u + 1 positions, element u reads as 1
-    uint32_t t;             // log2 T, FR_PROD_PER_LOG .. FR_PROD_CHUNK_LOG
+    uint32_t t;             // log2 T, FR_CHUNK_PER_LOG .. FR_CHUNK_LOG
     uint32_t op;            // FR_PROD_INVERT / FR_PROD_SCAN
     uint32_t level0;
     uint32_t check;         // level 0: src is the caller's, elements are checked for < r
@@ -86,8 +82,8 @@ FP_INLINE Fr fr_prod_element(const FrProdArgs& a, uint32_t i, bool& zero) {
 // dynamically, which would put them into scratch memory.
 //   load: x[e] = element i0 + e (1 for an idle thread), zmask bit e = it was a zero
 template <int E>
-FP_INLINE void fr_prod_load(const FrProdArgs& a, bool active, uint32_t i0, Fr (&x)[FR_PROD_PER], uint32_t& zmask) {
-    if constexpr (E < (int)FR_PROD_PER) {
+FP_INLINE void fr_prod_load(const FrProdArgs& a, bool active, uint32_t i0, Fr (&x)[FR_CHUNK_PER], uint32_t& zmask) {
+    if constexpr (E < (int)FR_CHUNK_PER) {
         bool zero = false;
         x[E] = active ? fr_prod_element(a, i0 + E, zero) : Fr::one();
         if (zero) zmask |= 1u << E;
@@ -96,25 +92,25 @@ FP_INLINE void fr_prod_load(const FrProdArgs& a, bool active, uint32_t i0, Fr (&
 }
 //   prefix: pre[e] = x[0] * .. * x[e], e < 7; returns through p the product of all 8
 template <int E>
-FP_INLINE void fr_prod_prefix(const Fr (&x)[FR_PROD_PER], Fr (&pre)[FR_PROD_PER - 1], Fr& p) {
-    if constexpr (E < (int)FR_PROD_PER - 1) {
+FP_INLINE void fr_prod_prefix(const Fr (&x)[FR_CHUNK_PER], Fr (&pre)[FR_CHUNK_PER - 1], Fr& p) {
+    if constexpr (E < (int)FR_CHUNK_PER - 1) {
         pre[E] = E == 0 ? x[0] : fp_mul<FrParams>(pre[E > 0 ? E - 1 : 0], x[E]);
         fr_prod_prefix<E + 1>(x, pre, p);
     } else {
-        p = fp_mul<FrParams>(pre[FR_PROD_PER - 2], x[FR_PROD_PER - 1]);
+        p = fp_mul<FrParams>(pre[FR_CHUNK_PER - 2], x[FR_CHUNK_PER - 1]);
     }
 }
 //   fold: p = x[0] * .. * x[7]
 template <int E>
-FP_INLINE void fr_prod_fold(const Fr (&x)[FR_PROD_PER], Fr& p) {
-    if constexpr (E < (int)FR_PROD_PER) {
+FP_INLINE void fr_prod_fold(const Fr (&x)[FR_CHUNK_PER], Fr& p) {
+    if constexpr (E < (int)FR_CHUNK_PER) {
         p = E == 0 ? x[0] : fp_mul<FrParams>(p, x[E]);
         fr_prod_fold<E + 1>(x, p);
     }
 }
 //   back: j = the inverse of x[0..E] -> out[i0 + E] = j * pre[E - 1], j -> j * x[E]; E = 7 .. 0; stores only below n
 template <int E>
-FP_INLINE void fr_prod_back(const Fr (&x)[FR_PROD_PER], const Fr (&pre)[FR_PROD_PER - 1], Fr& j, uint32_t zmask, uint8_t* dst,
+FP_INLINE void fr_prod_back(const Fr (&x)[FR_CHUNK_PER], const Fr (&pre)[FR_CHUNK_PER - 1], Fr& j, uint32_t zmask, uint8_t* dst,
                             uint32_t i0, uint32_t n) {
     if constexpr (E >= 0) {
         Fr o = j;
@@ -128,10 +124,10 @@ FP_INLINE void fr_prod_back(const Fr (&x)[FR_PROD_PER], const Fr (&pre)[FR_PROD_
 }
 //   emit: out[i0 + E] = h, h -> h * x[E]; E = 0 .. 7; stores only below n
 template <int E>
-FP_INLINE void fr_prod_emit(const Fr (&x)[FR_PROD_PER], Fr& h, uint8_t* dst, uint32_t i0, uint32_t n) {
-    if constexpr (E < (int)FR_PROD_PER) {
+FP_INLINE void fr_prod_emit(const Fr (&x)[FR_CHUNK_PER], Fr& h, uint8_t* dst, uint32_t i0, uint32_t n) {
+    if constexpr (E < (int)FR_CHUNK_PER) {
         if (i0 + E < n) fp_store<FrParams>(dst + 32 * (size_t)(i0 + E), fp_cond_sub<FrParams>(h));
-        if constexpr (E + 1 < (int)FR_PROD_PER) h = fp_mul<FrParams>(h, x[E]);
+        if constexpr (E + 1 < (int)FR_CHUNK_PER) h = fp_mul<FrParams>(h, x[E]);
         fr_prod_emit<E + 1>(x, h, dst, i0, n);
     }
 }
@@ -149,11 +145,10 @@ FP_INLINE void fr_prod_tree_up(uint32_t* lds, uint32_t tid, uint32_t nthr, const
 
 // Up-sweep.  Indices: a thread reads element i for i in [cT + 8 tid, cT + 8 tid + 8) with i < n only, thread 0 stores dst[c],
 // c < chunks = gridDim.x.
-__global__ void __launch_bounds__(FR_PROD_THREADS) k_fr_prod_chunk(const FrProdArgs a) {
-    __shared__ uint32_t lds[NL * 2 * FR_PROD_THREADS];
-    const uint32_t nthr = 1u << (a.t - FR_PROD_PER_LOG), tid = threadIdx.x, c = blockIdx.x;
-    const uint32_t i0 = (c << a.t) + (tid << FR_PROD_PER_LOG);
-    Fr x[FR_PROD_PER];
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_chunk(const FrProdArgs a) {
+    __shared__ uint32_t lds[NL * 2 * FR_CHUNK_THREADS];
+    const auto [nthr, tid, c, i0] = fr_chunk(a.t, blockIdx.x);
+    Fr x[FR_CHUNK_PER];
     uint32_t zmask = 0;
     fr_prod_load<0>(a, tid < nthr, i0, x, zmask);
     Fr p;
@@ -165,11 +160,10 @@ __global__ void __launch_bounds__(FR_PROD_THREADS) k_fr_prod_chunk(const FrProdA
 // Down-sweep of the inversion.  IN PLACE (dst == src) IS SAFE BECAUSE: a workgroup reads only its own chunk of src — every
 // thread its own 8 elements, all of them into registers before its first store — plus one element of `carry`, which is
 // another buffer; and it stores only at the 8 indices it loaded.  No thread reads what another one writes.
-__global__ void __launch_bounds__(FR_PROD_THREADS) k_fr_prod_invert(const FrProdArgs a) {
-    __shared__ uint32_t lds[NL * 2 * FR_PROD_THREADS];
-    const uint32_t nthr = 1u << (a.t - FR_PROD_PER_LOG), tid = threadIdx.x, c = blockIdx.x;
-    const uint32_t i0 = (c << a.t) + (tid << FR_PROD_PER_LOG);
-    Fr x[FR_PROD_PER], pre[FR_PROD_PER - 1];
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_invert(const FrProdArgs a) {
+    __shared__ uint32_t lds[NL * 2 * FR_CHUNK_THREADS];
+    const auto [nthr, tid, c, i0] = fr_chunk(a.t, blockIdx.x);
+    Fr x[FR_CHUNK_PER], pre[FR_CHUNK_PER - 1];
     uint32_t zmask = 0;
     fr_prod_load<0>(a, tid < nthr, i0, x, zmask);
     Fr p;
@@ -202,17 +196,16 @@ __global__ void __launch_bounds__(FR_PROD_THREADS) k_fr_prod_invert(const FrProd
     }
     if (tid >= nthr) return;   // (behind the last barrier)
     Fr j = fr_fft_lds_get(lds, nthr + tid);
-    fr_prod_back<(int)FR_PROD_PER - 1>(x, pre, j, zmask, a.dst, i0, a.n);
+    fr_prod_back<(int)FR_CHUNK_PER - 1>(x, pre, j, zmask, a.dst, i0, a.n);
 }
 
 // Down-sweep of the scan.  In place (dst == src, which h2agg_fr_grand_product_device allows for out and num) is safe for the
 // reason given at k_fr_prod_invert; dst[n - 1] (level 0: out[u]) is stored by the thread that owns position n - 1, which
 // loads nothing there.
-__global__ void __launch_bounds__(FR_PROD_THREADS) k_fr_prod_scan(const FrProdArgs a) {
-    __shared__ uint32_t lds[NL * 2 * FR_PROD_THREADS];
-    const uint32_t nthr = 1u << (a.t - FR_PROD_PER_LOG), tid = threadIdx.x, c = blockIdx.x;
-    const uint32_t i0 = (c << a.t) + (tid << FR_PROD_PER_LOG);
-    Fr x[FR_PROD_PER];
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_scan(const FrProdArgs a) {
+    __shared__ uint32_t lds[NL * 2 * FR_CHUNK_THREADS];
+    const auto [nthr, tid, c, i0] = fr_chunk(a.t, blockIdx.x);
+    Fr x[FR_CHUNK_PER];
     uint32_t zmask = 0;
     fr_prod_load<0>(a, tid < nthr, i0, x, zmask);
     Fr p;

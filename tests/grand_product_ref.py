@@ -117,15 +117,3 @@ def permuted_pair(seed, k, u):
     assert not left and sorted(sp) == sorted(s[:u])
     pad = [rng.randrange(R) for _ in range(n - u)]
     return a, s, ap + pad, sp + pad
-
-
-def enc(xs):
-    return b"".join((x % R).to_bytes(32, "little") for x in xs)
-
-
-def dec(b):
-    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
-
-
-def fe(x):
-    return (x % R).to_bytes(32, "little")

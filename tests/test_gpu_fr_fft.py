@@ -13,6 +13,7 @@ import pytest
 import __graft_entry__ as entry
 from oracle import bn254 as O
 from oracle import verifier as V
+from tests.fr_bytes import dec, enc
 
 pytestmark = pytest.mark.gpu
 
@@ -22,14 +23,6 @@ R = O.R
 @pytest.fixture(scope="module")
 def poly(pkg):
     return importlib.import_module(entry.PKG_NAME + ".poly")
-
-
-def enc(xs):
-    return b"".join(x.to_bytes(32, "little") for x in xs)
-
-
-def dec(b):
-    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
 
 
 def dft_definition(a, k, inverse, shift):

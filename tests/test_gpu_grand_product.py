@@ -17,9 +17,11 @@ import pytest
 import __graft_entry__ as entry
 from oracle import bn254 as O
 from oracle import pairing as E
-from tests.grand_product_ref import (BIG, DELTA, R, batch_invert_py, dec, enc, fe, grand_product_py, lookup_product_py, omega,
+from tests.fr_bytes import dec, enc, fe
+from tests.grand_product_ref import (BIG, DELTA, R, batch_invert_py, grand_product_py, lookup_product_py, omega,
                                      permutation_chain_py, permutation_product_py, permuted_pair, satisfied_permutation)
-from tests.poly_open_ref import horner
+from tests.poly_open_ref import BIG_Z, horner, quotient_py, random_input
+from tests.test_gpu_fr_fft import ntt_py
 
 pytestmark = pytest.mark.gpu
 
@@ -177,6 +179,41 @@ def test_batch_invert_device_in_and_out_of_place(eng):
     want = enc(batch_invert_py(xs))
     assert bytes(d_out.cpu().numpy()) == want and bytes(d_io.cpu().numpy()) == want
     assert bytes(d_in.cpu().numpy()) == enc(xs)
+
+
+# ---------------------------------------------------------------------------------------------- three families, one queue
+@pytest.mark.parametrize("k,t", [(7, 3), (12, 0)])
+def test_fft_divide_invert_queued_back_to_back(eng, k, t):
+    """fr_fft_device -> fr_poly_divide_device -> fr_batch_invert_device on one context, each output the next call's input,
+    nothing synchronised in between.  The three families share the level plan and the staging of csrc/fr_host.inc but no
+    level buffer: nothing of one call may show in the next.  t = 3 at k = 7 is the three-launch plan 128 -> 16 -> 2 -> 1 of
+    both chunked sweeps; t = 0 is the default chunk.  z has 254 bits; the quotient's top coefficient is the inversion's zero."""
+    import torch
+    dev = torch.device("cuda:0")
+    n = 1 << k
+    a = random_input(700 + k, k)
+    evals = ntt_py(a, k)
+    quot, rem = quotient_py(evals, BIG_Z), horner(evals, BIG_Z)
+    assert quot[n - 1] == 0 and BIG_Z.bit_length() == 254
+    want = batch_invert_py(quot)
+    d_a = torch.frombuffer(bytearray(enc(a)), dtype=torch.uint8).to(dev)
+    d_evals, d_quot, d_inv = torch.zeros_like(d_a), torch.zeros_like(d_a), torch.zeros_like(d_a)
+    d_rem = torch.zeros(32, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    eng.debug_configure("fr_poly_chunk", t)
+    eng.debug_configure("fr_scan_chunk", t)
+    try:
+        eng.fr_fft_device(d_a.data_ptr(), k, False, None, d_evals.data_ptr())
+        eng.fr_poly_divide_device(d_evals.data_ptr(), k, fe(BIG_Z), d_quot.data_ptr(), d_rem.data_ptr())
+        eng.fr_batch_invert_device(d_quot.data_ptr(), n, d_inv.data_ptr())
+        eng.synchronize()
+    finally:
+        eng.debug_configure("fr_poly_chunk", 0)
+        eng.debug_configure("fr_scan_chunk", 0)
+    assert bytes(d_evals.cpu().numpy()) == enc(evals)
+    assert bytes(d_quot.cpu().numpy()) == enc(quot) and bytes(d_rem.cpu().numpy()) == fe(rem)
+    assert bytes(d_inv.cpu().numpy()) == enc(want)
+    assert bytes(d_a.cpu().numpy()) == enc(a), "the input changed"
 
 
 # ---------------------------------------------------------------------------------------------- permutation / lookup

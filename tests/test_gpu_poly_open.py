@@ -17,6 +17,7 @@ import __graft_entry__ as entry
 from oracle import bn254 as O
 from oracle import pairing as E
 from oracle import verifier as V
+from tests.fr_bytes import dec, enc, fe
 from tests.poly_open_ref import BIG_Z, R, assert_division, horner, quotient_py, random_input
 
 pytestmark = pytest.mark.gpu
@@ -25,18 +26,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def poly(pkg):
     return importlib.import_module(entry.PKG_NAME + ".poly")
-
-
-def enc(xs):
-    return b"".join(x.to_bytes(32, "little") for x in xs)
-
-
-def dec(b):
-    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
-
-
-def fe(x):
-    return (x % R).to_bytes(32, "little")
 
 
 def inputs(seed, k, t):
