@@ -17,13 +17,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libh2agg.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "h2agg.h")
 
-OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, ERR_BAD_POINT, ERR_PEER = range(9)
+OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, ERR_BAD_POINT, ERR_PEER, ERR_NOT_IN_TABLE = range(10)
 OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
 FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
 FR_FFT_MAX_K = 24
 FR_POLY_CHUNK = 11   # log2 of the coefficients per workgroup of the KZG opening kernels by default (csrc/fr_chunk.hpp)
 FR_SCAN_CHUNK = 11   # log2 of the elements per workgroup of the grand-product kernels by default (csrc/fr_chunk.hpp)
 FR_PROD_MAX_COLUMNS = 16
+FR_SORT_TILE = 11    # log2 of the keys per workgroup of the lookup permutation by default (csrc/lookup_kernels.hpp)
+FR_SORT_TILE_MIN = 4
+FR_COMPRESS_MAX_COLUMNS = 1 << 16   # most columns of one fr_columns_compress (the library's limit: csrc/lookup.inc)
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
@@ -172,6 +175,10 @@ def load_library():
         "h2agg_permutation_product_device": (i32, [ctxp, vp, vp, sz, C.c_uint, sz, u8p, u8p, u8p, u8p, u8p, vp, vp]),
         "h2agg_lookup_product": (i32, [ctxp, vp, vp, vp, vp, C.c_uint, sz, u8p, u8p, vp, vp]),
         "h2agg_lookup_product_device": (i32, [ctxp, vp, vp, vp, vp, C.c_uint, sz, u8p, u8p, vp, vp]),
+        "h2agg_lookup_permute": (i32, [ctxp, vp, vp, C.c_uint, sz, vp, vp]),
+        "h2agg_lookup_permute_device": (i32, [ctxp, vp, vp, C.c_uint, sz, vp, vp]),
+        "h2agg_fr_columns_compress": (i32, [ctxp, vp, sz, C.c_uint, u8p, vp]),
+        "h2agg_fr_columns_compress_device": (i32, [ctxp, vp, sz, C.c_uint, u8p, vp]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -652,6 +659,39 @@ class H2Agg:
         self._need32(beta=beta, gamma=gamma)
         self._check(self._lib.h2agg_lookup_product_device(self._ctx, d_a_ptr, d_s_ptr, d_ap_ptr, d_sp_ptr, k, u, beta, gamma,
                                                           d_out_ptr, d_last_ptr))
+
+    # ------------------------------------------------------------------ lookup argument: compression, permutation
+    def lookup_permute(self, a: bytes, s: bytes, k: int, u: int):
+        """h2agg_lookup_permute: the first u rows of the compressed input and table -> (ap, sp), 32 * u bytes each
+        (permute_expression_pair); a and s hold at least u elements, only those are read"""
+        if 0 <= k <= FR_FFT_MAX_K and 0 <= u < (1 << k):
+            for x, what in ((a, "a"), (s, "s")):
+                if x is None or len(x) < 32 * u or len(x) % 32:
+                    raise ValueError("%s must hold at least %d elements of 32 bytes" % (what, u))
+        ap, sp = C.create_string_buffer(32 * max(u, 1)), C.create_string_buffer(32 * max(u, 1))
+        self._check(self._lib.h2agg_lookup_permute(self._ctx, self._hostptr(a), self._hostptr(s), k, u, ap, sp))
+        return ap.raw[:32 * max(u, 0)], sp.raw[:32 * max(u, 0)]
+
+    def lookup_permute_device(self, d_a_ptr: int, d_s_ptr: int, k: int, u: int, d_ap_ptr: int, d_sp_ptr: int):
+        """h2agg_lookup_permute_device: columns in device memory, queued on the context's stream (no synchronisation); rows
+        from u up of d_ap / d_sp are left alone; d_ap / d_sp must not overlap d_a, d_s or each other"""
+        self._check(self._lib.h2agg_lookup_permute_device(self._ctx, d_a_ptr, d_s_ptr, k, u, d_ap_ptr, d_sp_ptr))
+
+    def fr_columns_compress(self, cols: bytes, m: int, k: int, theta: bytes) -> bytes:
+        """h2agg_fr_columns_compress: a slab [m][2^k] -> out[i] = sum_j theta^(m - 1 - j) cols[j][i], 2^k elements"""
+        self._need32(theta=theta)
+        if not (0 <= k <= FR_FFT_MAX_K and m >= 1):
+            raise H2AggError(ERR_INVALID, "fr_columns_compress: k must be 0 .. %d and m >= 1" % FR_FFT_MAX_K)
+        _need(cols, (32 << k) * m, "cols")       # (the library refuses an m above its limit before it reads cols)
+        out = C.create_string_buffer(32 << k)
+        self._check(self._lib.h2agg_fr_columns_compress(self._ctx, self._hostptr(cols), m, k, theta, out))
+        return out.raw
+
+    def fr_columns_compress_device(self, d_cols_ptr: int, m: int, k: int, theta: bytes, d_out_ptr: int):
+        """h2agg_fr_columns_compress_device: slab and result in device memory, queued on the context's stream (no
+        synchronisation); d_out_ptr may be one of the columns"""
+        self._need32(theta=theta)
+        self._check(self._lib.h2agg_fr_columns_compress_device(self._ctx, d_cols_ptr, m, k, theta, d_out_ptr))
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

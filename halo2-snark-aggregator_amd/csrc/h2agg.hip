@@ -33,6 +33,7 @@
 #include "fr_fft_kernels.hpp"
 #include "poly_kernels.hpp"
 #include "prod_kernels.hpp"
+#include "lookup_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -194,6 +195,10 @@ struct h2agg_ctx {
     // h2agg_fr_grand_product), the chunk products of every level above the elements, the two-level table of w^i
     DevBuf prod_num, prod_den, prod_lvl, prod_tab;
     int dbg_fr_scan_chunk = 0;   // debug key fr_scan_chunk: log2 of the elements per workgroup (0 = FR_CHUNK_LOG)
+    // lookup permutation (csrc/lookup.inc): the key buffers, rank columns, count matrix, histograms and plans of a call
+    // (lk_layout), the descriptor of a compression
+    DevBuf lk_work, lk_desc;
+    int dbg_fr_sort_tile = 0;   // debug key fr_sort_tile: log2 of the keys per workgroup (0 = LK_TILE_LOG)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -321,6 +326,7 @@ int flags_to_status(h2agg_ctx* c, uint32_t f, bool earlier) {
         return fail(c, H2AGG_ERR_DIV_ZERO, std::string(pre) + "inversion of zero (reference: invert().unwrap() panics)");
     if (f & FLAG_NONCANONICAL) return fail(c, H2AGG_ERR_NONCANONICAL, std::string(pre) + "input integer >= modulus");
     if (f & FLAG_BAD_POINT) return fail(c, H2AGG_ERR_BAD_POINT, std::string(pre) + "invalid point encoding in proof");
+    if (f & FLAG_NOT_IN_TABLE) return fail(c, H2AGG_ERR_NOT_IN_TABLE, std::string(pre) + "a lookup input does not occur in the table");
     return H2AGG_OK;
 }
 
@@ -1358,7 +1364,7 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale,
                       &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work,
                       &c->poly_work, &c->poly_desc, &c->poly_slab, &c->poly_jac,
-                      &c->prod_num, &c->prod_den, &c->prod_lvl, &c->prod_tab};
+                      &c->prod_num, &c->prod_den, &c->prod_lvl, &c->prod_tab, &c->lk_work, &c->lk_desc};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -2361,6 +2367,10 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         if (value != 0 && (value < (int)FR_CHUNK_PER_LOG || value > (int)FR_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_scan_chunk must be 0 or 3 .. 11");
         c->dbg_fr_scan_chunk = value;
     }
+    else if (k == "fr_sort_tile") {                          // lookup permutation: log2 of the keys per workgroup, 4 .. 11 (0 = the default, 11)
+        if (value != 0 && (value < (int)LK_TILE_LOG_MIN || value > (int)LK_TILE_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_sort_tile must be 0 or 4 .. 11");
+        c->dbg_fr_sort_tile = value;
+    }
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
     return H2AGG_OK;
@@ -2577,3 +2587,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "fr_fft.inc"
 #include "poly_open.inc"
 #include "prod.inc"
+#include "lookup.inc"

@@ -1,7 +1,7 @@
 """EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), the two ways to commit to a polynomial, and
 the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen);
 and the grand products of the permutation and lookup arguments (h2agg_fr_batch_invert, h2agg_permutation_product,
-h2agg_lookup_product).
+h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr_columns_compress, h2agg_lookup_permute).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -143,3 +143,41 @@ def lookup_product(eng, a: bytes, s: bytes, ap: bytes, sp: bytes, k: int, usable
     their permuted forms (permute_expression_pair, a sort, is the caller's).  -> one column of 2^k rows."""
     z, _last = eng.lookup_product(_poly(a, k, "a"), _poly(s, k, "s"), _poly(ap, k, "ap"), _poly(sp, k, "sp"), k, usable, beta, gamma)
     return _z_column(z, k, usable, blinding)
+
+
+# ---------------------------------------------------------------------------------------------- lookup argument
+def compress_expressions(eng, cols, k: int, theta: bytes) -> bytes:
+    """the theta-fold of lookup::prover::commit_permuted: cols is a list of m >= 1 columns (2^k elements each), the first one
+    ends under the highest power of theta.  -> one column of 2^k rows."""
+    if not cols:
+        raise ValueError("cols must hold at least one column")
+    for col in cols:
+        _poly(col, k, "column")
+    return eng.fr_columns_compress(b"".join(cols), len(cols), k, theta)
+
+
+def permute_expression_pair(eng, a: bytes, s: bytes, k: int, usable: int, blinding=None):
+    """lookup::prover::permute_expression_pair: the compressed input a and table s (2^k rows each) -> (ap, sp), columns of 2^k
+    rows: ap the usable rows of a in ascending order, sp the usable rows of s rearranged so that sp[i] = ap[i] wherever
+    ap[i] starts a run.  The top 2^k - usable rows come from blinding = (block for ap, block for sp), or are zero.  Raises
+    H2AggError(ERR_NOT_IN_TABLE) if a usable input value is not among the usable table rows."""
+    top = (1 << k) - usable
+    if blinding is None:
+        blinding = (bytes(32 * top), bytes(32 * top))
+    if len(blinding) != 2 or any(len(b) != 32 * top for b in blinding):
+        raise ValueError("blinding must be two blocks of %d elements of 32 bytes" % top)
+    ap, sp = eng.lookup_permute(_poly(a, k, "a"), _poly(s, k, "s"), k, usable)
+    return ap + bytes(blinding[0]), sp + bytes(blinding[1])
+
+
+def lookup_argument(eng, inputs, tables, k: int, usable: int, theta: bytes, beta: bytes, gamma: bytes, blinding=None):
+    """one lookup from its expressions to its Z: compress_expressions of the input and the table columns,
+    permute_expression_pair, lookup_product.  blinding: None, or (block for ap, block for sp, block for z) with
+    2^k - usable, 2^k - usable and 2^k - usable - 1 elements.  -> (ap, sp, z), columns of 2^k rows."""
+    if blinding is not None and len(blinding) != 3:
+        raise ValueError("blinding must be three blocks: ap, sp, z")
+    a = compress_expressions(eng, inputs, k, theta)
+    s = compress_expressions(eng, tables, k, theta)
+    ap, sp = permute_expression_pair(eng, a, s, k, usable, None if blinding is None else blinding[:2])
+    z = lookup_product(eng, a, s, ap, sp, k, usable, beta, gamma, None if blinding is None else blinding[2])
+    return ap, sp, z

@@ -46,7 +46,8 @@ enum {
     H2AGG_ERR_NOMEM = 6,
     H2AGG_ERR_BAD_POINT = 7,    /* a compressed point does not decode: "invalid point encoding in proof", transcript.rs:65-70;
                                    a partial accumulator received from a peer rank is not on the curve */
-    H2AGG_ERR_PEER = 8          /* sharded aggregation: another rank failed (its code is in the message); this rank's inputs were fine */
+    H2AGG_ERR_PEER = 8,         /* sharded aggregation: another rank failed (its code is in the message); this rank's inputs were fine */
+    H2AGG_ERR_NOT_IN_TABLE = 9  /* h2agg_lookup_permute: an input value does not occur in the table (halo2: Error::ConstraintSystemFailure) */
 };
 
 /* field ops of h2agg_fr_batch_op */
@@ -644,7 +645,8 @@ int h2agg_kzg_multiopen_device(h2agg_ctx* ctx, uint64_t g_handle, const void* d_
  *   lookup_product       compressed input a, compressed table s, their permuted forms ap and sp, n rows each.
  *                          num[i] = (a[i] + beta)(s[i] + gamma),  den[i] = (ap[i] + beta)(sp[i] + gamma)
  *                        The result is grand_product(num, den, u, 1).  The theta-compression of the expressions (a linear
- *                        combination) and permute_expression_pair (a sort) are the caller's job.
+ *                        combination) and permute_expression_pair (a sort) are the caller's job.  Both are entry points of
+ *                        the next block: h2agg_fr_columns_compress and h2agg_lookup_permute.
  * Only rows i < u of a column are read.
  *
  * Every entry point is synchronous over host buffers (pageable or h2agg_host_alloc) and has a _device twin over DEVICE
@@ -674,6 +676,41 @@ int h2agg_lookup_product(h2agg_ctx* ctx, const uint8_t* a, const uint8_t* s, con
                          size_t u, const uint8_t beta[32], const uint8_t gamma[32], uint8_t* out, uint8_t last[32]);
 int h2agg_lookup_product_device(h2agg_ctx* ctx, const void* d_a, const void* d_s, const void* d_ap, const void* d_sp, unsigned k,
                                 size_t u, const uint8_t beta[32], const uint8_t gamma[32], void* d_out, void* d_last);
+
+/* ---- Lookup argument: theta-compression and permute_expression_pair ---------------------------------------------------------
+ * Stand for: the theta-fold of lookup::prover::commit_permuted and lookup::prover::permute_expression_pair of halo2_proofs —
+ * recalled from upstream, not pinned, like the block above; what the entry points compute is this definition.  Which pair a
+ * verifier accepts IS pinned (lookup.rs:98-113): on the rows below u, ap[0] = sp[0]; every row has ap[i] = sp[i] or
+ * ap[i] = ap[i-1]; ap is a permutation of a and sp one of s (which is what makes z[u] = 1).
+ *
+ * Elements, columns (n = 2^k rows, k <= 24) and u (0 <= u <= n - 1) are those of the block above.
+ *   lookup_permute(a, s, k, u) -> ap[0..u), sp[0..u)
+ *     - ap[0..u) is a[0..u) in ascending order of the canonical integer value (halo2curves' Ord for Fr).
+ *     - Row i is a head if i == 0 or ap[i] != ap[i-1].  For a head sp[i] = ap[i], and one occurrence of that value is taken
+ *       out of the multiset s[0..u).
+ *     - What is left of the multiset, in ascending order and with repeats kept, fills the non-head rows from the highest row
+ *       down: the j-th leftover value goes to the j-th non-head row counted from row u - 1 (halo2's
+ *       repeated_input_rows.pop() over an ascending BTreeMap).
+ *     - Rows from u up of a and s are not read; rows from u up of ap and sp are not written (the caller's blinding rows).
+ *     - A head value that does not occur in s[0..u): H2AGG_ERR_NOT_IN_TABLE (halo2: Error::ConstraintSystemFailure); the
+ *       outputs are then unspecified.  u == 0 writes nothing and succeeds.
+ *   columns_compress(cols[m][n], theta) -> out[n]:  out[i] = sum_j theta^(m-1-j) cols[j][i] — halo2's fold
+ *       acc * theta + expr, the first expression under the highest power; 1 <= m <= 65536, all n rows.
+ *
+ * The plain entry points are synchronous over host buffers; the _device twins are queued on the context's stream with no
+ * synchronisation and no host read-back between their kernels (buffer rules: h2agg_fr_fft_device; a workspace that has to
+ * grow drains the device first).  d_ap and d_sp must not overlap d_a, d_s or each other; d_out of the compression may be
+ * one of its columns.  The work memory of lookup_permute — four key buffers, five 32-bit columns and the count matrix of a
+ * sort pass, about 150 bytes per row — is kept in the context.
+ * Refusals, the context stays usable after each: k > 24, u >= 2^k, m == 0 or m > 65536, a null buffer, overlapping device
+ *   ranges: H2AGG_ERR_INVALID.  theta >= r: H2AGG_ERR_NONCANONICAL from the call.  A column element >= r
+ *   (H2AGG_ERR_NONCANONICAL) or an absent head value (H2AGG_ERR_NOT_IN_TABLE): through the context's device status — from the
+ *   call for the synchronous entry points, at h2agg_synchronize (or the next synchronous entry point), once, for the _device
+ *   twins.  Out of memory: H2AGG_ERR_NOMEM. */
+int h2agg_lookup_permute(h2agg_ctx* ctx, const uint8_t* a, const uint8_t* s, unsigned k, size_t u, uint8_t* ap, uint8_t* sp);
+int h2agg_lookup_permute_device(h2agg_ctx* ctx, const void* d_a, const void* d_s, unsigned k, size_t u, void* d_ap, void* d_sp);
+int h2agg_fr_columns_compress(h2agg_ctx* ctx, const uint8_t* cols, size_t m, unsigned k, const uint8_t theta[32], uint8_t* out);
+int h2agg_fr_columns_compress_device(h2agg_ctx* ctx, const void* d_cols, size_t m, unsigned k, const uint8_t theta[32], void* d_out);
 
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
@@ -743,6 +780,10 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *       "fr_scan_chunk" t the grand-product kernels (batch inversion, running product) cut an array into chunks of 2^t elements
  *                         per workgroup, 3 .. 11 (0 = the default, 11): inputs of 64 to 1024 rows then run the three- and
  *                         four-level plans
+ *       "fr_sort_tile" t  h2agg_lookup_permute sorts and ranks in tiles of 2^t keys per workgroup, 4 .. 11 (0 = the default, 11);
+ *                         below 11 the step of its row scans, the threads that take keys in its byte histogram (both 2^(t-2))
+ *                         and that histogram's grid (2 workgroups) shrink with the tile: at t = 4 inputs of 65 to 1024 rows
+ *                         then run every multi-tile path, the step loops of both scans and the histogram's stride loop included
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
  *       "seg_chunk" n     h2agg_g1_msm_segmented / h2agg_verify_proofs: at most n points per set of launches of the segmented
  *                         multi_exp (0 = automatic, 16384); a segment longer than that is an ordinary multi_exp of its own
