@@ -27,6 +27,7 @@ FR_PROD_MAX_COLUMNS = 16
 FR_SORT_TILE = 11    # log2 of the keys per workgroup of the lookup permutation by default (csrc/lookup_kernels.hpp)
 FR_SORT_TILE_MIN = 4
 FR_COMPRESS_MAX_COLUMNS = 1 << 16   # most columns of one fr_columns_compress (the library's limit: csrc/lookup.inc)
+EXPR_MAX_DEPTH = 16  # H2AGG_EXPR_MAX_DEPTH: the operand stack of h2agg_vk_expressions_eval / h2agg_quotient (csrc/quotient_kernels.hpp)
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
@@ -179,6 +180,10 @@ def load_library():
         "h2agg_lookup_permute_device": (i32, [ctxp, vp, vp, C.c_uint, sz, vp, vp]),
         "h2agg_fr_columns_compress": (i32, [ctxp, vp, sz, C.c_uint, u8p, vp]),
         "h2agg_fr_columns_compress_device": (i32, [ctxp, vp, sz, C.c_uint, u8p, vp]),
+        "h2agg_vk_expressions_eval": (i32, [ctxp, vp, i32, sz, C.c_uint, vp, vp, vp, u8p, u8p, vp]),
+        "h2agg_vk_expressions_eval_device": (i32, [ctxp, vp, i32, sz, C.c_uint, vp, vp, vp, u8p, u8p, vp]),
+        "h2agg_quotient": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
+        "h2agg_quotient_device": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -692,6 +697,82 @@ class H2Agg:
         synchronisation); d_out_ptr may be one of the columns"""
         self._need32(theta=theta)
         self._check(self._lib.h2agg_fr_columns_compress_device(self._ctx, d_cols_ptr, m, k, theta, d_out_ptr))
+
+    # ------------------------------------------------------------------ quotient polynomial
+    def _slab_or_null(self, data):
+        return None if data is None else self._hostptr(data)
+
+    def _vk_slabs(self, vk, k: int, named):
+        """host slabs of a key's columns: (data or None, count, name) -> pointers; where k is the key's, the library reads
+        count * 2^k elements of each, so their sizes are checked here"""
+        out = []
+        for data, count, what in named:
+            if data is not None and k == vk.shape["k"]:
+                _need(data, (32 << k) * count, what)
+            out.append(self._slab_or_null(data))
+        return out
+
+    @staticmethod
+    def _vk_challenges(vk, challenges):
+        if challenges is not None:
+            _need(challenges, 32 * vk.shape["num_challenges"], "challenges")
+        return challenges
+
+    def vk_expressions_eval(self, vk, which: int, j: int, k: int, advice, fixed, instance, challenges,
+                            fold: Optional[bytes] = None) -> bytes:
+        """h2agg_vk_expressions_eval: expressions of the key `vk` (a verifier.VerifyingKey) on every row of host value slabs
+        [columns][2^k] (None for a slab without columns; challenges: num_challenges x 32 bytes or None).  which = 0: the gate
+        polynomials, 1 / 2: the input / table expressions of lookup j.  fold None -> the slab [expressions][2^k]; a 32-byte
+        fold -> one column.  The sizes come from vk.shape."""
+        sh = vk.shape
+        if fold is not None:
+            _need(fold, 32, "fold")
+        m = sh["gate_polys"] if which == 0 else sh["lookups"][j][which - 1] if which in (1, 2) and 0 <= j < len(sh["lookups"]) else 0
+        cols = 1 if fold is not None else m
+        out = C.create_string_buffer(max((32 << sh["k"]) * cols, 1))   # (the library writes only when k is the key's)
+        slabs = self._vk_slabs(vk, k, ((advice, sh["num_advice"], "advice"), (fixed, sh["num_fixed"], "fixed"),
+                                       (instance, sh["num_instance"], "instance")))
+        self._check(self._lib.h2agg_vk_expressions_eval(self._ctx, vk._vk, which, j, k, *slabs, self._vk_challenges(vk, challenges),
+                                                        fold, out))
+        return out.raw[:(32 << sh["k"]) * cols]
+
+    def vk_expressions_eval_device(self, vk, which: int, j: int, k: int, d_advice_ptr, d_fixed_ptr, d_instance_ptr, challenges,
+                                   fold: Optional[bytes], d_out_ptr):
+        """h2agg_vk_expressions_eval_device: slabs and result in device memory, queued on the context's stream (no
+        synchronisation)"""
+        if fold is not None:
+            _need(fold, 32, "fold")
+        self._check(self._lib.h2agg_vk_expressions_eval_device(self._ctx, vk._vk, which, j, k, d_advice_ptr, d_fixed_ptr,
+                                                               d_instance_ptr, challenges, fold, d_out_ptr))
+
+    def quotient(self, vk, advice, fixed, instance, sigma, perm_z, lookup_z, lookup_ap, lookup_sp, challenges, theta: bytes,
+                 beta: bytes, gamma: bytes, y: bytes, delta: bytes) -> bytes:
+        """h2agg_quotient: coefficient slabs [polynomials][2^k] on the host (None for a slab without polynomials) -> the slab
+        [degree - 1][2^k] of h's pieces.  The sizes come from vk.shape."""
+        self._need32(theta=theta, beta=beta, gamma=gamma, y=y, delta=delta)
+        sh = vk.shape
+        k, pieces, nl = sh["k"], sh["degree"] - 1, len(sh["lookups"])
+        nsets = -(-sh["num_permutation_columns"] // (sh["degree"] - 2))
+        slabs = self._vk_slabs(vk, k, ((advice, sh["num_advice"], "advice"), (fixed, sh["num_fixed"], "fixed"),
+                                       (instance, sh["num_instance"], "instance"), (sigma, sh["num_permutation_columns"], "sigma"),
+                                       (perm_z, nsets, "perm_z"), (lookup_z, nl, "lookup_z"), (lookup_ap, nl, "lookup_ap"),
+                                       (lookup_sp, nl, "lookup_sp")))
+        if (pieces << k) > (1 << FR_FFT_MAX_K):   # (the library refuses it as well: the extended domain is 2^(k+e) >= pieces * 2^k)
+            raise H2AggError(ERR_INVALID, "quotient: the extended domain must be <= 2^%d" % FR_FFT_MAX_K)
+        out = C.create_string_buffer((32 << k) * pieces)
+        self._check(self._lib.h2agg_quotient(self._ctx, vk._vk, *slabs, self._vk_challenges(vk, challenges), theta, beta, gamma, y,
+                                             delta, out))
+        return out.raw
+
+    def quotient_device(self, vk, d_advice_ptr, d_fixed_ptr, d_instance_ptr, d_sigma_ptr, d_perm_z_ptr, d_lookup_z_ptr,
+                        d_lookup_ap_ptr, d_lookup_sp_ptr, challenges, theta: bytes, beta: bytes, gamma: bytes, y: bytes,
+                        delta: bytes, d_h_ptr):
+        """h2agg_quotient_device: coefficient slabs and the pieces in device memory, queued on the context's stream (no
+        synchronisation, no read-back)"""
+        self._need32(theta=theta, beta=beta, gamma=gamma, y=y, delta=delta)
+        self._check(self._lib.h2agg_quotient_device(self._ctx, vk._vk, d_advice_ptr, d_fixed_ptr, d_instance_ptr, d_sigma_ptr,
+                                                    d_perm_z_ptr, d_lookup_z_ptr, d_lookup_ap_ptr, d_lookup_sp_ptr, challenges,
+                                                    theta, beta, gamma, y, delta, d_h_ptr))
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

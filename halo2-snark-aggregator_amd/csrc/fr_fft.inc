@@ -41,13 +41,15 @@ int fr_fft_ensure_twiddles(h2agg_ctx* c, unsigned k, int inv) {
 }
 
 // Queues the transform of d_in into d_out on the context's stream (no synchronisation unless a workspace has to grow).
-// shift: null, or the checked non-zero shift.
-int fr_fft_queue(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, const ph::HFr* shift, uint8_t* d_out) {
+// shift: null, or the checked non-zero shift.  shift_ready: the context's shift table already holds this shift, direction and
+// k (the transform queued just before this one built it): several polynomials on one coset share one table.
+int fr_fft_queue(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, const ph::HFr* shift, uint8_t* d_out,
+                 bool shift_ready = false) {
     const unsigned L = c->dbg_fr_fft_local ? (unsigned)c->dbg_fr_fft_local : FR_FFT_LOCAL;
     const unsigned P = k ? (k + L - 1) / L : 1;
     if (P > 1) TRY(fr_ensure(c, c->frfft_work, (size_t)32 << k));
     if (k) TRY(fr_fft_ensure_twiddles(c, k, inv));
-    if (shift) {
+    if (shift && !shift_ready) {
         TRY(fr_ensure(c, c->frfft_shift, fr_table_bytes(k)));
         fr_table_launch(c, inv ? ph::inv(*shift) : *shift, k, (uint8_t*)c->frfft_shift.p);
     }

@@ -34,6 +34,7 @@
 #include "poly_kernels.hpp"
 #include "prod_kernels.hpp"
 #include "lookup_kernels.hpp"
+#include "quotient_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -199,6 +200,9 @@ struct h2agg_ctx {
     // (lk_layout), the descriptor of a compression
     DevBuf lk_work, lk_desc;
     int dbg_fr_sort_tile = 0;   // debug key fr_sort_tile: log2 of the keys per workgroup (0 = LK_TILE_LOG)
+    // quotient polynomial (csrc/quotient.inc): a coset's value slab with the columns behind it and the extended evaluations
+    // (qt_layout), the compiled programs and the permutation columns' places, the two-level table of w^i
+    DevBuf qt_work, qt_prog, qt_tab;
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -1364,7 +1368,8 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->seg_wsum, &c->seg_dev, &c->seg_out, &c->fft_tw[0], &c->fft_tw[1], &c->fft_scale,
                       &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work,
                       &c->poly_work, &c->poly_desc, &c->poly_slab, &c->poly_jac,
-                      &c->prod_num, &c->prod_den, &c->prod_lvl, &c->prod_tab, &c->lk_work, &c->lk_desc};
+                      &c->prod_num, &c->prod_den, &c->prod_lvl, &c->prod_tab, &c->lk_work, &c->lk_desc,
+                      &c->qt_work, &c->qt_prog, &c->qt_tab};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -2588,3 +2593,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "poly_open.inc"
 #include "prod.inc"
 #include "lookup.inc"
+#include "quotient.inc"

@@ -1,7 +1,8 @@
 """EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), the two ways to commit to a polynomial, and
 the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen);
 and the grand products of the permutation and lookup arguments (h2agg_fr_batch_invert, h2agg_permutation_product,
-h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr_columns_compress, h2agg_lookup_permute).
+h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr_columns_compress, h2agg_lookup_permute);
+and the quotient polynomial h(X) from a verifying key (h2agg_vk_expressions_eval, h2agg_quotient).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -181,3 +182,55 @@ def lookup_argument(eng, inputs, tables, k: int, usable: int, theta: bytes, beta
     ap, sp = permute_expression_pair(eng, a, s, k, usable, None if blinding is None else blinding[:2])
     z = lookup_product(eng, a, s, ap, sp, k, usable, beta, gamma, None if blinding is None else blinding[2])
     return ap, sp, z
+
+
+# ---------------------------------------------------------------------------------------------- quotient polynomial
+def _slab(cols, count: int, k: int, what: str):
+    """a list of `count` columns -> one slab, or None for no columns"""
+    cols = list(cols or [])
+    if len(cols) != count:
+        raise ValueError("%s must be %d columns (got %d)" % (what, count, len(cols)))
+    for col in cols:
+        _poly(col, k, what)
+    return b"".join(cols) if cols else None
+
+
+def _challenges(vk, challenges):
+    challenges = list(challenges or [])
+    if len(challenges) != vk.shape["num_challenges"] or any(len(c) != 32 for c in challenges):
+        raise ValueError("challenges must be %d scalars of 32 bytes" % vk.shape["num_challenges"])
+    return b"".join(challenges) if challenges else None
+
+
+def expressions_eval(eng, vk, which: int, j: int, advice, fixed, instance, challenges, fold=None):
+    """expressions of the key on every row of value columns (lists of 2^k-element columns per kind; challenges: a list of
+    32-byte scalars).  which = 0: the gate polynomials, 1 / 2: the input / table expressions of lookup j.  fold None -> a list
+    with one column per expression; fold = 32 bytes -> one column, sum_j fold^(m-1-j) E_j (fold = theta on a lookup's lists:
+    the compressed columns of commit_permuted; fold = y on the gates: their share of the quotient's numerator)."""
+    sh = vk.shape
+    k = sh["k"]
+    out = eng.vk_expressions_eval(vk, which, j, k, _slab(advice, sh["num_advice"], k, "advice"), _slab(fixed, sh["num_fixed"], k, "fixed"),
+                                  _slab(instance, sh["num_instance"], k, "instance"), _challenges(vk, challenges), fold)
+    return out if fold is not None else [out[at:at + (32 << k)] for at in range(0, len(out), 32 << k)]
+
+
+def quotient_pieces(eng, vk, advice, fixed, instance, sigma, perm_z, lookup_z, lookup_ap, lookup_sp, challenges, theta: bytes,
+                    beta: bytes, gamma: bytes, y: bytes, delta: bytes):
+    """the pieces h_0 .. h_{degree-2} of the quotient polynomial (include/h2agg.h): every argument in front of `challenges`
+    is a list of polynomials in coefficient form, 2^k elements each — the key's advice, fixed and instance columns, the
+    permutation's sigma polynomials and the Z of its sets, and Z, a', s' of every lookup.  -> a list of degree - 1
+    polynomials of 2^k coefficients."""
+    sh = vk.shape
+    k, chunk, nl = sh["k"], sh["degree"] - 2, len(sh["lookups"])
+    nsets = (sh["num_permutation_columns"] + chunk - 1) // chunk
+    out = eng.quotient(vk, _slab(advice, sh["num_advice"], k, "advice"), _slab(fixed, sh["num_fixed"], k, "fixed"),
+                       _slab(instance, sh["num_instance"], k, "instance"), _slab(sigma, sh["num_permutation_columns"], k, "sigma"),
+                       _slab(perm_z, nsets, k, "perm_z"), _slab(lookup_z, nl, k, "lookup_z"), _slab(lookup_ap, nl, k, "lookup_ap"),
+                       _slab(lookup_sp, nl, k, "lookup_sp"), _challenges(vk, challenges), theta, beta, gamma, y, delta)
+    return [out[at:at + (32 << k)] for at in range(0, len(out), 32 << k)]
+
+
+def commit_quotient(eng, g_handle: int, pieces):
+    """the commitments of h's pieces against the monomial table (ParamsKZG.g), in order: commit_coeff of each, as 96-byte
+    Jacobian points (the h commitments a proof carries, vanish.rs:18-72)"""
+    return [commit_coeff(eng, g_handle, p) for p in pieces]

@@ -73,6 +73,47 @@ def encode_vk(cs, aff_to_bytes) -> bytes:
     return out
 
 
+def vk_shape(blob: bytes) -> dict:
+    """the counts a caller of the quotient entry points sizes its buffers with, read off an "H2VK" description (format:
+    include/h2agg.h): k, the column counts, degree, blinding_factors, the number of gate polynomials and every lookup's
+    (input expressions, table expressions).  The library validates the blob; this only walks it."""
+    at = [8]
+
+    def skip(nbytes):
+        at[0] += nbytes
+
+    def u32():
+        skip(4)
+        return int.from_bytes(blob[at[0] - 4:at[0]], "little")
+
+    def exprs():
+        n = u32()
+        for _ in range(n):
+            nb = u32()
+            skip((nb + 3) & ~3)
+        return n
+    k, num_advice, num_instance, num_challenges, degree, blinding = [u32() for _ in range(6)]
+    skip(((num_advice + 3) & ~3) + ((num_challenges + 3) & ~3))
+    for _ in range(3):
+        nq = u32()
+        skip(8 * nq)
+    nperm = u32()
+    skip(8 * nperm)
+    nfixed = u32()
+    skip(64 * nfixed)
+    ncommit = u32()
+    skip(64 * ncommit + 32)
+    ngates = u32()
+    gate_polys = sum([exprs() for _ in range(ngates)])
+    nlookups = u32()
+    lookups = [(exprs(), exprs()) for _ in range(nlookups)]
+    if at[0] != len(blob):
+        raise ValueError("vk blob: %d bytes, its description ends at %d" % (len(blob), at[0]))
+    return {"k": k, "num_advice": num_advice, "num_instance": num_instance, "num_challenges": num_challenges, "degree": degree,
+            "blinding_factors": blinding, "num_fixed": nfixed, "num_permutation_columns": nperm, "gate_polys": gate_polys,
+            "lookups": lookups}
+
+
 class _CircuitProofs(C.Structure):
     _fields_ = [("vk", C.c_void_p), ("name", C.c_char_p), ("g_lagrange", C.c_uint64), ("nproofs", C.c_size_t),
                 ("transcripts", C.POINTER(C.c_char_p)), ("transcript_lens", C.POINTER(C.c_size_t)),
@@ -97,6 +138,7 @@ class VerifyingKey:
         # header words of the accepted blob (include/h2agg.h): magic, version, k, num_advice, num_instance, ...
         self.k, self.num_advice_columns, self.num_instance_columns = (
             int.from_bytes(blob[8 + 4 * i:12 + 4 * i], "little") for i in range(3))
+        self.shape = vk_shape(blob)
 
     def close(self):
         if self._vk:

@@ -465,7 +465,9 @@ int h2agg_verify_proofs(h2agg_ctx* ctx, const h2agg_circuit_proofs* circuits, si
  * slow call spent its time in); costs a few clock reads per call.  Owned by the context, valid until its next call.
  * After an h2agg_kzg_multiopen* call it is that call's split instead, from events on the context's stream:
  * " combine=ms divide=ms commit=ms" — the linear combinations, the up- and down-sweep over all groups, and the batch MSM with
- * the conversion to affine (this one includes the host's wait between the two). */
+ * the conversion to affine (this one includes the host's wait between the two).
+ * After an h2agg_quotient* call it is that call's split, also from events on the stream and summed over the cosets:
+ * " forward=ms gates=ms permutation=ms lookups=ms inverse=ms". */
 const char* h2agg_last_phases(h2agg_ctx* ctx);
 
 /* ---- multi-GPU exchange -----------------------------------------------------------
@@ -712,6 +714,80 @@ int h2agg_lookup_permute_device(h2agg_ctx* ctx, const void* d_a, const void* d_s
 int h2agg_fr_columns_compress(h2agg_ctx* ctx, const uint8_t* cols, size_t m, unsigned k, const uint8_t theta[32], uint8_t* out);
 int h2agg_fr_columns_compress_device(h2agg_ctx* ctx, const void* d_cols, size_t m, unsigned k, const uint8_t theta[32], void* d_out);
 
+/* ---- Quotient polynomial h(X): a key's expressions on every row, and the quotient from the verifying key ---------------------
+ * Stand for: the evaluation of h(X) in halo2_proofs' create_proof (evaluate_h, coeff_to_extended, extended_to_coeff) — recalled
+ * from upstream, not pinned, like the blocks above; what the entry points compute is this definition.  Which expressions h
+ * has to satisfy, and in which order, IS pinned: halo2-snark-aggregator-api/src/systems/halo2/params.rs:74-224 (gates, then the
+ * permutation argument, then every lookup), permutation.rs:54-136, lookup.rs:34-119, and vanish.rs:18-72 for how the verifier
+ * puts the pieces of h together.
+ *
+ * Elements are canonical 32-byte little-endian Fr; n = 2^k is the key's; columns are slabs [columns][n]:
+ * advice[num_advice_columns][n], fixed[nfixed][n] (nfixed = the key's number of fixed commitments), instance[
+ * num_instance_columns][n]; challenges = num_challenges x 32 bytes.  A slab whose count is zero may be NULL.
+ *
+ * h2agg_vk_expressions_eval — expressions of the key on every row i < n of value slabs.
+ *   which = 0: every gate polynomial in key order (gate by gate, poly by poly); 1: the input expressions of lookup j;
+ *   2: the table expressions of lookup j (j is ignored for which = 0).  The list has m expressions E_0 .. E_{m-1}.
+ *   Leaves: FIXED / ADVICE / INSTANCE(q) reads column queries[q].column of its slab at row (i + queries[q].rotation) mod n —
+ *   the mathematical modulus: negative rotations and |rotation| >= n are legal; CHALLENGE(c) and CONST are scalars; NEG, SUM,
+ *   PRODUCT, SCALED are the field operations.
+ *   fold == NULL: out is [m][n], out[j][i] = E_j(row i).  fold = 32 bytes: out is [n], out[i] = sum_j fold^(m-1-j) E_j(row i)
+ *   (acc * fold + E, the first expression under the highest power): fold = theta on a lookup's lists gives the two compressed
+ *   columns commit_permuted sorts, fold = y on the gates the gates' share of the quotient's numerator.
+ *   The operand stack of an expression (values alive at once while its postfix form runs) may be H2AGG_EXPR_MAX_DEPTH deep;
+ *   a deeper expression is H2AGG_ERR_INVALID from this call (h2agg_vk_create accepts what it always did).
+ *
+ * h2agg_quotient — the pieces of h from polynomials in COEFFICIENT form, n coefficients each, low degree first:
+ *   advice, fixed, instance as above; sigma[P][n] (P = the key's permutation columns), perm_z[n_sets][n] (n_sets =
+ *   ceil(P / chunk_len), chunk_len = degree - 2), lookup_z, lookup_ap, lookup_sp [L][n] each (L = the key's lookups); the
+ *   scalars challenges, theta, beta, gamma, y and delta (as in h2agg_permutation_product the library holds no literal for
+ *   delta).  Output h[degree - 1][n]: the pieces h_0 .. h_{degree-2}.
+ *   Let bf = blinding_factors, u = n - bf - 1; w the root h2agg_fr_fft uses for k; l_i the Lagrange polynomial of row i over
+ *   {w^i}; l_last = l_u, l_blind = l_{u+1} + .. + l_{n-1}, act = 1 - l_last - l_blind; c = chunk_len; a column polynomial p
+ *   at rotation t is p(w^t X).  The list E_0 .. E_{m-1}, as polynomial identities in X:
+ *     gates        every gate polynomial, leaves as above;
+ *     permutation  (only if n_sets > 0)  l_0 (1 - z_0);  l_last (z_last^2 - z_last), z_last the last set's;
+ *                  for i = 1 .. n_sets-1: l_0 (z_i - z_{i-1}(w^u X))   (w^u = w^-(bf+1): the "last" rotation);
+ *                  for every set s over its columns j, g = s c + j, v_g the polynomial of permutation column g:
+ *                  act ( z_s(wX) prod_j (v_g + beta sigma_g + gamma) - z_s(X) prod_j (v_g + delta^g beta X + gamma) );
+ *     per lookup   with A, S the theta-folds of its input / table expressions:  l_0 (1 - z);  l_last (z^2 - z);
+ *                  act ( z(wX)(a' + beta)(s' + gamma) - z(X)(A + beta)(S + gamma) );  l_0 (a' - s');
+ *                  act (a' - s')(a' - a'(w^-1 X)).
+ *   N = sum_i y^(m-1-i) E_i.  e = the smallest integer with 2^(k+e) >= n (degree - 1); w_ext = the root of h2agg_fr_fft for
+ *   k + e (w_ext^(2^e) = w); zeta = the cube root of unity of coeff_to_extended (the `shift = ZETA` of h2agg_fr_fft).
+ *   H = the unique polynomial of degree < 2^(k+e) with H(s) = N(s) / (s^n - 1) at every s = zeta w_ext^j, j < 2^(k+e);
+ *   h_i = the coefficients [i n, (i+1) n) of H, i < degree - 1 (higher ones are dropped, as extended_to_coeff truncates).
+ *   For a satisfied circuit H = N / (X^n - 1) exactly; for any other input it is still this one answer.
+ *   Work memory, kept in the context: one coset's values of every polynomial, nine more columns and the
+ *   extended evaluations — (the number of input polynomials + 9) n + 2^(k+e) elements, not columns x 2^(k+e).
+ *
+ * The plain entry points are synchronous over host buffers (pageable or h2agg_host_alloc); the _device twins take DEVICE
+ * memory and are queued on the context's stream with no synchronisation and no read-back (buffer rules: h2agg_fr_fft_device;
+ * a workspace that has to grow drains the device first).  Outputs must not overlap inputs.  With the debug key "phases" a
+ * quotient call waits for its own events and h2agg_last_phases gives " forward=ms gates=ms permutation=ms lookups=ms
+ * inverse=ms".
+ * Refusals, the context stays usable after each: an unknown `which` or j, k different from the key's (or > 24), a list
+ * without expressions, a null required buffer, an expression deeper than H2AGG_EXPR_MAX_DEPTH; for the quotient also
+ * k + e > 24 and degree < 3 with permutation columns: H2AGG_ERR_INVALID.  A scalar (challenge, fold, theta, beta, gamma, y,
+ * delta, a CONST of the key) >= r: H2AGG_ERR_NONCANONICAL from the call.  A column element >= r: H2AGG_ERR_NONCANONICAL through
+ * the context's device status — from the call for the synchronous entry points, at h2agg_synchronize (or the next
+ * synchronous entry point), once, for the _device twins; outputs are then unspecified.  Out of memory: H2AGG_ERR_NOMEM. */
+#define H2AGG_EXPR_MAX_DEPTH 16
+int h2agg_vk_expressions_eval(h2agg_ctx* ctx, const h2agg_vk* vk, int which, size_t j, unsigned k, const uint8_t* advice,
+                              const uint8_t* fixed, const uint8_t* instance, const uint8_t* challenges, const uint8_t fold[32],
+                              uint8_t* out);
+int h2agg_vk_expressions_eval_device(h2agg_ctx* ctx, const h2agg_vk* vk, int which, size_t j, unsigned k, const void* d_advice,
+                                     const void* d_fixed, const void* d_instance, const uint8_t* challenges, const uint8_t fold[32],
+                                     void* d_out);
+int h2agg_quotient(h2agg_ctx* ctx, const h2agg_vk* vk, const uint8_t* advice, const uint8_t* fixed, const uint8_t* instance,
+                   const uint8_t* sigma, const uint8_t* perm_z, const uint8_t* lookup_z, const uint8_t* lookup_ap,
+                   const uint8_t* lookup_sp, const uint8_t* challenges, const uint8_t theta[32], const uint8_t beta[32],
+                   const uint8_t gamma[32], const uint8_t y[32], const uint8_t delta[32], uint8_t* h);
+int h2agg_quotient_device(h2agg_ctx* ctx, const h2agg_vk* vk, const void* d_advice, const void* d_fixed, const void* d_instance,
+                          const void* d_sigma, const void* d_perm_z, const void* d_lookup_z, const void* d_lookup_ap,
+                          const void* d_lookup_sp, const uint8_t* challenges, const uint8_t theta[32], const uint8_t beta[32],
+                          const uint8_t gamma[32], const uint8_t y[32], const uint8_t delta[32], void* d_h);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
@@ -772,7 +848,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         for the pairing's second Miller loop, and waits only for the element streams in front of the sponges
  *                         (default 1; 0: the three latency measures of round 6 off, for an A/B)
  *       "phases" 0|1      keep every aggregation call's wall-clock split, and every h2agg_kzg_multiopen* call's split by events
- *                         (combine / divide / commit), for h2agg_last_phases
+ *                         (combine / divide / commit) and every h2agg_quotient* call's (forward / gates / permutation / lookups /
+ *                         inverse; the queued form then waits for its own events), for h2agg_last_phases
  *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
  *                         1024 elements then run the multi-pass paths
  *       "fr_poly_chunk" t the KZG opening kernels cut a polynomial into chunks of 2^t coefficients per workgroup, 3 .. 11 (0 = the
