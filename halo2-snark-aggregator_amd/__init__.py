@@ -140,6 +140,8 @@ def load_library():
         "h2agg_verify_aggregation_ex": (i32, [ctxp, vp, sz, u8p, u8p, vp, vp, vp, C.POINTER(i32), vp, sz]),
         "h2agg_verify_aggregation_sharded": (i32, [ctxp, vp, sz, vp, u8p, u8p, vp, vp, vp, C.POINTER(i32), vp, sz]),   # see verifier.py
         "h2agg_debug_configure": (i32, [ctxp, C.c_char_p, i32]),
+        "h2agg_debug_lean_variant": (i32, [i32, i32]),
+        "h2agg_debug_table_identity": (i32, [ctxp, u64, C.POINTER(i32), C.POINTER(i32)]),
         "h2agg_verify_proofs": (i32, [ctxp, vp, sz, u8p, u8p, vp, vp, C.POINTER(C.c_int32), C.POINTER(i32), vp, sz]),
         "h2agg_verify_plan_stats": (i32, [ctxp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "h2agg_last_phases": (C.c_char_p, [ctxp]),
@@ -955,6 +957,18 @@ class H2Agg:
     def debug_configure(self, key: str, value: int):
         """h2agg_debug_configure: per-context test hooks (include/h2agg.h "Environment")"""
         self._check(self._lib.h2agg_debug_configure(self._ctx, key.encode(), int(value)))
+
+    def table_may_hold_identity(self, handle: int) -> bool:
+        """False when the call that wrote the table stored no identity base (the bucket accumulation then skips the test)"""
+        v = C.c_int32(-1)
+        self._check(self._lib.h2agg_debug_table_identity(self._ctx, handle, C.byref(v), None))
+        return bool(v.value)
+
+    def last_lean_variant(self) -> int:
+        """the per-entry decisions the last bucket accumulation kept: 1 = identity test, 2 = endomorphism select; -1: none yet"""
+        v = C.c_int32(-1)
+        self._check(self._lib.h2agg_debug_table_identity(self._ctx, 0, None, C.byref(v)))
+        return v.value
 
     def msm_set_tail_overlap(self, level: int = 2):
         """0 = off, 1 = only the Horner kernel on a tail stream, 2 = bucket reduction + window sums + Horner"""

@@ -15,7 +15,12 @@ constexpr int BLOCK = 256;
 __global__ void k_flags_roll(uint32_t* flags) {
     flags[2] |= flags[0];
     flags[0] = 0;
+    flags[1] = 0;
 }
+// flags[1], the base-table word of the call in progress: the kernels that write a Montgomery affine base table raise it when
+// they store the identity (0, 0).  Read back by finish(); a table whose creating call left it clear holds no identity base, and
+// the bucket accumulation over it does not test for one (msm_kernels.hpp LEAN_ID).
+#define NOTE_IDENTITY_BASE(flags, is_id) do { if (is_id) atomicOr((flags) + 1, 1u); } while (0)
 
 // ------------------------------------------------------------------ block-wide reductions through LDS
 // SoA layout lds[k * BLOCK + tid] (k = limb index) keeps every ds access conflict-free.
@@ -335,6 +340,7 @@ FP_INLINE void jac_batch_normalise(const uint8_t* __restrict__ in, size_t n, uin
                     oy = fp_from_mont<FqParams>(oy);
                 }
             }
+            if (MONT) NOTE_IDENTITY_BASE(flags, ox.is_zero_int() && oy.is_zero_int());   // (what is stored, whatever z was)
             fp_store<FqParams>(out + 64 * i, ox);
             fp_store<FqParams>(out + 64 * i + 32, oy);
         }
@@ -483,6 +489,7 @@ __global__ void __launch_bounds__(BLOCK) k_bases_to_mont(const uint8_t* __restri
         uint32_t bad = 0;
         G1Affine p = affine_load_canonical(in + 64 * i, bad);
         if (bad) atomicOr(flags, FLAG_NONCANONICAL);
+        NOTE_IDENTITY_BASE(flags, p.is_identity());
         affine_store(out + 64 * i, p);
     }
 }
@@ -503,7 +510,9 @@ __global__ void __launch_bounds__(BLOCK) k_bases_generate(const uint8_t* __restr
         G1Affine g;
         g.x = Fq::one();
         g.y = FQ_DBL(Fq::one());
-        affine_store(out + 64 * i, affine_from_xyzz(g1_scalar_mul(g, s)));
+        const G1Affine o = affine_from_xyzz(g1_scalar_mul(g, s));
+        NOTE_IDENTITY_BASE(flags, o.is_identity());
+        affine_store(out + 64 * i, o);
     }
 }
 

@@ -150,6 +150,43 @@ FP_INLINE Fp<P> fp_neg(const Fp<P>& a) {
     return fp_normalize<P>(x);
 }
 
+// sgn == 0: a - b + KP*m;  sgn == ~0u: KN*m - a - b, in the one carry sweep a subtraction has anyway (a sign that is only
+// ever consumed by a subtraction needs no negation of its own).  REQUIRES value(b) <= KP*m and value(a) + value(b) <= KN*m.
+// bound: max(A + KP, KN).  Per limb -a is ~a + 1; the 1 sits in the constant: (a ^ sgn) + KP_i + (sgn & (KN_i + 1 - KP_i)) - b.
+template <int KP, int KN, class P>
+FP_INLINE Fp<P> fp_sub_sgn(const Fp<P>& a, uint32_t sgn, const Fp<P>& b) {
+    int32_t x[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i)
+        x[i] = (int32_t)((a.l[i] ^ sgn) + km_limb<P>(KP, i) + (sgn & (km_limb<P>(KN, i) + 1u - km_limb<P>(KP, i)))) - (int32_t)b.l[i];
+    return fp_normalize<P>(x);
+}
+
+// i-th limb of K*m in BORROWED form: every limb below the top one has 2^29 added and the limb above pays for it, so each is
+// >= 2^29 - 1 >= any tight limb and a limb-wise subtraction from it cannot go negative: it needs no carry sweep.
+template <class P>
+constexpr uint32_t km_limb_borrowed(int K, int i) {
+    return km_limb<P>(K, i) + (i < 8 ? (1u << 29) : 0u) - (i > 0 ? 1u : 0u);
+}
+// a - b + K*m and K*m - a WITHOUT the carry sweep: the same integer as fp_sub<K> / fp_neg<K>, in LOOSE limbs (limbs 0..7
+// < 2^29 + 2^30, resp. < 2^30).  Only as an operand of a product block whose 64-bit column bound allows it: the two-product
+// blocks fpa_mul2_ip / fpa_mul2_ip1 with one loose operand per product (tools/fp_column_bounds.py multiplies it out).
+// REQUIRES b (resp. a) tight with value <= (K - 1)*m: the top limb of K*m, less the 1 it lent, covers the top limb of b.
+template <int K, class P>
+FP_INLINE Fp<P> fp_sub_loose(const Fp<P>& a, const Fp<P>& b) {
+    Fp<P> r;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) r.l[i] = a.l[i] + km_limb_borrowed<P>(K, i) - b.l[i];
+    return r;
+}
+template <int K, class P>
+FP_INLINE Fp<P> fp_neg_loose(const Fp<P>& a) {
+    Fp<P> r;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) r.l[i] = km_limb_borrowed<P>(K, i) - a.l[i];
+    return r;
+}
+
 // Montgomery reduction of an 18-column accumulator (columns < 2^63) -> tight limbs, value < (T/R + 1)*m
 template <class P>
 FP_INLINE Fp<P> fp_mont_reduce(uint64_t (&acc)[18]) {

@@ -90,6 +90,9 @@ struct Table {
     uint8_t* d = nullptr;       // Montgomery affine, 64 B / point
     uint8_t* endo_x = nullptr;  // beta * x, 32 B / point (made on the first GLV MSM over this table)
     size_t n = 0;
+    // the call that wrote the table stored no identity base (flags[1], batch_kernels.hpp): MSMs over it take the bucket
+    // accumulation without the per-entry identity test.  false = not known: "may hold one" (msm_lean_variant)
+    bool no_identity = false;
     // fixed-base levels (h2agg_bases_precompute): pre[(w * n + i) * 64] = 2^(pre_c * w) * P_i, w < pre_W
     uint8_t* pre = nullptr;
     int pre_c = 0, pre_W = 0;
@@ -176,6 +179,9 @@ struct h2agg_ctx {
 
     // h2agg_debug_configure: test hooks read per call (chained host-buffer slices, comb route, plan cache)
     int dbg_pcie_slices = 0, dbg_pcie_glv = 0, dbg_pcie_chain = 1, dbg_comb_msm = 1, dbg_plan_cache = 1, dbg_small_sort = 1, dbg_eval_split = 1, dbg_pre_big = 0, dbg_lean_acc = 1, dbg_shard_fail = 0, dbg_shard_calls = 0, dbg_phases = 0, dbg_tape_lds = 1, dbg_prewake = 1;
+    int dbg_lean_full = 0;                  // 1: every bucket accumulation takes the instantiation for any table / any plan
+    uint32_t table_word = 0;                // flags[1] as the last finish() read it: the creating call stored an identity base
+    int last_lean_variant = -1;             // VAR of the last lean accumulation launched (h2agg_debug_table_identity)
     int dbg_seg_chunk = 0, dbg_seg_c = 0;   // segmented multi_exp: points per set of launches (0 = automatic), window bits (0 = default)
     DevBuf seg_wsum, seg_dev, seg_out;      // segmented multi_exp: window sums, segment offsets, results (csrc/seg_msm.inc)
     // G1 FFT (csrc/params.inc): ladder records of w_K^t, t < 2^(K-1), per direction (0 forward, 1 inverse) for the largest K asked
@@ -342,6 +348,7 @@ int finish(h2agg_ctx* c, uint32_t host_flags = 0) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     uint32_t f[3];
     memcpy(f, c->h_pinned + 2048, 12);
+    c->table_word = f[1];   // (the base-table word of the call that ends here: h2agg_bases_upload and its kin)
     f[0] |= host_flags;
     if (f[0] | f[2]) HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 12, c->stream));   // reported once, here
     if (f[0]) return flags_to_status(c, f[0], false);
@@ -615,8 +622,35 @@ bool fb_sort_knobs_clear(const h2agg_ctx* c) {
     return !c->cfg_no_dm && !c->cfg_no_stage && !c->cfg_stage_l1 && !c->cfg_sub_bits && !c->cfg_tile && !c->cfg_seg;
 }
 
+// Which instantiation of the lean bucket accumulation a call takes (msm_kernels.hpp VAR): the identity test stays unless the
+// table is KNOWN to hold none, the endomorphism select stays when the plan splits scalars.  Pure: h2agg_debug_lean_variant.
+int msm_lean_variant(bool table_no_identity, bool plan_glv) {
+    return (table_no_identity ? 0 : LEAN_ID) | (plan_glv ? LEAN_ENDO : 0);
+}
+// what the creating call's base-table word says about the table it wrote (word: flags[1] as finish() read it)
+bool table_word_clear(uint32_t word) { return word == 0; }
+
+using AccLeanKernel = decltype(&k_msm_accumulate_lean<0, true>);
+template <bool DUAL>
+AccLeanKernel acc_lean_kernel(int chain, int var) {
+    const int ch = chain == CHAIN_FIRST ? 1 : (chain == CHAIN_MID || chain == CHAIN_LAST) ? 2 : 0;
+#define ACC_LEAN_ROW(CH)                                                                                      \
+    case CH:                                                                                                   \
+        return var == 0 ? k_msm_accumulate_lean_v<CH, DUAL, 0> : var == LEAN_ID ? k_msm_accumulate_lean_v<CH, DUAL, LEAN_ID> \
+             : var == LEAN_ENDO ? k_msm_accumulate_lean_v<CH, DUAL, LEAN_ENDO> : k_msm_accumulate_lean<CH, DUAL>;
+    switch (ch) {
+        ACC_LEAN_ROW(1)
+        ACC_LEAN_ROW(2)
+        default:
+        ACC_LEAN_ROW(0)
+    }
+#undef ACC_LEAN_ROW
+}
+
+// no_identity: the table d_bases points into is known to hold no identity base (Table::no_identity)
 int msm_run(h2agg_ctx* c, const uint8_t* d_bases, const uint8_t* d_scalars, size_t n_base, uint8_t* d_out_jac,
-            uint32_t batch = 1, const uint8_t* d_endo_x = nullptr, const PreTable* pre = nullptr, uint32_t split = 0) {
+            uint32_t batch = 1, const uint8_t* d_endo_x = nullptr, const PreTable* pre = nullptr, uint32_t split = 0,
+            bool no_identity = false) {
     if (split) batch = 2;
     const size_t n = split ? n_base : n_base * batch;   // scalars
     crumb((uintptr_t)__builtin_return_address(0), ((uint64_t)batch << 40) | n_base);
@@ -1006,11 +1040,13 @@ int msm_run(h2agg_ctx* c, const uint8_t* d_bases, const uint8_t* d_scalars, size
         if (lean) {   // 128 VGPRs, four waves per SIMD; exceptional cases go to fix_list (msm_kernels.hpp)
 #ifdef H2AGG_MEASURE_KNOBS   // (one chain per product instead of two in lock step: an A/B variant, not in the shipped library)
             static const bool lean_dual = !(knob("H2AGG_ACC") && !strcmp(knob("H2AGG_ACC"), "lean1"));
-            auto kacc = lean_dual ? (chain == CHAIN_FIRST ? k_msm_accumulate_lean<1, true> : (chain == CHAIN_MID || chain == CHAIN_LAST) ? k_msm_accumulate_lean<2, true> : k_msm_accumulate_lean<0, true>)
-                                  : (chain == CHAIN_FIRST ? k_msm_accumulate_lean<1, false> : (chain == CHAIN_MID || chain == CHAIN_LAST) ? k_msm_accumulate_lean<2, false> : k_msm_accumulate_lean<0, false>);
+            const int var = msm_lean_variant(no_identity && !c->dbg_lean_full, p.glv || c->dbg_lean_full);
+            auto kacc = lean_dual ? acc_lean_kernel<true>(chain, var) : acc_lean_kernel<false>(chain, var);
 #else
-            auto kacc = chain == CHAIN_FIRST ? k_msm_accumulate_lean<1, true> : (chain == CHAIN_MID || chain == CHAIN_LAST) ? k_msm_accumulate_lean<2, true> : k_msm_accumulate_lean<0, true>;
+            const int var = msm_lean_variant(no_identity && !c->dbg_lean_full, p.glv || c->dbg_lean_full);
+            auto kacc = acc_lean_kernel<true>(chain, var);
 #endif
+            c->last_lean_variant = var;
             hipLaunchKernelGGL(kacc, dim3((unsigned)(((size_t)p.NBT * lpb + 63) / 64)), dim3(64), (size_t)acc_lds,
                                st, d_bases, d_endo_x, entries, offs, hist, ordered ? order : (uint32_t*)nullptr, p.NBT, p.big, lpb, acc_out,
                                big_list, big_keys, big_count, fix_list);
@@ -1703,6 +1739,7 @@ int h2agg_bases_upload(h2agg_ctx* c, const uint8_t* bases, size_t n, uint64_t* h
         hipFree(t.d);
         return rc;
     }
+    t.no_identity = table_word_clear(c->table_word);
     uint64_t h = c->next_handle++;
     c->tables[h] = t;
     *handle_out = h;
@@ -1755,6 +1792,7 @@ int h2agg_bases_generate(h2agg_ctx* c, const void* d_k, size_t n, uint64_t* hand
         hipFree(t.d);
         return rc;
     }
+    t.no_identity = table_word_clear(c->table_word);
     uint64_t h = c->next_handle++;
     c->tables[h] = t;
     *handle_out = h;
@@ -1947,7 +1985,8 @@ int h2agg_g1_msm_device_async(h2agg_ctx* c, uint64_t handle, const void* d_scala
             return msm_run(c, it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac, 1, nullptr, &pt);
     }
     const size_t SLICE = (size_t)1 << 22;
-    if (n <= SLICE) return msm_run(c, it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac, 1, endo);
+    const bool no_id = it->second.no_identity;
+    if (n <= SLICE) return msm_run(c, it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac, 1, endo, nullptr, 0, no_id);
     // The slices share ONE bucket set (chain modes of msm_run): every slice adds its points to the sums the buckets already
     // hold, and only the last one is followed by the bucket reduction / window sums / Horner tail.
     const size_t nsl = (n + SLICE - 1) / SLICE;
@@ -1961,7 +2000,8 @@ int h2agg_g1_msm_device_async(h2agg_ctx* c, uint64_t handle, const void* d_scala
     for (size_t k = 0; k < nsl && rc == H2AGG_OK; ++k) {
         const size_t off = k * SLICE, m = n - off < SLICE ? n - off : SLICE;
         c->chain = k == 0 ? CHAIN_FIRST : (k + 1 == nsl ? CHAIN_LAST : CHAIN_MID);
-        rc = msm_run(c, it->second.d + 64 * off, (const uint8_t*)d_scalars + 32 * off, m, (uint8_t*)d_out_jac, 1, endo + 32 * off);
+        rc = msm_run(c, it->second.d + 64 * off, (const uint8_t*)d_scalars + 32 * off, m, (uint8_t*)d_out_jac, 1, endo + 32 * off,
+                     nullptr, 0, no_id);
     }
     c->chain = CHAIN_OFF;
     c->tail_overlap = was_overlap;
@@ -2024,7 +2064,7 @@ int h2agg_g1_msm_device_batch_async(h2agg_ctx* c, uint64_t handle, const void* d
     for (size_t q = 0; q < batch && rc == H2AGG_OK; q += per) {
         const size_t b = batch - q < per ? batch - q : per;
         rc = msm_run(c, it->second.d, (const uint8_t*)d_scalars + 32 * n * q, n, (uint8_t*)d_out_jac + 96 * q, (uint32_t)b,
-                     use_pre ? nullptr : endo, use_pre ? &pt : nullptr);
+                     use_pre ? nullptr : endo, use_pre ? &pt : nullptr, 0, !use_pre && it->second.no_identity);
     }
     c->tail_overlap = was_overlap;
     c->overlap_level = was_level;
@@ -2376,8 +2416,26 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         if (value != 0 && (value < (int)LK_TILE_LOG_MIN || value > (int)LK_TILE_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_sort_tile must be 0 or 4 .. 11");
         c->dbg_fr_sort_tile = value;
     }
+    else if (k == "lean_full") c->dbg_lean_full = value;     // 1: the bucket accumulation keeps its identity test and endomorphism select whatever the table / plan
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
+    return H2AGG_OK;
+} catch (...) {
+    return H2AGG_ERR_INVALID;
+}
+
+int h2agg_debug_lean_variant(int table_no_identity, int plan_glv) {
+    return msm_lean_variant(table_no_identity != 0, plan_glv != 0);
+}
+
+int h2agg_debug_table_identity(h2agg_ctx* c, uint64_t handle, int* may_hold_out, int* last_variant_out) try {
+    TRY(bind(c));
+    if (may_hold_out) {
+        auto it = c->tables.find(handle);
+        if (it == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown base-table handle");
+        *may_hold_out = it->second.no_identity ? 0 : 1;
+    }
+    if (last_variant_out) *last_variant_out = c->last_lean_variant;
     return H2AGG_OK;
 } catch (...) {
     return H2AGG_ERR_INVALID;

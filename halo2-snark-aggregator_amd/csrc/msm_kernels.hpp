@@ -182,38 +182,53 @@ __global__ void __launch_bounds__(BLOCK) k_msm_accumulate(const uint8_t* __restr
 // fix_list and leaves; k_msm_accumulate_fix finishes those buckets with the general formulas.  For uniform scalars the
 // list holds the filter's false positives: ~10 * 2^-58 per insertion (two limbs), i.e. it is empty.
 struct RawPt { uint4 a, b, c, d; };   // x (a, b) || y (c, d) as loaded: 16 registers while the gather is in flight
+// What an instantiation still has to decide per insertion (VAR, a bit set).  Both are properties of the call, not of the entry:
+//   LEAN_ID    the table may hold the identity (0, 0): every base is tested.  A table whose creating kernel saw none
+//              (h2agg.hip Table::no_identity) takes an instantiation without the test.
+//   LEAN_ENDO  the plan has endomorphism entries (GLV): the x column is chosen per entry.  A plain plan has none.
+// k_msm_accumulate_lean<CHAIN, DUAL> is VAR = LEAN_ID | LEAN_ENDO (any table, any plan); k_msm_accumulate_lean_v carries the rest.
+constexpr int LEAN_ID = 1, LEAN_ENDO = 2;
+template <int VAR>
 FP_INLINE RawPt raw_gather(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ endo_x, uint32_t e) {
     const size_t idx = e & ENT_IDX;
-    const uint4* px = reinterpret_cast<const uint4*>((e & ENT_ENDO) ? endo_x + 32 * idx : bases + 64 * idx);
+    const uint4* px = reinterpret_cast<const uint4*>(((VAR & LEAN_ENDO) && (e & ENT_ENDO)) ? endo_x + 32 * idx : bases + 64 * idx);
     const uint4* py = reinterpret_cast<const uint4*>(bases + 64 * idx + 32);
     RawPt r;
     r.a = px[0]; r.b = px[1]; r.c = py[0]; r.d = py[1];
     return r;
 }
-FP_INLINE G1Affine raw_unpack(const RawPt& r, uint32_t e) {
+// the base as stored: the entry's sign is NOT applied here (it costs a negation, a carry sweep and a nine-way select in front of
+// S2 = Y2 * ZZZ1); its only consumer is r = +-S2 - Y1, formed by fp_sub_sgn in the sweep that subtraction has anyway
+FP_INLINE G1Affine raw_unpack(const RawPt& r) {
     G1Affine p;
     { uint32_t w[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w}; p.x = fp_unpack<FqParams>(w); }
     { uint32_t w[8] = {r.c.x, r.c.y, r.c.z, r.c.w, r.d.x, r.d.y, r.d.z, r.d.w}; p.y = fp_unpack<FqParams>(w); }
-    return (e & ENT_NEG) ? affine_neg(p) : p;
+    return p;
 }
-// acc += q (madd-2008-s, same bounds as xyzz_add_affine).  Returns false, acc untouched, when the general formula is
-// needed.  issue_next() starts the gather of the following entry (16 registers while in flight) at the point of the formula where
-// the fewest values are alive: behind (PPP, Q), with the last four products still to come.  (Measured alternative: the gather as
-// LDS-DMA, global_load_lds_dwordx4 into a per-wave stage, a whole addition ahead and no registers at all — 1 102 us per 2^20-point
-// launch against 1 076: the lead is not what bounds the kernel.)
+FP_INLINE uint32_t ent_sign(uint32_t e) {   // 0 or ~0u
+    static_assert(ENT_NEG == 0x80000000u, "the sign is the entry's top bit");
+    return (uint32_t)((int32_t)e >> 31);
+}
+// acc += +-q (madd-2008-s, same bounds as xyzz_add_affine); sgn = ent_sign(entry), q unsigned as stored, acc NOT the identity
+// (the caller's loop starts from a point, and ZZ3 = ZZ1 * PP with P != 0 stays one).  Returns false, acc untouched, when the
+// general formula is needed.  issue_next() starts the gather of the following entry (16 registers while in flight) at the point of
+// the formula where the fewest values are alive: behind (PPP, Q), with the last four products still to come.  (Measured
+// alternative: the gather as LDS-DMA, global_load_lds_dwordx4 into a per-wave stage, a whole addition ahead and no registers at
+// all — 1 102 us per 2^20-point launch against 1 076: the lead is not what bounds the kernel.)
 // DUAL: independent products as two chains in lock step (no dependent back-to-back multiply-adds: what three waves per SIMD
 // need); otherwise one chain per product (fewest temporaries; four waves per SIMD hide the dependent issue).
-template <bool DUAL, class NextF>
-FP_INLINE bool xyzz_add_affine_lean(G1XYZZ& acc, G1Affine q, NextF&& issue_next) {
-    bool ok = !q.is_identity() && !acc.is_identity();
+template <bool DUAL, int VAR, class NextF>
+FP_INLINE bool xyzz_add_affine_lean(G1XYZZ& acc, G1Affine q, uint32_t sgn, NextF&& issue_next) {
+    bool ok = true;
+    if (VAR & LEAN_ID) ok = !q.is_identity();
     if (DUAL) {
-        fpa_mul_dual_ip<FqParams>(q.x, acc.zz, q.y, acc.zzz);   // U2 [2], S2 [2]
+        fpa_mul_dual_ip<FqParams>(q.x, acc.zz, q.y, acc.zzz);   // U2 [2], |S2| [2]
     } else {
         fpa_mul_ip<FqParams>(q.x, acc.zz);
         fpa_mul_ip<FqParams>(q.y, acc.zzz);
     }
     Fq p = FQ_SUB(8, q.x, acc.x);                        // [10]
-    Fq r = FQ_SUB(4, q.y, acc.y);                        // [6]
+    Fq r = fp_sub_sgn<4, 6, FqParams>(q.y, sgn, acc.y);  // S2 - Y1 + 4p, or 6p - |S2| - Y1: [6]
     ok = ok && !fp_maybe_zero_mod2<10, FqParams>(p);
     if (!ok) return false;
     Fq pp, rr;
@@ -227,13 +242,14 @@ FP_INLINE bool xyzz_add_affine_lean(G1XYZZ& acc, G1Affine q, NextF&& issue_next)
         fpa_mul_ip<FqParams>(acc.x, pp);
     }
     Fq x3 = fp_sub_sub2<6, FqParams>(rr, p, acc.x);      // PPP + 2Q [6] -> [8]
-    Fq d = FQ_SUB(8, acc.x, x3);                         // Q - X3 [10]
+    // the two operands that only feed the last block stay loose (no carry sweep): its columns have the room (fp.hpp fp_sub_loose)
+    Fq d = fp_sub_loose<10, FqParams>(acc.x, x3);        // Q - X3 [12], X3 <= 9p
     acc.x = x3;
-    Fq ny = fp_neg<4, FqParams>(acc.y);                  // [4]
+    Fq ny = fp_neg_loose<8, FqParams>(acc.y);            // [8], Y1 <= [4]
     if (DUAL) {
         fpa_mul_dual_ip<FqParams>(acc.zz, pp, acc.zzz, p);   // [2], [2]
         issue_next();
-        fpa_mul2_ip<FqParams>(ny, p, r, d);              // (4p - Y1)*PPP + R*(Q - X3): (4*2 + 6*10)/169 + 1 -> [2]
+        fpa_mul2_ip<FqParams>(ny, p, r, d);              // (8p - Y1)*PPP + R*(Q - X3): (8*2 + 6*12)/169 + 1 -> [2]
     } else {
         fpa_mul_ip<FqParams>(acc.zz, pp);
         fpa_mul_ip<FqParams>(acc.zzz, p);
@@ -242,12 +258,13 @@ FP_INLINE bool xyzz_add_affine_lean(G1XYZZ& acc, G1Affine q, NextF&& issue_next)
     acc.y = ny;
     return true;
 }
-// a + q for two affine points (mmadd-2008-s, 4M + 2S): the second point of a bucket.  Same contract as above.
-template <bool DUAL>
-FP_INLINE bool xyzz_add_affine_affine_lean(G1XYZZ& o, const G1Affine& a, const G1Affine& q) {
+// a +- q for two affine points (mmadd-2008-s, 4M + 2S): the second point of a bucket.  a: its sign applied; q: as stored, with
+// sgn.  Same contract as above.
+template <bool DUAL, int VAR>
+FP_INLINE bool xyzz_add_affine_affine_lean(G1XYZZ& o, const G1Affine& a, const G1Affine& q, uint32_t sgn) {
     Fq p = FQ_SUB(2, q.x, a.x);                          // [4]
-    Fq r = FQ_SUB(2, q.y, a.y);                          // [4]
-    if (q.is_identity() || fp_maybe_zero_mod2<4, FqParams>(p)) return false;
+    Fq r = fp_sub_sgn<2, 4, FqParams>(q.y, sgn, a.y);    // y2 - y1 + 2p, or 4p - |y2| - y1: [4]
+    if (((VAR & LEAN_ID) && q.is_identity()) || fp_maybe_zero_mod2<4, FqParams>(p)) return false;
     Fq pp, rr;
     Fq qq = a.x;
     if (DUAL) {
@@ -260,9 +277,9 @@ FP_INLINE bool xyzz_add_affine_affine_lean(G1XYZZ& o, const G1Affine& a, const G
         fpa_mul_ip<FqParams>(qq, pp);
     }
     o.x = fp_sub_sub2<6, FqParams>(rr, p, qq);           // [8]
-    Fq d = FQ_SUB(8, qq, o.x);                           // [10]
-    Fq ny = fp_neg<2, FqParams>(a.y);                    // [2]
-    if (DUAL) fpa_mul2_ip<FqParams>(ny, p, r, d);        // (2*2 + 4*10)/169 + 1 -> [2]
+    Fq d = fp_sub_loose<10, FqParams>(qq, o.x);          // [12], loose
+    Fq ny = fp_neg_loose<4, FqParams>(a.y);              // [4], loose; y1 <= [2]
+    if (DUAL) fpa_mul2_ip<FqParams>(ny, p, r, d);        // (4*2 + 4*12)/169 + 1 -> [2]
     else fpa_mul2_ip1<FqParams>(ny, p, r, d);
     o.y = ny;
     o.zz = pp;
@@ -271,13 +288,13 @@ FP_INLINE bool xyzz_add_affine_affine_lean(G1XYZZ& o, const G1Affine& a, const G
 }
 
 // Same contract as k_msm_accumulate<CHAIN>; counters[2] counts fix_list's {slot, first unfinished entry} pairs.
-template <int CHAIN, bool DUAL>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_msm_accumulate_lean(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ endo_x,
-                      const uint32_t* __restrict__ entries, const uint32_t* __restrict__ offs,
-                      const uint32_t* __restrict__ hist, const uint32_t* __restrict__ order, uint32_t nbt, uint32_t big,
-                      uint32_t lpb, uint8_t* __restrict__ buckets, uint32_t* __restrict__ big_list,
-                      uint32_t* __restrict__ big_keys, uint32_t* __restrict__ counters, uint32_t* __restrict__ fix_list) {
+template <int CHAIN, bool DUAL, int VAR>
+FP_INLINE void msm_accumulate_lean_body(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ endo_x,
+                                        const uint32_t* __restrict__ entries, const uint32_t* __restrict__ offs,
+                                        const uint32_t* __restrict__ hist, const uint32_t* __restrict__ order, uint32_t nbt,
+                                        uint32_t big, uint32_t lpb, uint8_t* __restrict__ buckets,
+                                        uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_keys,
+                                        uint32_t* __restrict__ counters, uint32_t* __restrict__ fix_list) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nbt * lpb) return;
     const uint32_t part = t % lpb;
@@ -317,25 +334,28 @@ k_msm_accumulate_lean(const uint8_t* __restrict__ bases, const uint8_t* __restri
     uint32_t k = lo;
     if (hi > lo) {
         uint32_t e_cur = run(lo);
-        RawPt nxt = raw_gather(bases, endo_x, e_cur);
+        RawPt nxt = raw_gather<VAR>(bases, endo_x, e_cur);
         uint32_t e_nxt = run(lo + 1 < hi ? lo + 1 : hi - 1);
         auto advance = [&](uint32_t k_now) {   // gather entry k_now + 1 (past the end: the last entry again, unused), fetch the index of entry k_now + 2
             e_cur = e_nxt;
-            nxt = raw_gather(bases, endo_x, e_nxt);
-            e_nxt = run(k_now + 2 < hi ? k_now + 2 : hi - 1);
+            nxt = raw_gather<VAR>(bases, endo_x, e_nxt);
+            e_nxt = run(k_now + 2 < hi ? k_now + 2 : hi - 1);   // (the clamp keeps the prefetch inside the run, whatever lies behind it)
         };
         bool go = true;
-        if (acc.is_identity()) {   // the first point of a bucket is a copy, the second an affine + affine addition (4M + 2S)
-            const G1Affine first = raw_unpack(nxt, e_cur);
-            go = !first.is_identity();
+        // (the only accumulator that can be the identity is one a later slice loads: decided here, once, not per insertion)
+        if (CHAIN != 2 || acc.is_identity()) {   // the first point of a bucket is a copy, the second an affine + affine addition (4M + 2S)
+            G1Affine first = raw_unpack(nxt);
+            go = !first.is_identity();   // (every instantiation: once per bucket, and from_affine needs it)
             if (go) {
+                if (e_cur & ENT_NEG) first.y = fp_neg<2, FqParams>(first.y);
                 advance(lo);
                 k = lo + 1;
                 acc = G1XYZZ::from_affine(first);
                 if (k < hi) {
-                    const G1Affine second = raw_unpack(nxt, e_cur);
+                    const G1Affine second = raw_unpack(nxt);
+                    const uint32_t sgn = ent_sign(e_cur);
                     advance(lo + 1);
-                    go = xyzz_add_affine_affine_lean<DUAL>(acc, first, second);
+                    go = xyzz_add_affine_affine_lean<DUAL, VAR>(acc, first, second, sgn);
                     if (go) k = lo + 2;
                 }
             }
@@ -343,8 +363,9 @@ k_msm_accumulate_lean(const uint8_t* __restrict__ bases, const uint8_t* __restri
         if (go) {
 #pragma unroll 1
             for (; k < hi; ++k) {
-                const G1Affine cur = raw_unpack(nxt, e_cur);
-                if (!xyzz_add_affine_lean<DUAL>(acc, cur, [&]() { advance(k); })) break;
+                const G1Affine cur = raw_unpack(nxt);
+                const uint32_t sgn = ent_sign(e_cur);
+                if (!xyzz_add_affine_lean<DUAL, VAR>(acc, cur, sgn, [&]() { advance(k); })) break;
             }
         }
         if (k < hi) {
@@ -357,6 +378,25 @@ k_msm_accumulate_lean(const uint8_t* __restrict__ bases, const uint8_t* __restri
     asm volatile("" : "+v"(oslot));   // (keeps the 64-bit store address out of the loop's live set)
     xyzz_store(buckets + XYZZ_BYTES * (size_t)oslot, acc);
 }
+#define MSM_ACC_LEAN_PARAMS                                                                                              \
+    const uint8_t *__restrict__ bases, const uint8_t *__restrict__ endo_x, const uint32_t *__restrict__ entries,         \
+        const uint32_t *__restrict__ offs, const uint32_t *__restrict__ hist, const uint32_t *__restrict__ order,        \
+        uint32_t nbt, uint32_t big, uint32_t lpb, uint8_t *__restrict__ buckets, uint32_t *__restrict__ big_list,        \
+        uint32_t *__restrict__ big_keys, uint32_t *__restrict__ counters, uint32_t *__restrict__ fix_list
+#define MSM_ACC_LEAN_ARGS bases, endo_x, entries, offs, hist, order, nbt, big, lpb, buckets, big_list, big_keys, counters, fix_list
+// any table, any plan
+template <int CHAIN, bool DUAL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_msm_accumulate_lean(MSM_ACC_LEAN_PARAMS) {
+    msm_accumulate_lean_body<CHAIN, DUAL, LEAN_ID | LEAN_ENDO>(MSM_ACC_LEAN_ARGS);
+}
+// VAR < LEAN_ID | LEAN_ENDO: a table known to hold no identity and / or a plan without endomorphism entries
+template <int CHAIN, bool DUAL, int VAR>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_msm_accumulate_lean_v(MSM_ACC_LEAN_PARAMS) {
+    static_assert(VAR >= 0 && VAR < (LEAN_ID | LEAN_ENDO), "the full set is k_msm_accumulate_lean");
+    msm_accumulate_lean_body<CHAIN, DUAL, VAR>(MSM_ACC_LEAN_ARGS);
+}
+#undef MSM_ACC_LEAN_PARAMS
+#undef MSM_ACC_LEAN_ARGS
 // the buckets the lean kernel left unfinished, with the general formulas: one lane per list entry, from entry k on
 __global__ void __launch_bounds__(64) k_msm_accumulate_fix(const uint8_t* __restrict__ bases, const uint8_t* __restrict__ endo_x,
                                                            const uint32_t* __restrict__ entries,

@@ -157,6 +157,7 @@ int h2agg_bases_fft(h2agg_ctx* c, uint64_t in_handle, unsigned k, int inverse, u
         hipFree(t.d);
         return rc;
     }
+    t.no_identity = table_word_clear(c->table_word);
     const uint64_t h = c->next_handle++;
     c->tables[h] = t;
     *out_handle = h;
@@ -194,6 +195,7 @@ int h2agg_params_setup(h2agg_ctx* c, unsigned k, const uint8_t s[32], uint64_t* 
         if (tl.d) hipFree(tl.d);
         return rc;
     }
+    tg.no_identity = tl.no_identity = table_word_clear(c->table_word);   // (one word for the two tables of the call)
     if (tg.d) {
         const uint64_t h = c->next_handle++;
         c->tables[h] = tg;

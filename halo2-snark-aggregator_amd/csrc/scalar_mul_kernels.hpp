@@ -212,7 +212,9 @@ __global__ void __launch_bounds__(BLOCK) k_bases_generate_comb(const uint8_t* __
             const uint32_t d = (s.w[w >> 2] >> (8 * (w & 3))) & 0xffu;
             if (d) xyzz_add_affine(acc, affine_load(table + 64 * ((size_t)w * COMB_ROW + d - 1)));
         }
-        affine_store(out + 64 * i, affine_from_xyzz(acc));
+        const G1Affine o = affine_from_xyzz(acc);
+        NOTE_IDENTITY_BASE(flags, o.is_identity());
+        affine_store(out + 64 * i, o);
     }
 }
 

@@ -861,6 +861,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         below 11 the step of its row scans, the threads that take keys in its byte histogram (both 2^(t-2))
  *                         and that histogram's grid (2 workgroups) shrink with the tile: at t = 4 inputs of 65 to 1024 rows
  *                         then run every multi-tile path, the step loops of both scans and the histogram's stride loop included
+ *       "lean_full" 0|1   the bucket accumulation keeps its per-entry identity test and endomorphism select for every table
+ *                         and plan (1: A/B and tests of the instantiation for any table)
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
  *       "seg_chunk" n     h2agg_g1_msm_segmented / h2agg_verify_proofs: at most n points per set of launches of the segmented
  *                         multi_exp (0 = automatic, 16384); a segment longer than that is an ordinary multi_exp of its own
@@ -868,6 +870,15 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *       "shard_fail" 0..4  this rank of h2agg_verify_aggregation_sharded fails before (1) / between (2) its exchanges, or inside
  *                         exchange 1 (3) / 2 (4) before its all-gather */
 int h2agg_debug_configure(h2agg_ctx* ctx, const char* key, int value);
+/* The bucket accumulation has one instantiation per (table may hold the identity, plan has endomorphism entries): the two
+ * per-entry decisions it then leaves out are properties of the call (csrc/msm_kernels.hpp LEAN_ID = 1, LEAN_ENDO = 2).
+ * h2agg_debug_lean_variant: the set a call takes, from what is known of its table and plan; needs no device.
+ * h2agg_debug_table_identity: *may_hold_out = 0 when the call that wrote the table (h2agg_bases_upload / _generate / _fft,
+ * h2agg_params_setup) stored no identity base, 1 otherwise ("may hold one": also every table that was not written by one of
+ * them); *last_variant_out = the set of the context's last bucket accumulation, -1 before the first.  Either pointer may be NULL
+ * (handle is only looked up for may_hold_out).  h2agg_debug_configure(ctx, "lean_full", 1) makes every call take the full set. */
+int h2agg_debug_lean_variant(int table_no_identity, int plan_glv);
+int h2agg_debug_table_identity(h2agg_ctx* ctx, uint64_t handle, int* may_hold_out, int* last_variant_out);
 /* Overlap the latency-shaped tail of one MSM (enable = 1: the Horner kernel, one wave; 2: bucket reduction + window
  * sums + Horner; 3: as 2, and the bucket accumulation itself leaves the context's stream, so that the NEXT MSM's sort runs
  * under it — measured: a loss at 2^20 points (1.39 -> 1.55 ms per MSM: both kernels slow each other down), +3 % at 2^22) with the bulk kernels of the next ones: the tail runs on one of three tail streams of the context.  With overlap on, a result written by

@@ -30,12 +30,23 @@ def counters(path, kernel):
     return out
 
 
+def lean_counters(path, var):
+    """the whole-MSM bucket accumulation of a pass (two chains in lock step; <1> / <2>: chained slices): the instantiation for a
+    table without an identity base / a plan without endomorphism entries (k_msm_accumulate_lean_v<0, true, VAR>, csrc/msm_kernels.hpp)
+    that the workload takes, else the one for any table and plan"""
+    for k in ("h2agg::k_msm_accumulate_lean_v<0, true, %d>" % var, "h2agg::k_msm_accumulate_lean<0, true>"):
+        got = counters(path, k)
+        if got:
+            return got
+    raise KeyError("no k_msm_accumulate_lean launch in " + path)
+
+
 def main(prefix):
     import bench
-    k = "h2agg::k_msm_accumulate_lean<0, true>"   # (the whole-MSM instantiation, two chains in lock step; <1> / <2>: chained slices)
-    fetch = counters(prefix + "_pmc_fetch.txt", k)["FETCH_SIZE"]
-    write = counters(prefix + "_pmc_write.txt", k)["WRITE_SIZE"]
-    sq = counters(prefix + "_pmc_sq.txt", k)
+    # (a generated table holds no identity base and the 2^20-point plan has no endomorphism entries: VAR = 0)
+    fetch = lean_counters(prefix + "_pmc_fetch.txt", 0)["FETCH_SIZE"]
+    write = lean_counters(prefix + "_pmc_write.txt", 0)["WRITE_SIZE"]
+    sq = lean_counters(prefix + "_pmc_sq.txt", 0)
     insts, dur_us = sq["SQ_INSTS_VALU"]
     clk_hz = sq["GRBM_GUI_ACTIVE"][0] / 8.0 / (dur_us * 1e-6)          # summed over the 8 XCDs
     n, windows = 1 << 20, 16
@@ -57,7 +68,7 @@ def main(prefix):
                           "alignbit 2: profiles/r01_ubench_instruction_rates.txt, which quotes them at the 2.4 GHz nominal clock; "
                           "at the ~2.03 GHz the part sustains under this load — GRBM_GUI_ACTIVE of this very pass — a multiply-add "
                           "is 4.0 cycles): the 1 467 + 144 + 82 + 20 = 1 713 four-cycle instructions of one insertion (ISA of "
-                          "k_msm_accumulate_lean<0, true>, tools/isa_pressure.py) x 4, the rest of the MEASURED instructions "
+                          "k_msm_accumulate_lean, tools/isa_pressure.py) x 4, the rest of the MEASURED instructions "
                           "per insertion (wave_instructions_per_mixed_add) x 2",
         "source": "%s_pmc_{fetch,write,sq}.txt (rocprofv3 --pmc, separate passes, per-dispatch average, summed over the 8 XCDs)"
                   % os.path.basename(prefix),
@@ -69,9 +80,9 @@ def batch(prefix, log2n=22, nbatch=16):
     with fixed-base levels (tools/fixed_base_big.py 22 --fixed-only under rocprofv3 --pmc: the path bench.py's
     aggregate.config4_share runs on): bytes of the accumulation kernel per launch and per AGGREGATION"""
     import bench
-    k = "h2agg::k_msm_accumulate_lean<0, true>"
-    fetch = counters(prefix + "_pmc_batch_fetch.txt", k)["FETCH_SIZE"]
-    write = counters(prefix + "_pmc_batch_write.txt", k)["WRITE_SIZE"]
+    # (fixed-base levels count as "may hold the identity", and their plan has no endomorphism entries: VAR = 1)
+    fetch = lean_counters(prefix + "_pmc_batch_fetch.txt", 1)["FETCH_SIZE"]
+    write = lean_counters(prefix + "_pmc_batch_write.txt", 1)["WRITE_SIZE"]
     per_launch = (fetch[0] + write[0]) * 1024
     algo = 96.0 * ((1 << log2n) - 6)
     print(json.dumps({
