@@ -24,6 +24,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "scalar_mul_kernels.hpp"
@@ -116,10 +117,99 @@ struct PreTable {   // what msm_run needs of it
     int c, W;
 };
 
+// ---- the plain data of msm_run (csrc/msm_run.inc has the functions; the context below keeps a deferred tail by value)
+// Slices of ONE MSM that share a bucket set (an MSM is a sum over points: the slices' bucket sums just add up, so only
+// the last slice needs the bucket reduction / window sums / Horner tail — one latency chain per MSM instead of one per
+// slice).  CHAIN_FIRST / CHAIN_MID: sort + accumulation only, the tail slot does not rotate; CHAIN_LAST: accumulation
+// on top of what the slot holds, then the tail.
+enum { CHAIN_OFF = 0, CHAIN_FIRST = 1, CHAIN_MID = 2, CHAIN_LAST = 3 };
+
+struct MsmCall {   // the argument of msm_run (described there)
+    const uint8_t* d_bases = nullptr;
+    const uint8_t* d_scalars = nullptr;
+    size_t n_base = 0;
+    uint8_t* d_out_jac = nullptr;
+    uint32_t batch = 1;
+    const uint8_t* d_endo_x = nullptr;
+    const PreTable* pre = nullptr;
+    uint32_t split = 0;
+    bool no_identity = false;
+    int chain = CHAIN_OFF;    // ignored with batch != 1 or fixed-base levels
+    size_t chain_n = 0;       // the point count a chain's plan is made for (every slice the same plan)
+    bool chain_glv = false;   // a chain's endomorphism split
+};
+
+enum class SortKind {
+    SMALL,         // one launch (k_small_sort)
+    FB_LEVELS,     // the (level, point) sort of fixed-base levels at c = 20 (fb_sort_kernels.hpp)
+    DIGIT_MAJOR,   // 16- / 17-bit windows over one table, 2^16 .. 2^22 keys per window (k_dm_*)
+    PACKED,        // two levels over packed (sub-bucket | index) items, level 2 staged in LDS
+    PACKED_L1,     // ... level 1 staged as well (h2agg_msm_configure_sort stage_l1)
+    TWO_ARRAY      // two levels, index and sub-bucket in arrays of their own (the index does not fit the packed item)
+};
+enum class TailKind {
+    FB_GRIDS,   // fixed-base levels: one set of 2^19 buckets as 16 grids
+    R2D7,       // two-dimensional reduction, 16-bit windows
+    R2D8,       // ... 17-bit windows
+    SEGMENTS    // segment sums + window sums
+};
+
+// Every decision of one call (msm_route): a function of the call and of the context's configuration alone.
+struct MsmRoute {
+    int refuse_code;           // != H2AGG_OK: the call is refused with refuse_msg, nothing else is valid
+    const char* refuse_msg;
+    uint32_t batch, split;     // MSMs in the set of launches (a split MSM: 2); the split point or 0
+    int chain;                 // CHAIN_*
+    size_t n_base, n, nent;    // bases; scalars; bucket insertions
+    MsmPlan p;
+    int Wd, W1;                // digit positions per scalar; windows (bucket sets) per MSM
+    uint32_t WT;               // windows in total
+    SortKind sort;
+    SortPlan sp;
+    DmPlan dp;
+    bool dm17;                 // digit-major at c = 17
+    uint32_t dm_nwin, fb_ntile;
+    unsigned ntiles;
+    int idx_bits;
+    size_t tile_counts_bytes;
+    bool glv_here, endo_here;  // this call decomposes its scalars / makes the beta * x column
+    bool ordered;              // buckets are taken in the order of their lengths
+    uint32_t lpb;              // lanes per bucket
+    bool lean, lean_dual;
+    int lean_var;
+    bool big_possible;
+    size_t max_slots, max_keys;
+    TailKind tail;
+    bool par4;
+    uint32_t nseg_total;
+    // streams: the accumulation leaves the context's stream; sort outputs alternate; the over-long-bucket kernels go in front
+    // of the tail; the whole tail / its last chain leaves the accumulation's stream; the tail waits for the next call
+    bool piped, altbuf, tail_big, tails_off_stream, final_off_stream, defer;
+};
+
+// The buffers of one call (msm_bind): sort slot sq, tail slot par, as they were when the call was made.
+struct MsmWorkspace {
+    int sq, par;
+    bool meta_was_clean;
+    uint32_t *meta, *pcount, *pstart, *pcursor, *bin_count, *bin_start, *bin_cursor, *big_count;
+    uint32_t *hist, *offs, *order, *entries, *item_idx, *fb_long, *tile_counts;
+    uint16_t* item_sub;
+    uint32_t *big_list, *big_keys, *fix_list, *ticket;
+    uint8_t *big_part, *acc_out, *buckets, *segsum, *wsum, *res_xyzz;
+    const uint8_t *d_bases, *d_scalars, *d_endo_x;
+    uint8_t* d_out_jac;
+};
+
+struct MsmTailJob {   // a tail that waits for the next call: everything msm_tail needs
+    MsmRoute r;
+    MsmWorkspace w;
+    hipStream_t from;   // the accumulation's stream
+};
+static_assert(std::is_trivially_copyable<MsmTailJob>::value, "a deferred tail is kept and copied as plain data");
+
 }  // namespace
 
 constexpr int MSM_MAX_SLICES = 16;
-enum { CHAIN_OFF = 0, CHAIN_FIRST = 1, CHAIN_MID = 2, CHAIN_LAST = 3 };
 
 struct h2agg_ctx {
     int device = 0;
@@ -231,14 +321,6 @@ struct h2agg_ctx {
     hipEvent_t ev_bulk[TAIL_SLOTS] = {}, ev_tail[TAIL_SLOTS] = {};
     bool tail_pending[TAIL_SLOTS] = {};
     int parity = 0;   // slot of the next MSM
-    // Slices of ONE MSM that share a bucket set (an MSM is a sum over points: the slices' bucket sums just add up, so only
-    // the last slice needs the bucket reduction / window sums / Horner tail — one latency chain per MSM instead of one per
-    // slice).  0 = off; CHAIN_FIRST / CHAIN_MID: sort + accumulation only, the slot does not rotate; CHAIN_LAST: accumulation
-    // on top of what the slot holds, then the tail.  chain_n: the point count the plan is made for (every slice the same
-    // plan); chain_glv: the plan's endomorphism split.
-    int chain = 0;
-    size_t chain_n = 0;
-    bool chain_glv = false;
     // called by msm_run on the stream of the accumulation, behind the sort and in front of the first kernel that reads the
     // bases: the host-buffer MSM waits there for the slice's bases (the sort only needs the scalars, which cross PCIe first)
     std::function<int(hipStream_t)> bases_hook;
@@ -247,7 +329,8 @@ struct h2agg_ctx {
     // Deferred tail (overlap level >= 2): the tail of MSM k is launched from the NEXT MSM's call, behind that MSM's sort —
     // beside the sort it slows the sort's latency chains by 2x, beside the accumulation it only costs its own instructions.
     // Whoever needs the results first (join_tails) launches it at once.
-    std::function<int(bool)> deferred_tail;   // argument: true = wait for the event just recorded behind a sort
+    MsmTailJob deferred_job;      // valid while tail_deferred (flush_deferred_tail)
+    bool tail_deferred = false;
     hipEvent_t ev_sortdone = nullptr;
     hipStream_t acc_stream = nullptr;
     hipEvent_t ev_sorted[2] = {}, ev_accdone[2] = {};
@@ -353,53 +436,6 @@ int finish(h2agg_ctx* c, uint32_t host_flags = 0) {
     if (f[0] | f[2]) HIP_TRY(c, hipMemsetAsync(c->d_flags, 0, 12, c->stream));   // reported once, here
     if (f[0]) return flags_to_status(c, f[0], false);
     return flags_to_status(c, f[2], true);
-}
-
-// bits of the scalar that fall into the top window (a narrow top window means a few huge buckets).
-// plain: 254-bit scalars, W*c >= 255; GLV: 127-bit magnitudes, W*c >= 128
-int window_count(int c, bool glv) { return glv ? (128 + c - 1) / c : (255 + c - 1) / c; }
-int top_window_bits(int c, bool glv) { return (glv ? 127 : 254) - c * (window_count(c, glv) - 1); }
-int choose_window(size_t n, bool glv) {
-    // Measured on MI355X (tools/window_sweep.py, profiles/r01_window_sweep_*.txt).  Two things decide it, and the
-    // classic "log2(n) - 4" rule sees neither: (1) the tail (bucket reduce -> window sums -> Horner) is a serial
-    // chain whose length grows with the number of windows, so below ~2^17 points FEWER, WIDER windows win even
-    // though they leave most buckets empty; (2) only widths whose top window is as sparse as the others
-    // (GLV 8/13/16, plain 8/15/16: top window as sparse as the others) avoid a dense top window that costs as much as all the
-    // other windows together.
-    // (re-measured in round 4 behind the one-launch sort and the limb-parallel Horner chain, profiles/r04_sweeps.txt section 5:
-    // 8 bits up to 2^12 points — 2^11: 0.457 against 0.490 ms alone, 0.194 against 0.250 back to back; 2^12 equal; the two
-    // multi_exps of an evaluation of 4 proofs, 1 750 pairs: 0.68 against 0.76 ms)
-    if (glv) return n <= ((size_t)1 << 12) ? 8 : n <= ((size_t)1 << 14) ? 13 : 16;
-    // 17 bits from 1.5 * 2^20 points on: a bucket costs 2 general additions (~2.8 insertions) whatever the point count, a
-    // window's insertions grow with it — 15 windows of 2^16 buckets overtake 16 of 2^15 between 2^20 points (+0.7 %) and
-    // 2^21 (+5.7 %; 2^22: +8.8 %, profiles/r03_sweeps.txt section 11)
-    return n <= ((size_t)1 << 12) ? 8 : n < ((size_t)1 << 19) ? 15 : n < ((size_t)3 << 19) ? 16 : 17;
-}
-
-MsmPlan make_plan(const h2agg_ctx* c, size_t n, uint32_t batch = 1) {
-    MsmPlan p;
-    // GLV halves the latency-shaped stages (reduction, Horner tail) at the price of the decomposition pass and the
-    // slice-combine pass of the half-as-many buckets: a win whenever those stages are exposed — single-MSM latency
-    // mode, or small / medium MSMs — and a small loss when a large MSM's tail is hidden under the next one's bulk
-    // (profiles/r01_sweeps.txt), or when the tail is a small share anyway.  auto = on unless (overlap mode and n >= 2^20) or
-    // n >= 2^22.
-    p.glv = c->cfg_glv > 0 ||
-            (c->cfg_glv == 0 && !(c->tail_overlap && n >= ((size_t)1 << 20)) && n < ((size_t)1 << 22));
-    p.c = c->cfg_c ? c->cfg_c : choose_window(n, p.glv);
-    p.W = window_count(p.c, p.glv);
-    p.NB = 1u << (p.c - 1);
-    p.NBT = (uint32_t)p.W * batch * p.NB;   // a batch of MSMs over one table is one MSM with batch x W windows
-    // segment length of the bucket reduction: ~1024 waves of running sums (profiles/r01_sweeps.txt)
-    // (short segments = short chains; when the tail is hidden under the next MSM's bulk its WORK is what costs, and the
-    // double-and-add by the segment offset — as much work as 8 buckets of running sums — amortises over longer segments)
-    uint32_t seg = c->cfg_seg ? (uint32_t)c->cfg_seg
-                              : (p.NBT >= (1u << 18) ? (c->tail_overlap && p.NBT >= (1u << 19) ? 32u : 8u)
-                                                     : (p.NBT >= (1u << 15) ? 4u : 2u));
-    if (seg > p.NB) seg = p.NB;
-    p.seg = seg;
-    p.spw = p.NB / seg;
-    p.big = c->cfg_big ? (uint32_t)c->cfg_big : 256u;
-    return p;
 }
 
 struct StageTimer {
@@ -570,701 +606,7 @@ void profile_harvest_all(h2agg_ctx* c) {
     for (int k = 0; k < h2agg_ctx::PROF_RING; ++k) profile_harvest(c, k);
 }
 
-// make everything queued on the tail stream visible to the main stream
-int flush_deferred_tail(h2agg_ctx* c, bool behind_sort) {
-    if (!c->deferred_tail) return H2AGG_OK;
-    std::function<int(bool)> f;
-    f.swap(c->deferred_tail);
-    return f(behind_sort);
-}
-
-int join_tails(h2agg_ctx* c) {
-    TRY(flush_deferred_tail(c, false));
-    for (int k = 0; k < h2agg_ctx::TAIL_SLOTS; ++k) {
-        if (c->tail_pending[k]) {
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_tail[k], 0));
-            c->tail_pending[k] = false;
-        }
-    }
-    for (int q = 0; q < 2; ++q) {   // (every accumulation is followed by a tail, so these have completed: bookkeeping)
-        if (c->accdone_pending[q]) {
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_accdone[q], 0));
-            c->accdone_pending[q] = false;
-        }
-    }
-    return H2AGG_OK;
-}
-
-// The MSM proper.  d_bases: Montgomery affine table; d_scalars: canonical 32-B scalars (device).
-// Result: c->d_res_xyzz (Montgomery XYZZ) and, if d_out_jac != nullptr, canonical Jacobian there.
-// batch > 1: `batch` MSMs over the SAME n bases, scalars laid out [batch][n]; results: canonical Jacobian at
-// d_out_jac[96 * q] (c->d_res_xyzz then only holds MSM 0's XYZZ).  One set of launches does all of them: every
-// scalar's windows are numbered q * W + w, and the stages after the sort only see batch * W windows.
-// d_endo_x: beta * x per base (Table::endo_x) or nullptr = compute it here when the plan uses GLV.
-// pre: fixed-base levels of the table (then d_bases is ignored): plain c-bit digits of ALL positions into one bucket set
-// per MSM, bases looked up at level w; no Horner chain.
-// can two MSMs of n_total points in all run as one split MSM (below)?  The one-launch sort's range, nothing forced.
-bool msm_split_ok(const h2agg_ctx* c, size_t n_total) {
-    if (!c->dbg_small_sort || n_total < 2 || n_total > (size_t)SMALL_SORT_N) return false;
-    if (c->cfg_no_stage || c->cfg_stage_l1 || c->cfg_sub_bits || c->cfg_tile || c->chain) return false;
-    const MsmPlan p = make_plan(c, n_total, 2);
-    return p.NB <= (uint32_t)SMALL_SORT_NB;
-}
-
-// split != 0: TWO MSMs over the disjoint parts [0, split) and [split, n_base) of one table (scalars laid out alike), as one
-// set of launches with 2 W windows; results: XYZZ at c->d_res_xyzz and c->d_res_xyzz + XYZZ_BYTES.  Only for sizes the
-// one-launch sort takes (msm_split_ok): the evaluation's two multi_exps.  When the plan (make_plan(c, n_base, 2)) uses GLV,
-// d_scalars are glv_decompose() words and d_endo_x is given (k_eval_prep wrote both); the tail stays on the context's
-// stream — nothing follows that it could hide under, and a stream hand-over costs 10-20 us each way.
-// the (level, point) sort of fb_sort_kernels.hpp has no sort / segment knobs: a context configured with any
-// (h2agg_msm_configure_sort, reduce_segment) does not take it
-bool fb_sort_knobs_clear(const h2agg_ctx* c) {
-    return !c->cfg_no_dm && !c->cfg_no_stage && !c->cfg_stage_l1 && !c->cfg_sub_bits && !c->cfg_tile && !c->cfg_seg;
-}
-
-// Which instantiation of the lean bucket accumulation a call takes (msm_kernels.hpp VAR): the identity test stays unless the
-// table is KNOWN to hold none, the endomorphism select stays when the plan splits scalars.  Pure: h2agg_debug_lean_variant.
-int msm_lean_variant(bool table_no_identity, bool plan_glv) {
-    return (table_no_identity ? 0 : LEAN_ID) | (plan_glv ? LEAN_ENDO : 0);
-}
-// what the creating call's base-table word says about the table it wrote (word: flags[1] as finish() read it)
-bool table_word_clear(uint32_t word) { return word == 0; }
-
-using AccLeanKernel = decltype(&k_msm_accumulate_lean<0, true>);
-template <bool DUAL>
-AccLeanKernel acc_lean_kernel(int chain, int var) {
-    const int ch = chain == CHAIN_FIRST ? 1 : (chain == CHAIN_MID || chain == CHAIN_LAST) ? 2 : 0;
-#define ACC_LEAN_ROW(CH)                                                                                      \
-    case CH:                                                                                                   \
-        return var == 0 ? k_msm_accumulate_lean_v<CH, DUAL, 0> : var == LEAN_ID ? k_msm_accumulate_lean_v<CH, DUAL, LEAN_ID> \
-             : var == LEAN_ENDO ? k_msm_accumulate_lean_v<CH, DUAL, LEAN_ENDO> : k_msm_accumulate_lean<CH, DUAL>;
-    switch (ch) {
-        ACC_LEAN_ROW(1)
-        ACC_LEAN_ROW(2)
-        default:
-        ACC_LEAN_ROW(0)
-    }
-#undef ACC_LEAN_ROW
-}
-
-// no_identity: the table d_bases points into is known to hold no identity base (Table::no_identity)
-int msm_run(h2agg_ctx* c, const uint8_t* d_bases, const uint8_t* d_scalars, size_t n_base, uint8_t* d_out_jac,
-            uint32_t batch = 1, const uint8_t* d_endo_x = nullptr, const PreTable* pre = nullptr, uint32_t split = 0,
-            bool no_identity = false) {
-    if (split) batch = 2;
-    const size_t n = split ? n_base : n_base * batch;   // scalars
-    crumb((uintptr_t)__builtin_return_address(0), ((uint64_t)batch << 40) | n_base);
-    if (n >= ((size_t)1 << 30)) return fail(c, H2AGG_ERR_INVALID, "n must be < 2^30");
-    const int chain = (pre || batch != 1) ? CHAIN_OFF : c->chain;
-    MsmPlan p = make_plan(c, chain ? c->chain_n : n_base, batch);
-    if (chain && p.glv != c->chain_glv) {   // (the caller fixed the split for the whole chain)
-        const int was = c->cfg_glv;
-        c->cfg_glv = c->chain_glv ? 1 : -1;
-        p = make_plan(c, c->chain_n, batch);
-        c->cfg_glv = was;
-    }
-    int Wd = p.W;                             // digit positions per scalar (what the recoding loops over)
-    // fixed-base levels at c = 20 (tables of 2^18 .. 2^22 points): the (level, point) sort of fb_sort_kernels.hpp
-    const bool fbdm = pre && batch == 1 && pre->c == FB_C && pre->W == FB_W && pre->n_level <= ((size_t)FB_MAX_TILES * FB_T) &&
-                      fb_sort_knobs_clear(c);
-    const uint32_t fb_ntile = (uint32_t)((n + FB_T - 1) / FB_T);
-    if (pre) {
-        p.glv = false;
-        p.c = pre->c;
-        Wd = pre->W;
-        p.W = 1;                              // one bucket set per MSM
-        p.NB = 1u << (p.c - 1);
-        p.NBT = fbdm ? FB_NBT : batch * p.NB;   // (the top digit's own slots: fb_sort_kernels.hpp)
-        // measured (tools/instance_seg_sweep.py, 2^17-point columns): 16-bucket segments up to 8 MSMs per batch, 32 beyond
-        p.seg = c->cfg_seg ? (uint32_t)c->cfg_seg : (batch >= 16 ? 32u : 16u);
-        if (p.seg > p.NB) p.seg = p.NB;
-        p.spw = p.NB / p.seg;
-        d_bases = pre->d;
-    }
-    const int W1 = p.W;                       // windows (bucket sets) per MSM
-    const uint32_t WT = (uint32_t)W1 * batch;  // windows in total
-    const size_t nent = n * (size_t)Wd * (p.glv ? 2 : 1);   // bucket insertions
-    if (!c->cfg_big) {
-        // a lane walks a bucket alone up to `big` entries: 8x the mean keeps a denser top window (up to 4x the mean
-        // when it holds c-2 bits) out of the workgroup-per-chunk path, whose LDS tree only pays for real outliers
-        const size_t mean = nent / p.NBT;
-        if (8 * mean > p.big) p.big = (uint32_t)(8 * mean);
-    }
-    if (nent >= ((size_t)1 << 32)) return fail(c, H2AGG_ERR_INVALID, "n * windows must be < 2^32");
-    SortPlan sp;
-    int want_sub = c->cfg_sub_bits ? c->cfg_sub_bits : SORT_SUB_BITS;
-    if (pre && !c->cfg_sub_bits) {
-        // one bucket set per MSM: keep >= 256 level-2 partitions (one workgroup each) so the sort still fills the chip
-        while (want_sub > 4 && (((size_t)p.NB * batch) >> want_sub) < 256) --want_sub;
-    }
-    sp.sub_bits = (p.c - 1 < want_sub) ? p.c - 1 : want_sub;
-    while ((WT * (p.NB >> sp.sub_bits)) > (uint32_t)SORT_MAX_PW && sp.sub_bits < p.c - 1 &&
-           sp.sub_bits < SORT_MAX_SUB_BITS)
-        ++sp.sub_bits;  // keep the level-1 partition count within its LDS counters
-    sp.SB = 1u << sp.sub_bits;
-    sp.ppw = p.NB >> sp.sub_bits;
-    sp.PW = WT * sp.ppw;
-    if (batch > 1 && !split) {
-        sp.n_base = (uint32_t)n_base;
-        sp.W1 = (uint32_t)W1;
-    }
-    if (pre) sp.pre_n = (uint32_t)pre->n_level;
-    sp.tile = c->cfg_tile ? (uint32_t)c->cfg_tile : 2048u;
-    // packed-item staged path: index field of 31 - sub_bits bits, a tile's keys must fit the LDS stage
-    sp.glv = p.glv;
-    const int idx_bits = (p.glv ? 30 : 31) - sp.sub_bits;   // packed item: sub | neg | (endo) | idx
-    // items carry the BASE index (fixed-base mode: up to W * n_level of them)
-    bool staged = !c->cfg_no_stage && (pre ? (size_t)pre->W * pre->n_level : n_base) <= ((size_t)1 << idx_bits);
-    const size_t keys_per_scalar = (size_t)Wd * (p.glv ? 2 : 1);
-    if (staged && c->cfg_stage_l1 && (size_t)sp.tile * keys_per_scalar > (size_t)STAGE_ITEMS_L1)
-        sp.tile = (uint32_t)(STAGE_ITEMS_L1 / keys_per_scalar);
-    if (staged && sp.tile < (uint32_t)BLOCK) staged = false;
-    if (sp.PW > (uint32_t)SORT_MAX_PW) return fail(c, H2AGG_ERR_INVALID, "too many sort partitions");
-    const uint32_t nseg_total = WT * p.spw;
-    // 4 lanes per chain in the bucket reduction / window sums (latency) or 1 (least work): see msm_kernels.hpp
-    static const int par4_env = knob("H2AGG_PAR4") ? atoi(knob("H2AGG_PAR4")) : 0;
-    // measured: wins up to 16384 segments (c <= 13; also a 2^20-point MSM with 32-bucket segments in throughput mode,
-    // where 1 024 waves of 94-addition chains would otherwise outlast the step), loses to the extra work above
-    // (a split MSM is two such MSMs side by side, each within the range)
-    const bool par4 = par4_env ? par4_env > 0 : nseg_total <= (split ? 32768u : 16384u);
-    // pmeta words: pcount [PW] | pstart [PW + 1] | pcursor [PW] | bin_count [SIZE_BINS] | bin_start [SIZE_BINS + 1] |
-    //              bin_cursor [SIZE_BINS] | big-bucket counters [2], each padded by 64 words
-    constexpr uint32_t META_PW = DM_MAX_PW;   // (the digit-major path has up to 16 x 512 partitions)
-    constexpr uint32_t M_PSTART = META_PW + 64, M_PCURSOR = M_PSTART + META_PW + 64,
-                       M_BCOUNT = M_PCURSOR + META_PW + 64, M_BSTART = M_BCOUNT + SIZE_BINS + 64,
-                       M_BCURSOR = M_BSTART + SIZE_BINS + 64, M_BIG = M_BCURSOR + SIZE_BINS + 64, M_WORDS = M_BIG + 64;
-    // overlap level 3 (see h2agg_ctx::acc_stream): this MSM's accumulation leaves the context's stream
-    const bool piped = c->tail_overlap && c->overlap_level >= 3;
-    // overlap level >= 2: consecutive MSMs alternate between the two sets of sort outputs, so that what still reads one set
-    // behind the accumulation (over-long-bucket kernels, zeroing of the counters: tail stream) never holds up the next sort
-    const bool altbuf = c->tail_overlap && c->overlap_level >= 2;
-    const int sq = altbuf ? c->sort_par : 0;
-    {
-        const size_t cap0 = c->pmeta[sq].cap;
-        TRY(ensure(c, c->pmeta[sq], M_WORDS * 4));
-        if (c->pmeta[sq].cap != cap0) c->meta_clean[sq] = false;
-    }
-    TRY(ensure(c, c->hist[sq], (size_t)p.NBT * 4));
-    TRY(ensure(c, c->offs[sq], (size_t)p.NBT * 4));
-    TRY(ensure(c, c->order[sq], (size_t)p.NBT * 4));
-    // digit-major sort (sort_kernels.hpp): plain 16-bit windows over one table, 2^16 .. 2^22 points
-    static const bool dm_env_off = knob("H2AGG_SORT") && !strcmp(knob("H2AGG_SORT"), "packed");
-    const size_t dm_row = p.glv ? 2 * n : n;   // keys per window (GLV: both halves of a scalar land in the same 8 windows)
-    // (c = 17, plain scalars: 15 windows of 2^16 buckets, 16-bit magnitude codes + sign / zero bit rows — k_dm_digits17, k_dm_partition<true>)
-    const bool dm17 = p.c == 17 && !p.glv;
-    const bool dm = !dm_env_off && !c->cfg_no_dm && !c->cfg_no_stage && !c->cfg_stage_l1 && !c->cfg_sub_bits && !c->cfg_tile && !pre && batch == 1 &&
-                    (p.c == 16 || dm17) && dm_row >= ((size_t)1 << 16) && dm_row <= ((size_t)1 << 22);
-    const uint32_t dm_nwin = p.glv ? 8u : (dm17 ? 15u : 16u);
-    // the one-launch sort of small MSMs (sort_kernels.hpp k_small_sort); a forced sort configuration keeps its own kernels
-    static const bool small_env_off = knob("H2AGG_SMALL_SORT") && !strcmp(knob("H2AGG_SMALL_SORT"), "0");
-    const bool small_sort = !small_env_off && c->dbg_small_sort && !pre && !dm && n <= (size_t)SMALL_SORT_N && p.NB <= (uint32_t)SMALL_SORT_NB &&
-                            !c->cfg_no_stage && !c->cfg_stage_l1 && !c->cfg_sub_bits && !c->cfg_tile;
-    if (split && (!small_sort || split >= n_base)) return fail(c, H2AGG_ERR_INVALID, "split MSM outside the one-launch sort's range");
-    DmPlan dp{};
-    if (dm) {
-        const size_t n = dm_row;   // (shadows the point count inside this block)
-        dp.n_pts = p.glv ? (uint32_t)(dm_row / 2) : 0xffffffffu;
-        dp.n = (uint32_t)n;
-        dp.n_pad = dm17 ? (uint32_t)((n + 63) & ~(size_t)63) : (uint32_t)((n + 7) & ~(size_t)7);   // (17-bit windows: bit rows, 64 keys per word)
-        dp.ntile = (uint32_t)((n + DM_T1 - 1) / DM_T1);
-        dp.n_row = dp.ntile * (uint32_t)DM_T1;
-        dp.ppw = dm17 ? 128 : 64;   // (level 2 keeps <= 512 buckets per partition in LDS: sub_bits <= 9)
-        while (n / dp.ppw > 4096 && dp.ppw < (uint32_t)DM_MAX_PPW) dp.ppw *= 2;   // ~4 K keys per level-2 partition (8 K at 2^22)
-        dp.sub_bits = p.c - 1;
-        for (uint32_t q = dp.ppw; q > 1; q >>= 1) --dp.sub_bits;
-        dp.SB = 1u << dp.sub_bits;
-        dp.idx_bits = 31 - dp.sub_bits;
-    }
-    TRY(ensure(c, c->item_idx, fbdm ? (size_t)fb_ntile * FB_KEYS1 * 4 : dm ? (size_t)dm_nwin * dp.n_row * 4 : nent * 4));
-    if (fbdm) TRY(ensure(c, c->fb_long, FB_LONG_WORDS * 4));   // very long partitions across workgroups (fb_sort_kernels.hpp)
-    TRY(ensure(c, c->item_sub, fbdm ? 0 : dm ? (size_t)dm_nwin * dp.n_pad * 2 + (dm17 ? (size_t)2 * dm_nwin * (dp.n_pad / 8) : 0) : nent * 2));
-    TRY(ensure(c, c->entries[sq], nent * 4));
-    // buckets / segsum / wsum exist once per tail slot: in overlap mode the reduction of MSM k (tail stream)
-    // runs while MSM k+1 fills the next slot's set.  (They were one allocation cut at par * this-plan's-size: two MSMs
-    // with different plans in flight then overlapped — ADVICE r1.)
-    const int par = c->parity;
-    TRY(ensure(c, c->buckets[par], (size_t)p.NBT * XYZZ_BYTES));
-    {   // (the two-dimensional reduction keeps 4096 partial sums per window there)
-        const size_t r2d_records = p.NB == (uint32_t)(R2D_ROWS * R2D<7>::COLS) ? (size_t)WT * (R2D<7>::THREADS + 2)
-                                   : p.NB == (uint32_t)(R2D_ROWS * R2D<8>::COLS) ? (size_t)WT * (R2D<8>::THREADS + 2) : 0;
-        const size_t fb_records = fbdm ? (size_t)FB_R2D_WINDOWS * (R2D<7>::THREADS + 3) : 0;   // parts, halves, bucket sums
-        TRY(ensure(c, c->segsum[par], std::max(std::max((size_t)nseg_total, r2d_records), fb_records) * XYZZ_BYTES));
-    }
-    TRY(ensure(c, c->wsum[par], (size_t)(fbdm ? FB_R2D_WINDOWS + 2 : WT) * XYZZ_BYTES));
-    const size_t max_slots = nent / BIG_CHUNK + nent / ((size_t)p.big + 1) + 2;   // chunks of over-long buckets
-    const size_t max_keys = nent / ((size_t)p.big + 1) + 2;
-    TRY(ensure(c, c->big_list[sq], max_slots * 12));
-    TRY(ensure(c, c->big_keys[sq], max_keys * 12));
-    TRY(ensure(c, c->big_part[sq], max_slots * XYZZ_BYTES));
-    uint32_t* meta = (uint32_t*)c->pmeta[sq].p;
-    uint32_t *pcount = meta, *pstart = meta + M_PSTART, *pcursor = meta + M_PCURSOR;
-    uint32_t *bin_count = meta + M_BCOUNT, *bin_start = meta + M_BSTART, *bin_cursor = meta + M_BCURSOR;
-    uint32_t* hist = (uint32_t*)c->hist[sq].p;
-    uint32_t* offs = (uint32_t*)c->offs[sq].p;
-    uint32_t* order = (uint32_t*)c->order[sq].p;
-    uint32_t* item_idx = (uint32_t*)c->item_idx.p;
-    uint16_t* item_sub = (uint16_t*)c->item_sub.p;
-    uint32_t* fb_long = (uint32_t*)c->fb_long.p;
-    uint32_t* entries = (uint32_t*)c->entries[sq].p;
-    c->d_res_xyzz = (uint8_t*)c->small.p + 1024 + 144 * par;   // each tail slot has its own XYZZ result
-    if (split) c->d_res_xyzz = (uint8_t*)c->small.p + 2048 + 2 * 144 * par;   // ... or its own two
-    uint8_t* buckets = (uint8_t*)c->buckets[par].p;
-    uint8_t* segsum = (uint8_t*)c->segsum[par].p;
-    uint8_t* wsum = (uint8_t*)c->wsum[par].p;
-    uint32_t* big_list = (uint32_t*)c->big_list[sq].p;
-    uint32_t* big_keys = (uint32_t*)c->big_keys[sq].p;
-    uint8_t* big_part = (uint8_t*)c->big_part[sq].p;
-    uint32_t* big_count = meta + M_BIG;   // [0] chunk slots, [1] multi-chunk buckets (zeroed with the rest of meta)
-    hipStream_t st = c->stream;
-    const unsigned ntiles = (unsigned)((n + sp.tile - 1) / sp.tile);
-    // per-tile partition counts from the counting pass, read back by the packed scatter pass (same tiles)
-    uint32_t* tile_counts = nullptr;
-    if (fbdm) {
-        TRY(ensure(c, c->tile_counts, (size_t)fb_ntile * (FB_NPART + 1) * 4));
-        tile_counts = (uint32_t*)c->tile_counts.p;
-    } else if (dm) {
-        TRY(ensure(c, c->tile_counts, (size_t)dm_nwin * dp.ntile * (dp.ppw + 1) * 4));
-        tile_counts = (uint32_t*)c->tile_counts.p;
-    } else if (staged && !c->cfg_stage_l1) {
-        TRY(ensure(c, c->tile_counts, (size_t)ntiles * sp.PW * 4));
-        tile_counts = (uint32_t*)c->tile_counts.p;
-    }
-    const bool meta_was_clean = altbuf && c->meta_clean[sq];
-    c->meta_clean[sq] = false;
-    profile_begin_call(c);
-    // the accumulation that last read this slot's sort outputs (two MSMs ago, or any earlier one for an MSM that does not
-    // leave the stream: it uses slot 0 and scratch the accumulation stream may still read — beta*x column, slice sums)
-    for (int q = 0; q < 2; ++q) {
-        if (c->accdone_pending[q] && (!altbuf || q == sq || (p.glv && !d_endo_x))) {
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_accdone[q], 0));
-            c->accdone_pending[q] = false;
-        }
-    }
-
-    bool endo_late = false;   // (with a bases hook the beta*x column is computed behind it, in front of the accumulation)
-    if (p.glv && !d_endo_x) {
-        TRY(ensure(c, c->endo_buf, n_base * 32));
-        if (c->bases_hook) endo_late = true;
-        else
-            hipLaunchKernelGGL(k_bases_endo_x, dim3(grid_for(c, n_base)), dim3(BLOCK), 0, st, d_bases, n_base,
-                               (uint8_t*)c->endo_buf.p);
-        d_endo_x = (const uint8_t*)c->endo_buf.p;
-    }
-    debug_sync(1);
-    chaos_wait(4, st);
-    if (p.glv && !split) {  // k = k1 + lambda*k2: the sort below reads the decomposed words instead of the scalars
-        // (a split MSM's caller hands over the decomposed words and the beta * x column: k_eval_prep)
-        TRY(ensure(c, c->glv_buf, n * 32));
-        StageTimer t(c, ST_PART_COUNT);
-        hipLaunchKernelGGL(k_glv_decompose, dim3(grid_for(c, n)), dim3(BLOCK), 0, st, d_scalars, n,
-                           (uint8_t*)c->glv_buf.p, c->d_flags);
-        d_scalars = (const uint8_t*)c->glv_buf.p;
-    }
-    if (small_sort) {
-        StageTimer t(c, ST_BUCKET_SORT);
-        // (the length-ordering pass below counts into the scratch words: then they are cleared as a whole)
-        if (nent >= ((size_t)1 << 16) && !meta_was_clean) HIP_TRY(c, hipMemsetAsync(meta, 0, M_WORDS * 4, st));
-        hipLaunchKernelGGL(k_small_sort, dim3(WT), dim3(SMALL_SORT_TB), 0, st, d_scalars, (uint32_t)n, p.c, Wd,
-                           (batch > 1 && !split) ? (uint32_t)n_base : 0u, split, p.glv, p.NB, hist, offs, entries, c->d_flags,
-                           big_count);
-    } else if (fbdm) {
-        {
-            StageTimer t(c, ST_PART_SCATTER);
-            if (!meta_was_clean) HIP_TRY(c, hipMemsetAsync(meta, 0, M_WORDS * 4, st));
-            hipLaunchKernelGGL(k_fb_partition, dim3(fb_ntile), dim3(FB_TB1), 0, st, d_scalars, (uint32_t)n, pcount, tile_counts, item_idx,
-                               c->d_flags);
-            hipLaunchKernelGGL(k_fb_scan_list, dim3(1), dim3(1024), 0, st, (const uint32_t*)pcount, pstart, fb_ntile, fb_long);
-        }
-        {
-            StageTimer t(c, ST_BUCKET_SORT);
-            hipLaunchKernelGGL(k_fb_bucket_sort, dim3(FB_NPART), dim3(FB_TB2), 0, st, (const uint32_t*)pstart, (const uint32_t*)tile_counts,
-                               (const uint32_t*)item_idx, (uint32_t)pre->n_level, fb_ntile, hist, offs, entries);
-            // partitions too long for the stage (skewed / small scalars): the very long ones split over workgroups, the rest one
-            // workgroup each; with uniform scalars every workgroup of the three launches leaves at once
-            hipLaunchKernelGGL(k_fb_long_count, dim3(FB_LONG_CAP, FB_LONG_S), dim3(FB_TB2), 0, st, (const uint32_t*)pstart,
-                               (const uint32_t*)tile_counts, (const uint32_t*)item_idx, (uint32_t)pre->n_level, fb_ntile, fb_long, hist, offs);
-            hipLaunchKernelGGL(k_fb_long_place, dim3(FB_LONG_CAP, FB_LONG_S), dim3(FB_TB2), 0, st, (const uint32_t*)pstart,
-                               (const uint32_t*)tile_counts, (const uint32_t*)item_idx, (uint32_t)pre->n_level, fb_ntile,
-                               (const uint32_t*)fb_long, entries);
-            hipLaunchKernelGGL(k_fb_bucket_sort_long, dim3(FB_NPART), dim3(FB_TB2), 0, st, (const uint32_t*)pstart,
-                               (const uint32_t*)tile_counts, (const uint32_t*)item_idx, (uint32_t)pre->n_level, fb_ntile,
-                               (const uint32_t*)fb_long, hist, offs, entries);
-        }
-    } else if (dm) {
-        const uint32_t PW = dm_nwin * dp.ppw;
-        {
-            StageTimer t(c, ST_PART_COUNT);
-            if (!meta_was_clean) HIP_TRY(c, hipMemsetAsync(meta, 0, M_WORDS * 4, st));
-            const unsigned dg = (unsigned)((n + BLOCK * DM_DIG_PER - 1) / (BLOCK * DM_DIG_PER));
-            if (p.glv)   // d_scalars: the decomposed words (range-checked by k_glv_decompose)
-                hipLaunchKernelGGL(k_dm_digits_glv, dim3(dg), dim3(BLOCK), 0, st, d_scalars, (uint32_t)n, dp.n_pad, item_sub);
-            else if (dm17)
-                hipLaunchKernelGGL(k_dm_digits17, dim3(dg), dim3(BLOCK), 0, st, d_scalars, dp.n, dp.n_pad, item_sub, c->d_flags);
-            else
-                hipLaunchKernelGGL(k_dm_digits, dim3(dg), dim3(BLOCK), 0, st, d_scalars, dp.n, dp.n_pad, item_sub, c->d_flags);
-        }
-        {
-            StageTimer t(c, ST_PART_SCATTER);
-            if (dm17)
-                hipLaunchKernelGGL(k_dm_partition<true>, dim3(dp.ntile, dm_nwin), dim3(DM_TB1), 0, st, (const uint16_t*)item_sub, dp, pcount,
-                                   tile_counts, item_idx);
-            else
-                hipLaunchKernelGGL(k_dm_partition<false>, dim3(dp.ntile, dm_nwin), dim3(DM_TB1), 0, st, (const uint16_t*)item_sub, dp, pcount,
-                                   tile_counts, item_idx);
-                hipLaunchKernelGGL(k_dm_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)pcount, PW, pstart);
-            }
-        {
-            StageTimer t(c, ST_BUCKET_SORT);
-            if (dp.n / dp.ppw <= 4096)
-                hipLaunchKernelGGL(k_dm_bucket_sort<16>, dim3(PW), dim3(DM_TB2), 0, st, (const uint32_t*)pstart,
-                                   (const uint32_t*)tile_counts, (const uint32_t*)item_idx, dp, p.NB, hist, offs, entries);
-            else
-                hipLaunchKernelGGL(k_dm_bucket_sort<32>, dim3(PW), dim3(DM_TB2), 0, st, (const uint32_t*)pstart,
-                                   (const uint32_t*)tile_counts, (const uint32_t*)item_idx, dp, p.NB, hist, offs, entries);
-        }
-    } else {
-    {
-        StageTimer t(c, ST_PART_COUNT);
-        if (!meta_was_clean) HIP_TRY(c, hipMemsetAsync(meta, 0, M_WORDS * 4, st));
-        hipLaunchKernelGGL(k_part_count, dim3(ntiles), dim3(BLOCK), 0, st, d_scalars, n, p.c, Wd, sp, pcount,
-                           c->d_flags, tile_counts);
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(BLOCK), 0, st, pcount, sp.PW, pstart, pcursor);
-    }
-    if (staged) {
-        // LDS-staged sort: keys leave the CU as contiguous runs (n fits the packed item's index field)
-        const size_t lds1 = (size_t)(4 * SORT_MAX_PW + STAGE_ITEMS_L1) * 4;
-        constexpr int SORT2_TB = 1024;   // level-2 workgroup size (one workgroup per CU: see k_bucket_sort_staged)
-        const size_t lds2 = (size_t)(SORT_MAX_SB + SORT2_TB + STAGE_ITEMS) * 4;
-        if (!c->staged_attr_set) {
-            HIP_TRY(c, hipFuncSetAttribute((const void*)k_part_scatter_staged,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-            HIP_TRY(c, hipFuncSetAttribute((const void*)k_bucket_sort_staged<SORT2_TB>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            c->staged_attr_set = true;
-        }
-        {
-            StageTimer t(c, ST_PART_SCATTER);
-            if (c->cfg_stage_l1)
-                hipLaunchKernelGGL(k_part_scatter_staged, dim3(ntiles), dim3(BLOCK), lds1, st, d_scalars, n, p.c, Wd,
-                                   sp, idx_bits, pcursor, item_idx);
-            else
-                hipLaunchKernelGGL(k_part_scatter_packed, dim3(ntiles), dim3(BLOCK), 0, st, d_scalars, n, p.c, Wd, sp,
-                                   idx_bits, pcursor, item_idx, (const uint32_t*)tile_counts);
-        }
-        {
-            StageTimer t(c, ST_BUCKET_SORT);
-            hipLaunchKernelGGL(k_bucket_sort_staged<SORT2_TB>, dim3(sp.PW), dim3(SORT2_TB), lds2, st, pstart, item_idx, sp, idx_bits,
-                               p.NB, hist, offs, entries);
-        }
-    } else {
-        {
-            StageTimer t(c, ST_PART_SCATTER);
-            hipLaunchKernelGGL(k_part_scatter, dim3(ntiles), dim3(BLOCK), 0, st, d_scalars, n, p.c, Wd, sp, pcursor,
-                               item_idx, item_sub);
-        }
-        {
-            StageTimer t(c, ST_BUCKET_SORT);
-            hipLaunchKernelGGL(k_bucket_sort, dim3(sp.PW), dim3(BLOCK), 0, st, pstart, item_idx, item_sub, sp, p.NB,
-                               hist, offs, entries);
-        }
-    }
-    }
-    // ordering the buckets by length balances the lanes of a wave; with few entries the longest run bounds the kernel
-    // either way and the three launches (~25 us) are pure latency
-    const bool ordered = nent >= ((size_t)1 << 16);
-    if (ordered) {
-        StageTimer t(c, ST_ORDER);
-        unsigned g = (p.NBT + BLOCK * 8 - 1) / (BLOCK * 8);
-        if (g > (unsigned)c->cu_count * 4) g = (unsigned)c->cu_count * 4;
-        hipLaunchKernelGGL(k_size_count, dim3(g), dim3(BLOCK), 0, st, hist, p.NBT, bin_count);
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(BLOCK), 0, st, bin_count, (uint32_t)SIZE_BINS, bin_start,
-                           bin_cursor);
-        hipLaunchKernelGGL(k_size_scatter, dim3(g), dim3(BLOCK), 0, st, hist, p.NBT, bin_cursor, order);
-    }
-    if (c->deferred_tail) {   // the previous MSM's tail goes out now, behind this MSM's sort
-        HIP_TRY(c, hipEventRecord(c->ev_sortdone, st));
-        TRY(flush_deferred_tail(c, true));
-    }
-    if (piped) {   // from here on: the accumulation stream
-        HIP_TRY(c, hipEventRecord(c->ev_sorted[sq], st));
-        HIP_TRY(c, hipStreamWaitEvent(c->acc_stream, c->ev_sorted[sq], 0));
-        st = c->acc_stream;
-    }
-    if (c->tail_pending[par]) {  // the tail TAIL_SLOTS MSMs ago read this slot's buckets / segsum / wsum
-        HIP_TRY(c, hipStreamWaitEvent(st, c->ev_tail[par], 0));
-        c->tail_pending[par] = false;
-    }
-    // lanes per bucket: keep >= ~8192 waves in flight (3 per SIMD x 1024 SIMDs, 2-3 rounds) when buckets are few
-    // With few buckets the kernel is bound by its longest run (one mixed add is ~6 us of dependent latency): 8 lanes
-    // per bucket turn a 60-entry run into 8 entries + 7 adds of the combine.
-    uint32_t lpb = 1;
-    if (c->cfg_lpb) lpb = (uint32_t)c->cfg_lpb;
-    else   // ... but only while the mean run still covers the slices (measured, profiles/r01_sweeps.txt): sparse buckets
-           // (small MSMs with wide windows) gain nothing from slices and pay lpb - 1 additions per bucket in the combine
-        while (lpb < 8 && (size_t)p.NBT * lpb < (size_t)8192 * 64 &&
-               (chain ? c->chain_n * (size_t)Wd * (p.glv ? 2 : 1) : nent) >= (size_t)lpb * p.NBT)
-            lpb *= 2;   // (a chain's slices all cut their buckets alike: the slots are resumed)
-    if (c->bases_hook) {
-        TRY(c->bases_hook(st));
-        if (endo_late)
-            hipLaunchKernelGGL(k_bases_endo_x, dim3(grid_for(c, n_base)), dim3(BLOCK), 0, st, d_bases, n_base, (uint8_t*)c->endo_buf.p);
-    }
-    uint8_t* acc_out = buckets;
-    if (lpb > 1) {
-        TRY(ensure(c, c->parts, (size_t)p.NBT * lpb * XYZZ_BYTES));
-        acc_out = (uint8_t*)c->parts.p;
-    }
-    // (experiment knob: 256-thread workgroups + H2AGG_ACC_LDS pin the accumulation at exactly N waves per SIMD and leave the rest
-    // of the CU — registers and LDS — to whatever else is in flight; see profiles/r03_sweeps.txt section 10)
-    static const int acc_block = knob("H2AGG_ACC_BLOCK") ? atoi(knob("H2AGG_ACC_BLOCK")) : 64;
-    // the generic kernel (compiler-scheduled formulas, 166 VGPRs) lives in the measure build only, behind the debug key
-    // lean_acc = 0 / H2AGG_ACC=generic, for A/B runs; the shipped library carries the lean one alone
-#ifdef H2AGG_MEASURE_KNOBS
-    static const bool lean_env = !(knob("H2AGG_ACC") && !strcmp(knob("H2AGG_ACC"), "generic"));
-    const bool lean = lean_env && c->dbg_lean_acc;
-#else
-    const bool lean = true;
-#endif
-    uint32_t* fix_list = nullptr;
-    if (lean) {
-        TRY(ensure(c, c->fix_list[sq], (size_t)p.NBT * lpb * 8));
-        fix_list = (uint32_t*)c->fix_list[sq].p;
-    }
-    debug_sync(2);
-    chaos_wait(2, st);
-    {
-        StageTimer t(c, ST_ACCUM, st);
-        // one-wave workgroups: a 4-wave workgroup needs a free slot on all four SIMDs of a CU at once and its waves retire
-        // at different times; single waves fill any slot as it frees up (2^20 points: 1.74 -> 1.67 ms/step)
-        static const int acc_lds = knob("H2AGG_ACC_LDS") ? atoi(knob("H2AGG_ACC_LDS")) : 0;   // experiment: unused LDS per wave caps the occupancy
-        if (lean) {   // 128 VGPRs, four waves per SIMD; exceptional cases go to fix_list (msm_kernels.hpp)
-#ifdef H2AGG_MEASURE_KNOBS   // (one chain per product instead of two in lock step: an A/B variant, not in the shipped library)
-            static const bool lean_dual = !(knob("H2AGG_ACC") && !strcmp(knob("H2AGG_ACC"), "lean1"));
-            const int var = msm_lean_variant(no_identity && !c->dbg_lean_full, p.glv || c->dbg_lean_full);
-            auto kacc = lean_dual ? acc_lean_kernel<true>(chain, var) : acc_lean_kernel<false>(chain, var);
-#else
-            const int var = msm_lean_variant(no_identity && !c->dbg_lean_full, p.glv || c->dbg_lean_full);
-            auto kacc = acc_lean_kernel<true>(chain, var);
-#endif
-            c->last_lean_variant = var;
-            hipLaunchKernelGGL(kacc, dim3((unsigned)(((size_t)p.NBT * lpb + 63) / 64)), dim3(64), (size_t)acc_lds,
-                               st, d_bases, d_endo_x, entries, offs, hist, ordered ? order : (uint32_t*)nullptr, p.NBT, p.big, lpb, acc_out,
-                               big_list, big_keys, big_count, fix_list);
-        } else {
-#ifdef H2AGG_MEASURE_KNOBS
-        auto kacc = chain == CHAIN_FIRST ? k_msm_accumulate<1> : (chain == CHAIN_MID || chain == CHAIN_LAST) ? k_msm_accumulate<2> : k_msm_accumulate<0>;
-        hipLaunchKernelGGL(kacc, dim3((unsigned)(((size_t)p.NBT * lpb + acc_block - 1) / acc_block)), dim3(acc_block), (size_t)acc_lds,
-                           st, d_bases, d_endo_x, entries, offs, hist, ordered ? order : (uint32_t*)nullptr, p.NBT, p.big, lpb, acc_out,
-                           big_list, big_keys, big_count);
-#endif
-        }
-    }
-    // Buckets longer than `big` (skewed scalars; none for uniform ones, where the two launches below only find empty lists):
-    // with alternating sort outputs they leave the bulk stream and go in front of the bucket reduction on the tail stream,
-    // followed by the zeroing of this slot's counters for the MSM after next.
-    const bool tail_big = altbuf && c->overlap_level >= 2 && lpb == 1 && (chain == CHAIN_OFF || chain == CHAIN_LAST) && !split;
-    const uint32_t resume = (chain == CHAIN_MID || chain == CHAIN_LAST) ? 1u : 0u;
-    const bool chain_open = chain == CHAIN_FIRST || chain == CHAIN_MID;   // no tail yet
-    // (no bucket can hold more keys than its bucket set receives: a multi_exp of a dozen points skips the two launches,
-    // ~35 us at the head of its tail)
-    const bool big_possible = nent / WT > p.big;
-    auto big_kernels = [=](hipStream_t bs) {
-        StageTimer t(c, ST_ACCUM_BIG, bs);
-        if (lean)   // (grid-stride over a list that is empty but for the one-limb filter's false positives and adversarial inputs)
-            hipLaunchKernelGGL(k_msm_accumulate_fix, dim3((unsigned)std::min<size_t>((size_t)c->cu_count * 12, ((size_t)p.NBT * lpb + 63) / 64)), dim3(64), 0, bs, d_bases, d_endo_x, entries, offs,
-                               hist, lpb, acc_out, (const uint32_t*)big_count, (const uint32_t*)fix_list);
-        if (!big_possible && lpb == 1) return;
-        size_t grid = max_slots;
-        const size_t cap = (size_t)c->cu_count * 8;   // one-wave workgroups, grid-stride over the (usually empty) lists
-        if (grid > cap) grid = cap;
-        hipLaunchKernelGGL(k_msm_accumulate_big, dim3((unsigned)grid), dim3(64), 0, bs, d_bases, d_endo_x, entries, offs, hist,
-                           acc_out, lpb, big_part, big_list, big_count, resume);
-        size_t gk = max_keys < cap ? max_keys : cap;
-        hipLaunchKernelGGL(k_msm_big_combine, dim3((unsigned)gk), dim3(64), 0, bs, big_part, big_keys, big_count,
-                           acc_out, lpb, resume);
-        // (in a chain only the last slice folds the slice slots, and it folds ALL of them: a bucket that is over-long in this
-        // slice may hold ordinary partial sums from earlier ones)
-        if (lpb > 1 && !chain_open) {
-            const uint32_t cbig = chain ? 0xffffffffu : p.big;
-            const unsigned gq = (unsigned)(((size_t)p.NBT * 2 * lpb + BLOCK - 1) / BLOCK);
-            if (p.NBT > 16384u || (lpb != 2 && lpb != 4 && lpb != 8))   // many buckets: one lane each (work, not latency)
-                hipLaunchKernelGGL(k_msm_bucket_combine, dim3((p.NBT + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, bs,
-                                   (const uint8_t*)acc_out, hist, p.NBT, cbig, lpb, buckets);
-            else if (lpb == 8)
-                hipLaunchKernelGGL(k_msm_bucket_combine_par4<8>, dim3(gq), dim3(BLOCK), 0, bs, (const uint8_t*)acc_out, hist, p.NBT, cbig, buckets);
-            else if (lpb == 4)
-                hipLaunchKernelGGL(k_msm_bucket_combine_par4<4>, dim3(gq), dim3(BLOCK), 0, bs, (const uint8_t*)acc_out, hist, p.NBT, cbig, buckets);
-            else
-                hipLaunchKernelGGL(k_msm_bucket_combine_par4<2>, dim3(gq), dim3(BLOCK), 0, bs, (const uint8_t*)acc_out, hist, p.NBT, cbig, buckets);
-        }
-    };
-    if (!tail_big) {
-        big_kernels(st);
-        if (altbuf) {
-            HIP_TRY(c, hipEventRecord(c->ev_accdone[sq], st));
-            c->accdone_pending[sq] = true;
-        }
-    }
-    if (altbuf) c->sort_par ^= 1;
-    if (chain_open) {   // the bucket set stays open for the next slice: no tail, the slot does not rotate
-        HIP_TRY(c, hipGetLastError());
-        profile_end_call(c);
-        return H2AGG_OK;
-    }
-    // Everything after the bucket accumulation is latency-shaped (one wave per SIMD or less): bucket
-    // reduction, per-window sums, Horner tail.  In overlap mode it runs on one of the context's tail streams, under the
-    // accumulation of the next MSM (launched from that MSM's call, behind its sort: `deferred_tail`); results are picked
-    // up by join_tails().
-#ifdef H2AGG_MEASURE_KNOBS   // timing experiments only (WRONG results): 1 skips the bucket reduction, 2 the window sums, 4 the Horner tail
-    static const int dbg_skip = knob("H2AGG_DBG_SKIP") ? atoi(knob("H2AGG_DBG_SKIP")) : 0;
-#else
-    constexpr int dbg_skip = 0;   // (a shipped library has no switch that changes results)
-#endif
-    // two-dimensional bucket reduction for 16-bit windows (msm_kernels.hpp); H2AGG_REDUCE=segments keeps the segment kernels
-    static const bool r2d_env_off = knob("H2AGG_REDUCE") && !strcmp(knob("H2AGG_REDUCE"), "segments");
-    const int r2d_lc = p.NB == (uint32_t)(R2D_ROWS * R2D<7>::COLS) ? 7 : p.NB == (uint32_t)(R2D_ROWS * R2D<8>::COLS) ? 8 : 0;
-    const bool r2d = !r2d_env_off && !c->cfg_seg && !pre && r2d_lc != 0;
-    uint32_t* ticket = nullptr;
-    if (r2d || fbdm) {
-        DevBuf& tk = c->r2d_ticket[par];   // arrival counters of the two half-window workgroups: zero between MSMs
-        const size_t tickets = fbdm ? (size_t)FB_R2D_WINDOWS : (size_t)WT;
-        if (tickets * 4 > tk.cap) {
-            TRY(ensure(c, tk, tickets * 4));
-            HIP_TRY(c, hipMemset(tk.p, 0, tk.cap));
-        }
-        ticket = (uint32_t*)tk.p;
-    }
-    debug_sync(4);
-    const bool tails_off_stream = c->tail_overlap && c->overlap_level >= 2 && !split;
-    const bool final_off_stream = c->tail_overlap && !split;
-    uint8_t* const res_xyzz = c->d_res_xyzz;
-    if (tails_off_stream) HIP_TRY(c, hipEventRecord(c->ev_bulk[par], st));
-    // `from`: the stream the accumulation ran on.  behind_sort: the tail stream also waits for c->ev_sortdone.
-    auto tail_fn = [=](bool behind_sort) -> int {
-        hipStream_t ts = st;
-        if (tails_off_stream) {
-            ts = c->tail_streams[par];
-            HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_bulk[par], 0));
-            if (behind_sort) HIP_TRY(c, hipStreamWaitEvent(ts, c->ev_sortdone, 0));
-        }
-        chaos_wait(1, ts);
-        if (tail_big) {
-            big_kernels(ts);
-            HIP_TRY(c, hipMemsetAsync(meta, 0, M_WORDS * 4, ts));
-            c->meta_clean[sq] = true;
-            HIP_TRY(c, hipEventRecord(c->ev_accdone[sq], ts));
-            c->accdone_pending[sq] = true;
-        }
-        if (fbdm) {   // one set of 2^19 buckets as 16 grids of 256 x 128 (msm_kernels.hpp, above k_fb_fold)
-            constexpr uint32_t per_w = (uint32_t)R2D<7>::THREADS, total = FB_R2D_WINDOWS * per_w;
-            uint8_t* halves = segsum + XYZZ_BYTES * (size_t)total;
-            uint8_t* tsum = halves + XYZZ_BYTES * (size_t)(2 * FB_R2D_WINDOWS);
-            uint8_t* w2 = wsum + XYZZ_BYTES * (size_t)FB_R2D_WINDOWS;
-            {
-                StageTimer t(c, ST_REDUCE, ts);
-                hipLaunchKernelGGL(k_fb_fold, dim3((FB_XB >> FB_XPARTS_LOG) / 64), dim3(64), 0, ts, buckets);
-                hipLaunchKernelGGL(k_msm_reduce2d_parts<7>, dim3(total / 64), dim3(64), 0, ts, (const uint8_t*)buckets, total, segsum);
-            }
-            {
-                StageTimer t(c, ST_WINDOW_SUM, ts);
-                hipLaunchKernelGGL(k_msm_reduce2d_window<7>, dim3(FB_R2D_WINDOWS, 2), dim3(R2D_TB), 0, ts, (const uint8_t*)segsum, halves, ticket,
-                                   wsum, tsum);
-            }
-            if (final_off_stream && !tails_off_stream) {   // overlap level 1: only the last chain leaves the stream
-                HIP_TRY(c, hipEventRecord(c->ev_bulk[par], st));
-                HIP_TRY(c, hipStreamWaitEvent(c->tail_streams[par], c->ev_bulk[par], 0));
-                ts = c->tail_streams[par];
-            }
-            {
-                StageTimer t(c, ST_FINAL, ts);
-                hipLaunchKernelGGL(k_fb_wsum, dim3(1), dim3(64), 0, ts, (const uint8_t*)wsum, (const uint8_t*)tsum, w2);
-                hipLaunchKernelGGL(k_msm_final_lp, dim3(1), dim3(64), 0, ts, (const uint8_t*)w2, 15, 2, res_xyzz, d_out_jac);
-            }
-            if (final_off_stream) {
-                HIP_TRY(c, hipEventRecord(c->ev_tail[par], c->tail_streams[par]));
-                c->tail_pending[par] = true;
-            }
-            return H2AGG_OK;
-        }
-        if (r2d) {
-            const uint32_t per_w = r2d_lc == 7 ? (uint32_t)R2D<7>::THREADS : (uint32_t)R2D<8>::THREADS;
-            if (!(dbg_skip & 1)) {
-                StageTimer t(c, ST_REDUCE, ts);
-                const uint32_t total = WT * per_w;
-                if (r2d_lc == 7)
-                    hipLaunchKernelGGL(k_msm_reduce2d_parts<7>, dim3(total / 64), dim3(64), 0, ts, (const uint8_t*)buckets, total, segsum);
-                else
-                    hipLaunchKernelGGL(k_msm_reduce2d_parts<8>, dim3(total / 64), dim3(64), 0, ts, (const uint8_t*)buckets, total, segsum);
-            }
-            if (!(dbg_skip & 2)) {
-                StageTimer t(c, ST_WINDOW_SUM, ts);
-                if (r2d_lc == 7)
-                    hipLaunchKernelGGL(k_msm_reduce2d_window<7>, dim3(WT, 2), dim3(R2D_TB), 0, ts, (const uint8_t*)segsum,
-                                       segsum + XYZZ_BYTES * (size_t)WT * per_w, ticket, wsum);
-                else
-                    hipLaunchKernelGGL(k_msm_reduce2d_window<8>, dim3(WT, 2), dim3(R2D_TB), 0, ts, (const uint8_t*)segsum,
-                                       segsum + XYZZ_BYTES * (size_t)WT * per_w, ticket, wsum);
-            }
-        } else {
-            if (!(dbg_skip & 1)) {
-                StageTimer t(c, ST_REDUCE, ts);
-                if (par4)
-                    hipLaunchKernelGGL(k_msm_reduce_segments_par4, dim3((4 * nseg_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ts,
-                                       buckets, p.NB, p.seg, p.spw, nseg_total, segsum);
-                else
-                    hipLaunchKernelGGL(k_msm_reduce_segments, dim3((nseg_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ts, buckets,
-                                       p.NB, p.seg, p.spw, nseg_total, segsum);
-            }
-            if (!(dbg_skip & 2)) {
-                StageTimer t(c, ST_WINDOW_SUM, ts);
-                if (par4)
-                    hipLaunchKernelGGL(k_msm_window_sum_par4, dim3(WT), dim3(PAR4_THREADS), 0, ts, segsum, p.spw, wsum);
-                else
-                    hipLaunchKernelGGL(k_msm_window_sum, dim3(WT), dim3(BLOCK), 0, ts, segsum, p.spw, wsum);
-            }
-        }
-        if (final_off_stream && !tails_off_stream) {   // overlap level 1: only the Horner tail leaves the stream
-            HIP_TRY(c, hipEventRecord(c->ev_bulk[par], st));
-            HIP_TRY(c, hipStreamWaitEvent(c->tail_streams[par], c->ev_bulk[par], 0));
-            ts = c->tail_streams[par];
-        }
-        if (!(dbg_skip & 4)) {
-            StageTimer t(c, ST_FINAL, ts);
-            // the Horner chain in the limb-parallel form (lp_kernels.hpp): 1.2 instead of 2.0 us per doubling
-            static const bool final_par4 = knob("H2AGG_FINAL") && !strcmp(knob("H2AGG_FINAL"), "par4");
-            if (final_par4)
-                hipLaunchKernelGGL(k_msm_final, dim3(batch), dim3(64), 0, ts, wsum, p.c, W1, (batch > 1 && !split) ? (uint8_t*)nullptr : res_xyzz,
-                                   d_out_jac);
-            else
-                hipLaunchKernelGGL(k_msm_final_lp, dim3(batch), dim3(64), 0, ts, wsum, p.c, W1, (batch > 1 && !split) ? (uint8_t*)nullptr : res_xyzz,
-                                   d_out_jac);
-        }
-        if (final_off_stream) {
-            HIP_TRY(c, hipEventRecord(c->ev_tail[par], c->tail_streams[par]));
-            c->tail_pending[par] = true;
-        }
-        return H2AGG_OK;
-    };
-    // deferral needs another MSM to carry it; a full per-stage profiling pass keeps every stage inside its own call
-    static const bool defer_env_off = knob("H2AGG_DEFER_TAILS") && !strcmp(knob("H2AGG_DEFER_TAILS"), "0");
-    // (and it only pays from 2^20 points on — measured, profiles/r02_sweeps.txt: below that the tail is a large share of the
-    // MSM and wants to start at once; the two multi_exps of an evaluation in particular)
-    // (not for the fixed-base levels of big tables: their sort's whole-CU workgroups collide with a tail either way — a tail always
-    // ends up beside some later MSM's sort, profiles/r05_sweeps.txt section 1(g) — and the batch of 16 x 2^22 measures 71.6 ms with
-    // the tail launched at once against 72.5 deferred)
-    if (tails_off_stream && !defer_env_off && !(c->profiling && c->prof_only < 0) && n >= ((size_t)1 << 20) && !fbdm) {
-        c->deferred_tail = tail_fn;
-    } else {
-        TRY(tail_fn(false));
-    }
-    // the slot (buckets / segsum / wsum / XYZZ result) rotates on every MSM, overlap or not: a caller may queue
-    // two MSMs and read both results afterwards (evaluate_multiopen_proof does)
-    c->parity = (c->parity + 1) % h2agg_ctx::TAIL_SLOTS;
-    debug_sync(8);
-    HIP_TRY(c, hipGetLastError());
-    profile_end_call(c);
-    return H2AGG_OK;
-}
+#include "msm_run.inc"
 
 int set_identity_jac(uint8_t out[96]) {
     memset(out, 0, 96);
@@ -1981,32 +1323,35 @@ int h2agg_g1_msm_device_async(h2agg_ctx* c, uint64_t handle, const void* d_scala
     // slice's bulk) and add the slices' results.
     if (it->second.pre && !c->cfg_c) {   // fixed-base levels (h2agg_bases_precompute); an explicit window_bits overrides
         const PreTable pt{it->second.pre, it->second.n, it->second.pre_c, it->second.pre_W};
-        if ((size_t)pt.W * n < ((size_t)1 << 32))
-            return msm_run(c, it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac, 1, nullptr, &pt);
+        if ((size_t)pt.W * n < ((size_t)1 << 32)) {
+            MsmCall call{it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac};
+            call.pre = &pt;
+            return msm_run(c, call);
+        }
     }
     const size_t SLICE = (size_t)1 << 22;
-    const bool no_id = it->second.no_identity;
-    if (n <= SLICE) return msm_run(c, it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac, 1, endo, nullptr, 0, no_id);
+    MsmCall call{it->second.d, (const uint8_t*)d_scalars, n, (uint8_t*)d_out_jac};
+    call.d_endo_x = endo;
+    call.no_identity = it->second.no_identity;
+    if (n <= SLICE) return msm_run(c, call);
     // The slices share ONE bucket set (chain modes of msm_run): every slice adds its points to the sums the buckets already
     // hold, and only the last one is followed by the bucket reduction / window sums / Horner tail.
     const size_t nsl = (n + SLICE - 1) / SLICE;
     const bool was_overlap = c->tail_overlap;
-    const int was_level = c->overlap_level;
-    c->tail_overlap = true;
-    c->overlap_level = 2;
-    c->chain_n = n;
-    c->chain_glv = false;
-    int rc = H2AGG_OK;
-    for (size_t k = 0; k < nsl && rc == H2AGG_OK; ++k) {
-        const size_t off = k * SLICE, m = n - off < SLICE ? n - off : SLICE;
-        c->chain = k == 0 ? CHAIN_FIRST : (k + 1 == nsl ? CHAIN_LAST : CHAIN_MID);
-        rc = msm_run(c, it->second.d + 64 * off, (const uint8_t*)d_scalars + 32 * off, m, (uint8_t*)d_out_jac, 1, endo + 32 * off,
-                     nullptr, 0, no_id);
+    {
+        OverlapScope overlap(c);
+        call.chain_n = n;
+        call.chain_glv = false;
+        for (size_t k = 0; k < nsl; ++k) {
+            const size_t off = k * SLICE;
+            call.d_bases = it->second.d + 64 * off;
+            call.d_scalars = (const uint8_t*)d_scalars + 32 * off;
+            call.d_endo_x = endo + 32 * off;
+            call.n_base = n - off < SLICE ? n - off : SLICE;
+            call.chain = k == 0 ? CHAIN_FIRST : (k + 1 == nsl ? CHAIN_LAST : CHAIN_MID);
+            TRY(msm_run(c, call));
+        }
     }
-    c->chain = CHAIN_OFF;
-    c->tail_overlap = was_overlap;
-    c->overlap_level = was_level;
-    TRY(rc);
     if (!was_overlap) TRY(join_tails(c));   // without overlap mode the caller's stream orders the result
     return H2AGG_OK;
 } catch (const std::bad_alloc&) {
@@ -2055,20 +1400,21 @@ int h2agg_g1_msm_device_batch_async(h2agg_ctx* c, uint64_t handle, const void* d
     const uint8_t* endo = nullptr;
     TRY(table_endo(c, it->second, &endo));
     const bool was_overlap = c->tail_overlap;
-    const int was_level = c->overlap_level;
-    if (one_by_one && batch > 1) {
-        c->tail_overlap = true;
-        c->overlap_level = 2;
+    {
+        OverlapScope overlap(c, one_by_one && batch > 1);
+        MsmCall call;
+        call.d_bases = it->second.d;
+        call.n_base = n;
+        call.d_endo_x = use_pre ? nullptr : endo;
+        call.pre = use_pre ? &pt : nullptr;
+        call.no_identity = !use_pre && it->second.no_identity;
+        for (size_t q = 0; q < batch; q += per) {
+            call.d_scalars = (const uint8_t*)d_scalars + 32 * n * q;
+            call.d_out_jac = (uint8_t*)d_out_jac + 96 * q;
+            call.batch = (uint32_t)(batch - q < per ? batch - q : per);
+            TRY(msm_run(c, call));
+        }
     }
-    int rc = H2AGG_OK;
-    for (size_t q = 0; q < batch && rc == H2AGG_OK; q += per) {
-        const size_t b = batch - q < per ? batch - q : per;
-        rc = msm_run(c, it->second.d, (const uint8_t*)d_scalars + 32 * n * q, n, (uint8_t*)d_out_jac + 96 * q, (uint32_t)b,
-                     use_pre ? nullptr : endo, use_pre ? &pt : nullptr, 0, !use_pre && it->second.no_identity);
-    }
-    c->tail_overlap = was_overlap;
-    c->overlap_level = was_level;
-    TRY(rc);
     if (one_by_one && batch > 1 && !was_overlap) TRY(join_tails(c));   // without overlap mode the caller's stream orders the results
     return H2AGG_OK;
 } catch (const std::bad_alloc&) {
@@ -2197,7 +1543,7 @@ int msm_host(h2agg_ctx* c, const uint8_t* bases, size_t stride, const uint8_t* s
         else
             hipLaunchKernelGGL(k_bases_to_mont, dim3(grid_for(c, n)), dim3(BLOCK), 0, c->stream, (const uint8_t*)c->in_a.p, n,
                                (uint8_t*)c->tmp_bases.p, c->d_flags);
-        TRY(msm_run(c, (const uint8_t*)c->tmp_bases.p, (const uint8_t*)c->in_b.p, n, c->d_res_jac));
+        TRY(msm_run(c, MsmCall{(const uint8_t*)c->tmp_bases.p, (const uint8_t*)c->in_b.p, n, c->d_res_jac}));
         return fetch_result_jac(c, out);
     }
     TRY(ensure(c, c->out, 96 * MSM_MAX_SLICES));
@@ -2205,21 +1551,19 @@ int msm_host(h2agg_ctx* c, const uint8_t* bases, size_t stride, const uint8_t* s
     HIP_TRY(c, hipEventRecord(c->ev_ready, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_ready, 0));
     const size_t per = (n + nslices - 1) / nslices;
-    const bool was_overlap = c->tail_overlap;
-    const int was_level = c->overlap_level;
-    c->tail_overlap = true;
-    c->overlap_level = 2;
     // The slices share one bucket set (chain modes of msm_run): slice k only sorts its keys and adds its points to the bucket
     // sums; ONE reduction / window-sum / Horner chain follows the last slice — that chain (0.6-0.9 ms of pure latency) is what
     // is left exposed behind the last byte of the transfer, so the slices can be small.  H2AGG_PCIE_CHAIN=0: the earlier
     // scheme (every slice a whole MSM, results added) for A/B runs.
     const int chain_glv_env = c->dbg_pcie_glv;
+    MsmCall call;
     if (chained) {
-        c->chain_n = n;
-        c->chain_glv = chain_glv_env ? chain_glv_env > 0 : (c->cfg_glv >= 0 && n < ((size_t)1 << 22));
+        call.chain_n = n;
+        call.chain_glv = chain_glv_env ? chain_glv_env > 0 : (c->cfg_glv >= 0 && n < ((size_t)1 << 22));
     }
     int rc = H2AGG_OK;
     size_t done = 0, k = 0;
+    OverlapScope overlap(c);
     for (; done < n && rc == H2AGG_OK; done += per, ++k) {
         const size_t m = n - done < per ? n - done : per;
         chaos_wait(16, c->copy_stream);
@@ -2246,7 +1590,7 @@ int msm_host(h2agg_ctx* c, const uint8_t* bases, size_t stride, const uint8_t* s
                                    (const uint8_t*)c->in_a.p + 64 * done, m, (uint8_t*)c->tmp_bases.p + 64 * done, c->d_flags);
         };
         if (chained) {
-            c->chain = done == 0 ? CHAIN_FIRST : (done + per >= n ? CHAIN_LAST : CHAIN_MID);
+            call.chain = done == 0 ? CHAIN_FIRST : (done + per >= n ? CHAIN_LAST : CHAIN_MID);
             hipEvent_t ev_bases = c->ev_copy[k];
             c->bases_hook = [=](hipStream_t st) -> int {
                 HIP_TRY(c, hipStreamWaitEvent(st, ev_bases, 0));
@@ -2256,13 +1600,14 @@ int msm_host(h2agg_ctx* c, const uint8_t* bases, size_t stride, const uint8_t* s
         } else {
             convert(c->stream);
         }
-        rc = msm_run(c, (const uint8_t*)c->tmp_bases.p + 64 * done, (const uint8_t*)c->in_b.p + 32 * done, m,
-                     chained ? c->d_res_jac : (uint8_t*)c->out.p + 96 * k);
+        call.d_bases = (const uint8_t*)c->tmp_bases.p + 64 * done;
+        call.d_scalars = (const uint8_t*)c->in_b.p + 32 * done;
+        call.n_base = m;
+        call.d_out_jac = chained ? c->d_res_jac : (uint8_t*)c->out.p + 96 * k;
+        rc = msm_run(c, call);
         c->bases_hook = nullptr;
     }
-    c->chain = CHAIN_OFF;
-    c->tail_overlap = was_overlap;
-    c->overlap_level = was_level;
+    overlap.restore();
     TRY(rc);
     TRY(join_tails(c));
     if (!chained)
@@ -2302,7 +1647,7 @@ int h2agg_eval_flat(h2agg_ctx* c, const uint8_t* pts, const uint8_t* scalars, co
     TRY(clear_flags(c));
     hipLaunchKernelGGL(k_bases_to_mont, dim3(grid_for(c, m)), dim3(BLOCK), 0, c->stream, (const uint8_t*)c->in_a.p, m,
                        (uint8_t*)c->tmp_bases.p, c->d_flags);
-    TRY(msm_run(c, (const uint8_t*)c->tmp_bases.p, (const uint8_t*)c->in_b.p, m, nullptr));
+    TRY(msm_run(c, MsmCall{(const uint8_t*)c->tmp_bases.p, (const uint8_t*)c->in_b.p, m, nullptr}));
     TRY(join_tails(c));
     hipLaunchKernelGGL(k_eval_tail, dim3(1), dim3(BLOCK), 0, c->stream, (const uint8_t*)c->d_res_xyzz,
                        (const uint8_t*)c->in_c.p, k, c->d_res_jac, c->d_flags);

@@ -235,7 +235,9 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
     if (split) {
         const size_t mt = m[0] + m[1];
         // gather + Montgomery form + beta * x + GLV decomposition in one launch (the plan says whether the last two apply)
-        const bool glv = make_plan(c, mt, 2).glv;
+        MsmCall call{(const uint8_t*)c->sch_bases[0].p, (const uint8_t*)c->sch_scalars[0].p, mt, nullptr};
+        call.split = (uint32_t)m[0];
+        const bool glv = msm_route(c, call).p.glv;
         const unsigned g = (unsigned)((mt + BLOCK - 1) / BLOCK);
         if (glv) {
             TRY(ensure(c, c->sch_endo, mt * 32));
@@ -247,8 +249,8 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
                                (const uint32_t*)(d + off_idx[0]), (const uint8_t*)(d + off_pts[0]), (uint32_t)mt,
                                (uint8_t*)c->sch_scalars[0].p, (uint8_t*)c->sch_bases[0].p, (uint8_t*)nullptr, c->d_flags);
         }
-        TRY(msm_run(c, (const uint8_t*)c->sch_bases[0].p, (const uint8_t*)c->sch_scalars[0].p, mt, nullptr, 1,
-                    glv ? (const uint8_t*)c->sch_endo.p : nullptr, nullptr, (uint32_t)m[0]));
+        call.d_endo_x = glv ? (const uint8_t*)c->sch_endo.p : nullptr;
+        TRY(msm_run(c, call));
         for (int s = 0; s < 2; ++s) {
             sc->side_xyzz[s] = c->d_res_xyzz + XYZZ_BYTES * s;
             sc->side_pns[s] = d + off_pns[s];
@@ -262,7 +264,7 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
                            (uint8_t*)c->sch_scalars[s].p);
         hipLaunchKernelGGL(k_bases_to_mont, dim3(grid_for(c, m[s])), dim3(BLOCK), 0, st,
                            (const uint8_t*)(d + off_pts[s]), m[s], (uint8_t*)c->sch_bases[s].p, c->d_flags);
-        TRY(msm_run(c, (const uint8_t*)c->sch_bases[s].p, (const uint8_t*)c->sch_scalars[s].p, m[s], nullptr));
+        TRY(msm_run(c, MsmCall{(const uint8_t*)c->sch_bases[s].p, (const uint8_t*)c->sch_scalars[s].p, m[s], nullptr}));
         sc->side_xyzz[s] = c->d_res_xyzz;   // this MSM's slot
         sc->side_pns[s] = d + off_pns[s];
         sc->side_k[s] = k[s];
@@ -645,14 +647,10 @@ int h2agg_evaluate_multiopen_proof(h2agg_schema* sc, uint32_t w_x, uint32_t w_g,
     // the two multi_exps always overlap (the second one's sort + accumulation under the first one's bucket
     // reduction and Horner tail), whatever the context's setting for back-to-back standalone MSMs: both are
     // joined before this call returns
-    const bool was_overlap = c->tail_overlap;
-    const int was_level = c->overlap_level;
-    c->tail_overlap = true;
-    c->overlap_level = 2;
-    const int rc_launch = eval_launch_sides(sc, L, 2, extra_pts, extra, prepared ? &P : nullptr);
-    c->tail_overlap = was_overlap;
-    c->overlap_level = was_level;
-    TRY(rc_launch);
+    {
+        OverlapScope overlap(c);
+        TRY(eval_launch_sides(sc, L, 2, extra_pts, extra, prepared ? &P : nullptr));
+    }
     lap("launch");
     TRY(join_tails(c));
     // scalar-less points (evaluation.rs:198-200) + to_value (verify.rs:730-731), both sides in one launch

@@ -32,7 +32,7 @@ int seg_msm_run(h2agg_ctx* c, const uint8_t* d_bases, const uint8_t* d_scalars, 
     while (s < S) {
         const size_t len = (size_t)(seg[s + 1] - seg[s]);
         if (len > longest) {
-            TRY(msm_run(c, d_bases + 64 * seg[s], d_scalars + 32 * seg[s], len, d_out_jac + 96 * s));
+            TRY(msm_run(c, MsmCall{d_bases + 64 * seg[s], d_scalars + 32 * seg[s], len, d_out_jac + 96 * s}));
             ++s;
             continue;
         }

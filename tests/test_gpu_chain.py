@@ -1,4 +1,4 @@
-"""GPU: slices of ONE multi_exp that share a bucket set (`msm_run`'s chain modes in csrc/h2agg.hip): the host-buffer MSM
+"""GPU: slices of ONE multi_exp that share a bucket set (`msm_run`'s chain modes in csrc/msm_run.inc): the host-buffer MSM
 (`h2agg_g1_msm`, the call behind ArithEccChip::multi_exp in the drop-in, mock/arith/ecc.rs:106-129) cuts its input into slices
 that cross PCIe while the previous one is accumulated; only the last slice is followed by the bucket reduction / Horner tail.
 Every slice resumes the bucket sums the earlier ones left — including buckets that are over-long (chunked path) in some slices

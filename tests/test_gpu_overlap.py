@@ -3,6 +3,8 @@ segment / window-sum regions were cut out of one allocation at par * (this MSM's
 could write into the region a large MSM's tail was still reading), plus the sticky status word of asynchronous calls.
 
 Every expected value is (sum_{i<n} k_i s_i) * G from the Python oracle."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -103,6 +105,45 @@ def test_overlap_mode_alternating_sizes(eng, level):
     finally:
         eng.msm_set_tail_overlap(0)
         eng.bases_free(table)
+
+
+@functools.lru_cache(maxsize=None)
+def _growth_workload():
+    """computed once for both levels: (base scalars, MSM scalars, expected points of the first 2^20 and of all the pairs)"""
+    n0, n1 = 1 << 20, (1 << 20) + (1 << 18)
+    ks, k_np = _workload(n1, 141)
+    ss, s_np = _workload(n1, 142)
+    t0 = sum(k * s for k, s in zip(ks[:n0], ss[:n0]))
+    t1 = t0 + sum(k * s for k, s in zip(ks[n0:], ss[n0:]))
+    return k_np, s_np, _expected(t0), _expected(t1)
+
+
+@pytest.mark.parametrize("level", [2, 3])
+def test_deferred_tail_forced_out_by_workspace_growth(pkg, level):
+    """A tail that waits for the next MSM (overlap level >= 2, 2^20 points) is launched from INSIDE that MSM's call when the call
+    has to replace a workspace buffer: on a fresh context the second MSM (2^20 + 2^18 points) needs more than the first one's
+    buffers with their 12.5 % head-room hold, and a grow-only buffer is only replaced behind everything queued or still to be
+    queued that may refer to it.  Both results must be right."""
+    n0, n1 = 1 << 20, (1 << 20) + (1 << 18)
+    k_np, s_np, want0, want1 = _growth_workload()
+    dev = torch.device("cuda", 0)
+    d_k = torch.from_numpy(k_np.copy()).to(dev)
+    d_s = torch.from_numpy(s_np.copy()).to(dev)
+    d_out = torch.zeros((2, 96), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    e = pkg.H2Agg(0)
+    try:
+        table = e.bases_generate(d_k.data_ptr(), n1)
+        e.msm_set_tail_overlap(level)
+        e.g1_msm_device_async(table, d_s.data_ptr(), n0, d_out[0].data_ptr())
+        e.g1_msm_device_async(table, d_s.data_ptr(), n1, d_out[1].data_ptr())
+        e.synchronize()
+        aff = e.g1_batch_to_affine(bytes(d_out.cpu().numpy().tobytes()))
+        assert aff[:64] == want0
+        assert aff[64:128] == want1
+        e.bases_free(table)
+    finally:
+        e.close()
 
 
 def test_host_sliced_msm_with_short_last_slice(eng):
