@@ -247,7 +247,7 @@ struct h2agg_ctx {
     DevBuf sch_regs, sch_in, sch_scalars[2], sch_bases[2], sch_endo;
     uint8_t* h_stage = nullptr;
     size_t h_stage_cap = 0;
-    uint8_t* h_down = nullptr;        // page-locked landing block of the from-bytes call's downloads (csrc/verifier.inc)
+    uint8_t* h_down = nullptr;        // page-locked landing block of the from-bytes call's downloads (csrc/verify_run.inc)
     size_t h_down_cap = 0;
     const void* sch_owner = nullptr;  // the schema whose tape sch_regs reflects
     struct AggPlanCache* agg_plans = nullptr;   // recorded aggregations kept for the next call of the same shape (csrc/verifier.inc)
@@ -1990,6 +1990,7 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "seg_msm.inc"
 #include "comm.inc"
 #include "verifier.inc"
+#include "verify_run.inc"
 #include "fr_host.inc"
 #include "params.inc"
 #include "fr_fft.inc"

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: a stand-in for librccl.so.1 that lets every "rank" of a communicator live on ONE device, so that the
-// multi-rank branches of the library (csrc/comm.inc, csrc/verifier.inc shard_allgather) can run on a one-GPU box.  The real
+// multi-rank branches of the library (csrc/comm.inc, csrc/verify_run.inc ShardExchange::allgather) can run on a one-GPU box.  The real
 // RCCL refuses two ranks on one device.  Only the entry points csrc/comm.inc resolves.  Not part of the product.
 //
 // What it keeps of RCCL's contract — the part the library relies on:

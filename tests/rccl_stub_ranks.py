@@ -3,8 +3,8 @@
     python tests/rccl_stub_ranks.py <RCCL stand-in .so> <world> <ok | fail1 | fail2 | fail3 | fail4> [threads | procs] [loops]
 
 h2agg_verify_aggregation_sharded with shard->allgather = NULL — the library's OWN transport: h2agg_comm_init_rank, then both
-exchanges as ncclAllGather on the context's stream between a host-to-device and a device-to-host copy (csrc/verifier.inc
-shard_allgather) — at world > 1 on a one-GPU box.  RCCL is tests/cpp/rccl_stub.cpp (stream-ordered all-gather; see its
+exchanges as ncclAllGather on the context's stream between a host-to-device and a device-to-host copy (csrc/verify_run.inc
+ShardExchange::allgather) — at world > 1 on a one-GPU box.  RCCL is tests/cpp/rccl_stub.cpp (stream-ordered all-gather; see its
 header), named to the library with H2AGG_RCCL_LIB; this process never imports torch.
 
   threads   the ranks are threads of this process, one context each

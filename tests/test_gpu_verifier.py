@@ -1,5 +1,5 @@
-"""GPU: the verifier-params pipeline + aggregation driver of the product (csrc/verifier.inc through h2agg_verify_aggregation)
-against the oracle restatement (oracle/verifier.py) on proofs made by the trapdoor prover (tests/toy_prover.py).
+"""GPU: the verifier-params pipeline + aggregation driver of the product (csrc/verifier.inc, csrc/verify_run.inc through
+h2agg_verify_aggregation) against the oracle restatement (oracle/verifier.py) on proofs made by the trapdoor prover (tests/toy_prover.py).
 
 The product gets ONLY what the reference's entry point gets — verifying-key descriptions, instance values, transcript
 bytes, [s]_2 and [1]_2 — derives every challenge on the device (Poseidon), evaluates gates / permutation / lookup /
@@ -322,3 +322,50 @@ def test_phase_split_prewake_and_tape_keys_do_not_change_the_result(eng, pkg):
         eng.debug_configure("tape_lds", 1)
         eng.transcript_configure("auto")
     assert eng.last_phases() != ""
+
+
+_PADDED = {}
+
+
+def _zero_column_batch():
+    """SHAPES[0], 2 proofs, the second proof's instance column all zero; made once, with the oracle's result"""
+    if not _PADDED:
+        from tests import toy_prover as T
+        rng = O.SplitMix64(0xB3)
+        dlogs = {}
+        setup = T.Setup(5, rng.fr(), 16)
+        cs = T.make_constraint_system(rng, dlogs=dlogs, **SHAPES[0])
+        c = V.CircuitProofs("circuit0", cs, setup.g_lagrange)
+        for i, col in enumerate(([rng.fr() for _ in range(3)], [0, 0, 0])):
+            c.proofs.append(([[col]], T.prove(cs, setup, rng, [[col]], dlogs, "%s_p%d" % (c.name, i))))
+        want_l, want_r, _plain, _commits, want_lam = V.verify_aggregation_proofs_in_chip(S.OracleEccChip(), [c])
+        _PADDED["batch"] = (setup, c, S.final_pair_bytes(want_l, want_r), O.fe_to_bytes(want_lam))
+    return _PADDED["batch"]
+
+
+def test_non_uniform_instance_lengths_equal_the_uniform_call(eng, pkg, backend):
+    """An instance column is committed as sum_i v_i L_i (verify.rs:574-649), so explicit trailing zeros change nothing.  Equal
+    column lengths go through ONE batched MSM; padding one proof's column makes the lengths differ and sends every (proof,
+    column) through an MSM of its own, and an all-zero column passed with length 0 takes the identity upload (None =>
+    assign_const(identity), :638).  Every variant must give the unpadded call's pair and lambda byte for byte, the oracle's."""
+    setup, c, want_pair, want_lam = _zero_column_batch()
+    ver = importlib.import_module(entry.PKG_NAME + ".verifier")
+    table = eng.bases_upload(b"".join(O.aff_to_bytes(p) for p in setup.g_lagrange))
+    vk = ver.VerifyingKey(eng, ver.encode_vk(c.cs, O.aff_to_bytes))
+    (inst0, data0), (inst1, data1) = c.proofs
+    col0, col1 = (b"".join(O.fe_to_bytes(v) for v in inst[0][0]) for inst in (inst0, inst1))
+    zero = bytes(32)
+    assert col1 == 3 * zero
+
+    def call(a, b):
+        return ver.verify_aggregation(eng, [(vk, c.name, table, [([a], data0), ([b], data1)])], g2b(setup.s_g2), g2b(setup.g2))
+
+    try:
+        plain = call(col0, col1)                                   # lengths 3, 3: the uniform batch
+        assert (plain[0] + plain[1], plain[2], plain[3]) == (want_pair, want_lam, True)
+        assert call(col0 + 2 * zero, col1) == plain                # 5, 3: one MSM per column
+        assert call(col0 + zero, b"") == plain                     # 4, 0: ... and the identity upload
+        assert call(col0, b"") == plain                            # 3, 0
+    finally:
+        vk.close()
+        eng.bases_free(table)

@@ -6,7 +6,7 @@ What runs through the stand-in, all inside the C ABI:
   * h2agg_comm_create + h2agg_allgather_add_points with nctx == world (ncclCommInitAll, ncclGroupStart / ncclAllGather per
     context / ncclGroupEnd; csrc/comm.inc) — a C++ driver, the stand-in found under its soname librccl.so.1;
   * h2agg_verify_aggregation_sharded with shard->allgather = NULL (h2agg_comm_init_rank + both exchanges as ncclAllGather on
-    the context's stream; csrc/verifier.inc shard_allgather) with the ranks as THREADS and as PROCESSES (hipIpc), named to the
+    the context's stream; csrc/verify_run.inc ShardExchange::allgather) with the ranks as THREADS and as PROCESSES (hipIpc), named to the
     library with H2AGG_RCCL_LIB — verify.rs:909-913, :924 (lambda) and :926-938 (the fold), SURVEY.md 8(e);
   * bench.py --gpus 2 with both ranks on device 0: `aggregate` and `from_bytes_sharded` over the library's communicator of TWO
     ranks in two processes (`rccl_ranks: 2`), equal to the one-rank recomputation.
