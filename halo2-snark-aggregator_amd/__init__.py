@@ -162,6 +162,7 @@ def load_library():
         "h2agg_params_setup": (i32, [ctxp, C.c_uint, u8p, C.POINTER(u64), C.POINTER(u64)]),
         "h2agg_fr_fft": (i32, [ctxp, vp, C.c_uint, i32, u8p, vp]),
         "h2agg_fr_fft_device": (i32, [ctxp, vp, C.c_uint, i32, u8p, vp]),
+        "h2agg_fr_fft_batch": (i32, [ctxp, vp, C.c_size_t, C.c_uint, i32, u8p, vp]),
         "h2agg_fr_poly_eval": (i32, [ctxp, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, vp]),
         "h2agg_fr_poly_eval_device": (i32, [ctxp, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, vp]),
         "h2agg_fr_poly_divide": (i32, [ctxp, vp, C.c_uint, u8p, vp, vp]),
@@ -523,6 +524,15 @@ class H2Agg:
             _need(shift, 32, "shift")
         return self._in_place_or_new(
             data, lambda src, dst: self._lib.h2agg_fr_fft(self._ctx, src, k, int(bool(inverse)), shift, dst))
+
+    def fr_fft_batch(self, data, k: int, inverse: bool = False, shift: Optional[bytes] = None) -> bytes:
+        """fr_fft of every column of a slab [m][2^k] in one call (h2agg_fr_fft_batch): m = len(data) / (32 * 2^k), column j of
+        the result is fr_fft of column j.  A bytearray is transformed in place and returned; bytes give a new bytes object."""
+        m = self._slab(data, k)
+        if shift is not None:
+            _need(shift, 32, "shift")
+        return self._in_place_or_new(
+            data, lambda src, dst: self._lib.h2agg_fr_fft_batch(self._ctx, src, m, k, int(bool(inverse)), shift, dst))
 
     def fr_fft_device(self, d_in_ptr: int, k: int, inverse: bool, shift: Optional[bytes], d_out_ptr: int):
         """h2agg_fr_fft_device: 2^k elements in device memory, queued on the context's stream (no synchronisation);

@@ -31,6 +31,15 @@
 // shift^j is the same pair of tables, built per call.  The tables come from k_fr_powers: k_fr_affine_powers' algorithm with
 // the constants as kernel arguments — that kernel reads them from a device block which a host copy fills, and a second
 // transform queued behind a first must not rewrite the block the first one's launch has not read yet.
+//
+// Batch.  A launch transforms m columns of 2^k elements, one pass of all of them: the tile index space of a pass is
+// m * 2^(k - width), tile T being tile T & (2^(k - width) - 1) of column T >> (k - width).  Digit, jrest, twiddle exponent and
+// the last pass's digit reversal act on the within-column tile; only the addresses know the column.  A workgroup's C tile
+// columns run on across column boundaries: at k = 7 one workgroup holds 16 whole transforms, and the last workgroup of a
+// launch may be partly empty.  The single transform is the batch of one.  The first pass reads its columns from a table of at
+// most FR_FFT_SEGS segments (base pointer, first column), each a contiguous slab of stride 2^k — by value in the kernel
+// arguments, for the reason above; the work array and the destination are contiguous slabs [m][2^k].  The shift table, the
+// twiddle tables, cvt and the FLAG_NONCANONICAL report are shared by all columns of a launch.
 #pragma once
 #include "g1_fft_kernels.hpp"
 
@@ -41,6 +50,8 @@ constexpr unsigned FR_FFT_TILE_LOG = 11;    // elements a workgroup holds in LDS
 constexpr unsigned FR_FFT_TILE = 1u << FR_FFT_TILE_LOG;
 constexpr int FR_FFT_THREADS = 512;
 constexpr int FRW_TABLE = 13;               // base^(2^j), j < 13: the tables have at most 2^12 entries
+constexpr int FR_FFT_SEGS = 9;              // source slabs of one batched launch (the quotient's nine kinds of polynomial)
+constexpr unsigned FR_FFT_BATCH_WORK_LOG = 23;   // a batch's work array: at most 2^23 elements (256 MiB), or one column
 
 struct FrPowersArgs {
     uint32_t pw[FRW_TABLE][8];   // base^(2^j), canonical
@@ -65,8 +76,10 @@ __global__ void __launch_bounds__(BLOCK) k_fr_powers(const FrPowersArgs args, ui
 }
 
 struct FrFftPass {
-    const uint8_t* src;
-    uint8_t* dst;
+    const uint8_t* seg_base[FR_FFT_SEGS];   // source slabs: columns seg_first[s] .. seg_first[s + 1] - 1 of the launch are the
+    uint32_t seg_first[FR_FFT_SEGS];        // columns of slab s from its base on; seg_first[0] = 0, an unused entry ~0
+    uint8_t* dst;                           // [m][2^k]
+    uint32_t m;                             // columns of this launch; m * 2^(k - width) < 2^32
     const uint8_t* tw_lo;   // Montgomery w^i, i < 2^tw_T
     const uint8_t* tw_hi;   // Montgomery w^(i * 2^tw_T)
     const uint8_t* sh_lo;   // Montgomery shift^i (forward) / shift^-i (inverse), i < 2^sh_T; null without a shift
@@ -115,13 +128,15 @@ FP_INLINE void fr_fft_lds_put(uint32_t* lds, uint32_t e, const Fr& v) {
     for (int i = 0; i < NL; ++i) lds[NL * e + i] = v.l[i];
 }
 
-// One pass (see the file header).  Workgroup b holds tiles b * C .. b * C + C - 1, C = FR_FFT_TILE >> width; element
-// (row, column) of the tile set is at LDS index row * C + column.  Every global index is < 2^k and every LDS index
-// < FR_FFT_TILE: rows < 2^width, columns < C, columns of tiles >= 2^(k - width) are skipped.
+// One pass (see the file header).  Workgroup b holds tiles b * C .. b * C + C - 1 of the batch's m * 2^(k - width), C =
+// FR_FFT_TILE >> width; element (row, column) of the tile set is at LDS index row * C + column.  Every global address is a
+// column's base (column < m) plus 32 g, g < 2^k, and every LDS index < FR_FFT_TILE: rows < 2^width, columns < C, columns of
+// tiles >= m * 2^(k - width) are skipped.
 __global__ void __launch_bounds__(FR_FFT_THREADS) k_fr_fft_pass(const FrFftPass p) {
     __shared__ uint32_t lds[NL * FR_FFT_TILE];
     const uint32_t lgC = FR_FFT_TILE_LOG - p.width, C = 1u << lgC;
-    const uint32_t ntiles = 1u << (p.k - p.width);
+    const uint32_t ctb = p.k - p.width, ctmask = (1u << ctb) - 1u;   // tiles of one column: 2^ctb
+    const uint32_t ntiles = p.m << ctb;
     const uint32_t tile0 = blockIdx.x * C;
     const uint32_t lbmask = (1u << p.lb) - 1u;
 
@@ -131,8 +146,8 @@ __global__ void __launch_bounds__(FR_FFT_THREADS) k_fr_fft_pass(const FrFftPass 
         // the last pass reads whole tiles (digit fastest); the others runs of C columns (column fastest)
         const uint32_t c = p.last ? idx >> p.width : idx & (C - 1u);
         const uint32_t d = p.last ? idx & ((1u << p.width) - 1u) : idx >> lgC;
-        const uint32_t t = tile0 + c;
-        if (t >= ntiles) continue;
+        if (tile0 + c >= ntiles) continue;
+        const uint32_t col = (tile0 + c) >> ctb, t = (tile0 + c) & ctmask;
         uint32_t g;
         if (p.last) {
             uint32_t pi = 0, rho = t;
@@ -145,7 +160,17 @@ __global__ void __launch_bounds__(FR_FFT_THREADS) k_fr_fft_pass(const FrFftPass 
         } else {
             g = ((t >> p.lb) << (p.width + p.lb)) | (d << p.lb) | (t & lbmask);
         }
-        Fr x = fp_load<FrParams>(p.src + 32 * (size_t)g);
+        const uint8_t* base = p.seg_base[0];
+        uint32_t at = col;
+        if (p.seg_first[1] != ~0u) {   // (uniform: one slab — the work array, a single transform — looks nothing up)
+#pragma unroll
+            for (int sg = 1; sg < FR_FFT_SEGS; ++sg)
+                if (col >= p.seg_first[sg]) {
+                    base = p.seg_base[sg];
+                    at = col - p.seg_first[sg];
+                }
+        }
+        Fr x = fp_load<FrParams>(base + (((size_t)at << p.k) + g) * 32);
         if (p.first) {
             if (!fp_is_canonical<FrParams>(x)) atomicOr(p.flags, FLAG_NONCANONICAL);
             Fr cv;
@@ -183,8 +208,8 @@ __global__ void __launch_bounds__(FR_FFT_THREADS) k_fr_fft_pass(const FrFftPass 
 #pragma unroll 1
     for (uint32_t idx = threadIdx.x; idx < FR_FFT_TILE; idx += FR_FFT_THREADS) {
         const uint32_t c = idx & (C - 1u), d = idx >> lgC;
-        const uint32_t t = tile0 + c;
-        if (t >= ntiles) continue;
+        if (tile0 + c >= ntiles) continue;
+        const uint32_t col = (tile0 + c) >> ctb, t = (tile0 + c) & ctmask;
         Fr v = fr_fft_lds_get(lds, idx);
         uint32_t g;
         if (p.last) {
@@ -197,7 +222,7 @@ __global__ void __launch_bounds__(FR_FFT_THREADS) k_fr_fft_pass(const FrFftPass 
             const uint32_t e = (d << p.hb) * jrest;   // < 2^k
             if (e) v = fp_mul<FrParams>(v, fr_fft_table(p.tw_lo, p.tw_hi, p.tw_T, e << p.tw_up));
         }
-        fp_store<FrParams>(p.dst + 32 * (size_t)g, v);
+        fp_store<FrParams>(p.dst + (((size_t)col << p.k) + g) * 32, v);
     }
 }
 

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <cassert>
 #include <csignal>
 #include <dlfcn.h>
 #include <unistd.h>
@@ -284,6 +285,7 @@ struct h2agg_ctx {
     DevBuf frfft_tw[2], frfft_shift, frfft_work;
     int frfft_tw_k[2] = {-1, -1};
     int dbg_fr_fft_local = 0;   // debug key fr_fft_local: radix-2 stages fused per pass (0 = FR_FFT_LOCAL)
+    int dbg_fr_fft_batch_chunk = 0;   // debug key fr_fft_batch_chunk: columns per set of launches of a batched transform (0 = by the work array)
     // KZG openings (csrc/poly_open.inc): the chunk values of every level above the coefficients, the queries / group lists of
     // the call in progress, the combined polynomials (then their quotients) of a multiopen, its Jacobian commitments
     DevBuf poly_work, poly_desc, poly_slab, poly_jac;
@@ -1748,6 +1750,10 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
     else if (k == "fr_fft_local") {                          // Fr FFT: radix-2 stages fused per pass, 1 .. 11 (0 = the default, 10)
         if (value < 0 || value > (int)FR_FFT_TILE_LOG) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_fft_local must be 0 or 1 .. 11");
         c->dbg_fr_fft_local = value;
+    }
+    else if (k == "fr_fft_batch_chunk") {                    // Fr FFT: a batch runs in chunks of this many columns (0 = as many as the work array holds)
+        if (value < 0) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_fft_batch_chunk must be >= 0");
+        c->dbg_fr_fft_batch_chunk = value;
     }
     else if (k == "fr_poly_chunk") {                         // KZG openings: log2 of the coefficients per workgroup, 3 .. 11 (0 = the default, 11)
         if (value != 0 && (value < (int)FR_CHUNK_PER_LOG || value > (int)FR_CHUNK_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_poly_chunk must be 0 or 3 .. 11");

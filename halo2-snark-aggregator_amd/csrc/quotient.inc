@@ -322,7 +322,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     TRY(fr_ensure(c, c->qt_work, 32 * l.total));
     TRY(fr_ensure(c, c->qt_prog, 4 * prog_words + 4));
     TRY(fr_ensure(c, c->qt_tab, fr_table_bytes(k)));
-    TRY(fr_ensure(c, c->frfft_work, (size_t)32 << K));
+    TRY(fr_ensure(c, c->frfft_work, std::max((size_t)32 << K, fr_fft_batch_work_bytes(l.polys, k))));
     TRY(fr_ensure(c, c->frfft_shift, fr_table_bytes(K)));
     if (K) {
         TRY(fr_fft_ensure_twiddles(c, K, 0));
@@ -352,26 +352,19 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     phases.mark(c, QtPhases::FORWARD);
     const uint32_t u = (uint32_t)n - vk.blinding_factors - 1u;
     hipLaunchKernelGGL(k_qe_lagrange_rows, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, lcoef, (uint32_t)n, u);
-    for (int t = 0; t < 3; ++t) TRY(fr_fft_queue(c, lcoef + t * col, k, 1, nullptr, lcoef + t * col));
-    // ---- the source of every column of the slab
-    std::vector<const uint8_t*> src(l.polys);
-    for (uint32_t i = 0; i < l.A; ++i) src[i] = in.advice + i * col;
-    for (uint32_t i = 0; i < l.F; ++i) src[l.fixed0 + i] = in.fixed + i * col;
-    for (uint32_t i = 0; i < l.I; ++i) src[l.instance0 + i] = in.instance + i * col;
-    for (uint32_t i = 0; i < l.P; ++i) src[l.sigma0 + i] = in.sigma + i * col;
-    for (uint32_t i = 0; i < l.sets; ++i) src[l.z0 + i] = in.perm_z + i * col;
-    for (uint32_t i = 0; i < l.L; ++i) {
-        src[l.lz0 + i] = in.lookup_z + i * col;
-        src[l.lap0 + i] = in.lookup_ap + i * col;
-        src[l.lsp0 + i] = in.lookup_sp + i * col;
+    {
+        const FrFftSeg rows3 = {lcoef, 3};
+        TRY(fr_fft_queue_batch(c, &rows3, 1, 3, k, 1, nullptr, lcoef));
     }
-    for (int t = 0; t < 3; ++t) src[l.l0 + t] = lcoef + t * col;
+    // ---- the sources of the slab's columns, in QtLayout's order: one transform launch per pass takes them all
+    const FrFftSeg src[FR_FFT_SEGS] = {{in.advice, l.A},    {in.fixed, l.F},     {in.instance, l.I},  {in.sigma, l.P}, {in.perm_z, l.sets},
+                                       {in.lookup_z, l.L},  {in.lookup_ap, l.L}, {in.lookup_sp, l.L}, {lcoef, 3}};
     const ph::HFr w_ext = fft_omega(K), zeta = qt_zeta();
     const dim3 rows((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
     ph::HFr s = zeta;
     for (uint32_t cs = 0; cs < cosets; ++cs, s = ph::mul(s, w_ext)) {
         if (cs) phases.mark(c, QtPhases::FORWARD);
-        for (uint32_t p = 0; p < l.polys; ++p) TRY(fr_fft_queue(c, src[p], k, 0, &s, cos + p * col, p != 0));
+        TRY(fr_fft_queue_batch(c, src, FR_FFT_SEGS, l.polys, k, 0, &s, cos));
         QeCoset q;
         q.cos = cos;
         q.acc_out = acc;

@@ -195,6 +195,45 @@ def _slab(cols, count: int, k: int, what: str):
     return b"".join(cols) if cols else None
 
 
+# ---------------------------------------------------------------------------------------------- domain conversions of a slab
+def _columns(cols, k: int, what: str) -> bytes:
+    """a non-empty list of 2^k-element columns -> one slab"""
+    cols = list(cols or [])
+    if not cols:
+        raise ValueError("%s must hold at least one column" % what)
+    return _slab(cols, len(cols), k, what)
+
+
+def _split(slab: bytes, k: int):
+    return [slab[at:at + (32 << k)] for at in range(0, len(slab), 32 << k)]
+
+
+def columns_lagrange_to_coeff(eng, cols, k: int):
+    """lagrange_to_coeff of every column of a list, in one call (h2agg_fr_fft_batch) -> a list of columns"""
+    return _split(eng.fr_fft_batch(_columns(cols, k, "evals"), k, inverse=True), k)
+
+
+def columns_coeff_to_lagrange(eng, cols, k: int):
+    """coeff_to_lagrange of every column of a list, in one call -> a list of columns"""
+    return _split(eng.fr_fft_batch(_columns(cols, k, "coeffs"), k), k)
+
+
+def columns_coeff_to_extended(eng, cols, k: int, extended_k: int, shift: bytes = ZETA):
+    """coeff_to_extended of every column of a list, in one call: every column is zero-padded to 2^extended_k -> a list of
+    columns of 2^extended_k evaluations"""
+    if extended_k < k:
+        raise ValueError("extended_k must be >= k")
+    cols = list(cols or [])
+    _columns(cols, k, "coeffs")
+    pad = bytes((32 << extended_k) - (32 << k))
+    return _split(eng.fr_fft_batch(b"".join(bytes(c) + pad for c in cols), extended_k, shift=shift), extended_k)
+
+
+def columns_extended_to_coeff(eng, cols, extended_k: int, shift: bytes = ZETA):
+    """extended_to_coeff of every column of a list, in one call -> a list of columns of all 2^extended_k coefficients"""
+    return _split(eng.fr_fft_batch(_columns(cols, extended_k, "evals"), extended_k, inverse=True, shift=shift), extended_k)
+
+
 def _challenges(vk, challenges):
     challenges = list(challenges or [])
     if len(challenges) != vk.shape["num_challenges"] or any(len(c) != 32 for c in challenges):

@@ -570,6 +570,18 @@ int h2agg_g2_batch_compress(const uint8_t* aff, size_t n, uint8_t* out);
 int h2agg_fr_fft(h2agg_ctx* ctx, const uint8_t* in, unsigned k, int inverse, const uint8_t shift[32], uint8_t* out);
 int h2agg_fr_fft_device(h2agg_ctx* ctx, const void* d_in, unsigned k, int inverse, const uint8_t shift[32], void* d_out);
 
+/* h2agg_fr_fft_batch — the transform above over a slab: `in` and `out` are host slabs [m][2^k] (pageable or from
+ * h2agg_host_alloc), column j at byte 32 * 2^k * j; out == in is allowed; synchronous.  Column j of `out` is byte for byte
+ * what h2agg_fr_fft returns for column j of `in` with the same k, inverse and shift.  All columns of a call share one shift
+ * table and every pass of the transform is one launch over all of them (in chunks of as many columns as the context's work
+ * array holds: DESIGN.md 5.8), which is what makes many small columns cheaper than as many calls.  This is what a prover does
+ * to all its Lagrange columns at once (lagrange_to_coeff of every advice column) and what h2agg_quotient does inside.
+ * Refusals: those of h2agg_fr_fft, and m == 0: H2AGG_ERR_INVALID.  The slab is staged whole (as h2agg_fr_poly_eval stages its
+ * slab): one the device cannot hold is H2AGG_ERR_NOMEM.  An element >= r in any column: H2AGG_ERR_NONCANONICAL from the call;
+ * `out` is then unspecified.  The context stays usable after any of them.  There is no _device twin yet. */
+int h2agg_fr_fft_batch(h2agg_ctx* ctx, const uint8_t* in, size_t m, unsigned k, int inverse, const uint8_t shift[32],
+                       uint8_t* out);
+
 /* ---- KZG openings: evaluation, division by (X - z), the GWC multiopen prover -------------------------------------------
  * Stand for: eval_polynomial and kate_division (halo2_proofs arithmetic.rs) and the prover of poly/kzg/multiopen/gwc
  * (prover.rs).  halo2_proofs is an unvendored git dependency of the reference: recalled from upstream, not pinned (DESIGN.md
@@ -759,7 +771,9 @@ int h2agg_fr_columns_compress_device(h2agg_ctx* ctx, const void* d_cols, size_t 
  *   h_i = the coefficients [i n, (i+1) n) of H, i < degree - 1 (higher ones are dropped, as extended_to_coeff truncates).
  *   For a satisfied circuit H = N / (X^n - 1) exactly; for any other input it is still this one answer.
  *   Work memory, kept in the context: one coset's values of every polynomial, nine more columns and the
- *   extended evaluations — (the number of input polynomials + 9) n + 2^(k+e) elements, not columns x 2^(k+e).
+ *   extended evaluations — (the number of input polynomials + 9) n + 2^(k+e) elements, not columns x 2^(k+e) — and the
+ *   transform's work array: max(2^(k+e), min((the number of input polynomials + 3) n, 2^23)) elements, so that a coset's
+ *   transforms are one launch per pass (h2agg_fr_fft_batch's rule) wherever that fits 256 MiB.
  *
  * The plain entry points are synchronous over host buffers (pageable or h2agg_host_alloc); the _device twins take DEVICE
  * memory and are queued on the context's stream with no synchronisation and no read-back (buffer rules: h2agg_fr_fft_device;
@@ -852,6 +866,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         inverse; the queued form then waits for its own events), for h2agg_last_phases
  *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
  *                         1024 elements then run the multi-pass paths
+ *       "fr_fft_batch_chunk" B  a batched transform (h2agg_fr_fft_batch, the transforms inside h2agg_quotient) runs in chunks of
+ *                         B columns, every pass of a chunk one launch (0 = the default: as many columns as the work array holds)
  *       "fr_poly_chunk" t the KZG opening kernels cut a polynomial into chunks of 2^t coefficients per workgroup, 3 .. 11 (0 = the
  *                         default, 11): inputs of 64 to 1024 coefficients then run the three- and four-level plans
  *       "fr_scan_chunk" t the grand-product kernels (batch inversion, running product) cut an array into chunks of 2^t elements

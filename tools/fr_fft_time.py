@@ -2,6 +2,7 @@
 """Timing of the Fr Fourier transform, device variant (h2agg_fr_fft_device), beside the two bounds it could sit at.
 
     python tools/fr_fft_time.py [--ks 12,16,20,22,24] > profiles/fr_fft.txt
+    python tools/fr_fft_time.py --batch --ks 12,16,20 >> profiles/fr_fft.txt
     rocprofv3 --kernel-trace --stats -- python tools/fr_fft_time.py --only 20      (k_fr_fft_pass's own line; on its own,
                                                                                    no counters in the run)
 
@@ -10,6 +11,16 @@ resident, the context runs on a stream of the caller, two events on that stream 
 after two warm-up transforms (which also build the twiddle tables and grow the work array); the figure is the median of
 five such brackets divided by REPS.  In place (d_out == d_in): a transform of random data is random data, so repeating
 it needs no reset.
+
+--batch: h2agg_fr_fft_batch against the same columns through h2agg_fr_fft, m in {1, 8, 34} columns at k in {12, 16, 20},
+forward with shift zeta (a coset's transforms).  The batch has no device-buffer twin yet, so these rows go through the host
+entry points, in place on one host buffer, and the two events bracket the staging copies as well as the launches — equally in
+every column of the table:
+  singles   m calls of h2agg_fr_fft, one column each (m copies in, m sets of launches, m copies out, m synchronisations)
+  chunk 1   one h2agg_fr_fft_batch call with the debug key fr_fft_batch_chunk = 1: the slab staged whole, one column per set of
+            launches — what of the gain over `singles` is the staging
+  batch     one h2agg_fr_fft_batch call: every pass one launch over all columns the work array holds
+The resident comparison is the quotient's `forward` phase (tools/quotient_time.py), which runs 34 columns per coset.
 
 Bounds printed beside each time:
   mem    passes x 64 n bytes (every pass reads and writes 32 B per element) at the rate of a device-to-device copy of the
@@ -23,6 +34,7 @@ Bounds printed beside each time:
          alone would carry.
 """
 import argparse
+import ctypes as C
 import os
 import statistics
 import sys
@@ -60,6 +72,7 @@ def products(k, local, shift):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="12,16,20,22,24")
+    ap.add_argument("--batch", action="store_true", help="h2agg_fr_fft_batch against m single calls (see the header)")
     ap.add_argument("--only", type=int, default=0, help="two warm-up transforms and one bracket at this k, forward, no shift")
     a = ap.parse_args()
     import torch
@@ -96,6 +109,48 @@ def main():
         torch.cuda.synchronize()
         return d
 
+    if a.batch:
+        reps = 3
+        print("# %s" % eng.describe())
+        print("# forward, shift zeta, host entry points in place; %d repetitions per bracket, median of 5 brackets; times in ms" % reps)
+        print("#  k    m    singles    chunk 1      batch   singles / batch   chunk 1 / batch")
+
+        def timed(f):
+            def one():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(reps):
+                    f()
+                e1.record(stream)
+                e1.synchronize()
+                return e0.elapsed_time(e1) / reps
+            f()
+            f()
+            return statistics.median(one() for _ in range(5))
+
+        for k in [int(x) for x in a.ks.split(",") if x]:
+            col = 32 << k
+            for m in (1, 8, 34):
+                buf = bytearray(resident(k).cpu().numpy().tobytes() * m)
+                views = [(C.c_char * col).from_buffer(buf, j * col) for j in range(m)]
+
+                def singles():
+                    for v in views:
+                        eng._check(eng._lib.h2agg_fr_fft(eng._ctx, C.addressof(v), k, 0, poly.ZETA, C.addressof(v)))
+
+                def batch():
+                    eng.fr_fft_batch(buf, k, False, poly.ZETA)
+
+                t_single = timed(singles)
+                eng.debug_configure("fr_fft_batch_chunk", 1)
+                t_chunk1 = timed(batch)
+                eng.debug_configure("fr_fft_batch_chunk", 0)
+                t_batch = timed(batch)
+                print("%4d  %3d  %9.4f  %9.4f  %9.4f   %15.2f   %15.2f" % (k, m, t_single, t_chunk1, t_batch, t_single / t_batch,
+                                                                          t_chunk1 / t_batch))
+                sys.stdout.flush()
+                del views, buf
+        return
     if a.only:
         d = resident(a.only)
         measure(lambda: eng.fr_fft_device(d.data_ptr(), a.only, False, None, d.data_ptr()))

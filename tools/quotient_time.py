@@ -19,7 +19,8 @@ brackets.
               2^(k+2) inverse transform and the copy of the pieces here)
   transforms  the same 4 x 34 shifted forward transforms of size 2^k, 3 plain inverse ones and one shifted inverse of size
               2^(k+2), queued through h2agg_fr_fft_device alone (that entry point exists in the parent commit): what of the
-              call is not new.  Each of these calls builds its own shift table; inside the quotient a coset shares one.
+              call is not new.  Each of these calls builds its own shift table and is its own set of launches; inside the
+              quotient a coset is one batched transform (fr_fft_queue_batch): one table, one launch per pass for all 34.
 """
 import argparse
 import os
