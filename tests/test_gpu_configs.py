@@ -21,19 +21,9 @@ import __graft_entry__ as entry
 from oracle import bn254 as O, cref
 from oracle import schema as S
 from tests.test_dist_gloo import make_proofs, reference_final_pair
+from tests.util import CEccChip
 
 pytestmark = pytest.mark.gpu
-
-
-class CEccChip(S.OracleEccChip):
-    """MockEccChip with multi_exp = oracle_multi_exp_naive (the reference's loop, mock/arith/ecc.rs:106-129, in C)"""
-
-    def multi_exp(self, ctx, points, scalars):
-        ctx.point_list = [O.debug_fmt(p) for p in points]
-        n = len(points)
-        out = cref.multi_exp_naive(b"".join(O.aff_to_bytes(p) for p in points),
-                                   b"".join(O.fe_to_bytes(s) for s in scalars), n)
-        return O.aff_from_bytes(out)
 
 
 def oracle_pair(specs, lam, first_commitments=None):

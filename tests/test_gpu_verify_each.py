@@ -56,12 +56,12 @@ class Product:
         self.eng.bases_free(self.table)
 
 
-def oracle_pairs(circuits):
-    """verify_single_proof_in_chip per proof: (left, right) as 128 bytes"""
+def oracle_pairs(circuits, chip=S.OracleEccChip):
+    """verify_single_proof_in_chip per proof: (left, right) as 128 bytes; chip: the MockEccChip restatement to run it over"""
     out = []
     for c in circuits:
         for i, (inst, data) in enumerate(c.proofs):
-            pchip, ctx = S.OracleEccChip(), S.OracleCtx()
+            pchip, ctx = chip(), S.OracleCtx()
             _plain, commitments = V.assign_instance_commitment(pchip, ctx, inst, c.cs, c.g_lagrange)
             t = V.P.PoseidonTranscriptRead(data)
             proof, _adv, _vp = V.verify_single_proof_no_eval(t, pchip, ctx, commitments, c.cs, "%s_p%d" % (c.name, i))

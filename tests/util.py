@@ -1,5 +1,6 @@
 """Shared helpers for the tests (checker side: uses the oracle)."""
 from oracle import bn254 as O, cref
+from oracle import schema as S
 
 G_BYTES = O.aff_to_bytes(O.G1)
 
@@ -46,3 +47,14 @@ def msm_want(gs, ss):
     """canonical affine bytes of sum_i s_i * (g_i * G) = ((sum_i g_i s_i) mod r) * G: Python integers and one scalar
     multiplication by the oracle"""
     return O.aff_to_bytes(O.scalar_mul(sum(g * s for g, s in zip(gs, ss)) % O.R, O.G1))
+
+
+class CEccChip(S.OracleEccChip):
+    """MockEccChip with multi_exp = oracle_multi_exp_naive (the reference's loop, mock/arith/ecc.rs:106-129, in C)"""
+
+    def multi_exp(self, ctx, points, scalars):
+        ctx.point_list = [O.debug_fmt(p) for p in points]
+        n = len(points)
+        out = cref.multi_exp_naive(b"".join(O.aff_to_bytes(p) for p in points),
+                                   b"".join(O.fe_to_bytes(s) for s in scalars), n)
+        return O.aff_from_bytes(out)
