@@ -27,6 +27,7 @@ FR_PROD_MAX_COLUMNS = 16
 FR_SORT_TILE = 11    # log2 of the keys per workgroup of the lookup permutation by default (csrc/lookup_kernels.hpp)
 FR_SORT_TILE_MIN = 4
 FR_COMPRESS_MAX_COLUMNS = 1 << 16   # most columns of one fr_columns_compress (the library's limit: csrc/lookup.inc)
+PERM_MAX_COLUMNS = 4096   # H2AGG_PERM_MAX_COLUMNS: most columns of one permutation (csrc/keygen_kernels.hpp)
 EXPR_MAX_DEPTH = 16  # H2AGG_EXPR_MAX_DEPTH: the operand stack of h2agg_vk_expressions_eval / h2agg_quotient (csrc/quotient_kernels.hpp)
 
 IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
@@ -187,6 +188,9 @@ def load_library():
         "h2agg_vk_expressions_eval_device": (i32, [ctxp, vp, i32, sz, C.c_uint, vp, vp, vp, u8p, u8p, vp]),
         "h2agg_quotient": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
         "h2agg_quotient_device": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
+        "h2agg_permutation_assembly": (i32, [sz, C.c_uint, sz, vp, sz, vp]),
+        "h2agg_permutation_sigmas": (i32, [ctxp, vp, sz, C.c_uint, sz, u8p, vp, vp]),
+        "h2agg_commit_columns": (i32, [ctxp, u64, vp, sz, C.c_uint, vp]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -235,6 +239,47 @@ def g2_scalar_mul(g2_aff: bytes, s: bytes) -> bytes:
     out = C.create_string_buffer(128)
     _check_host(load_library().h2agg_g2_scalar_mul(g2_aff, s, out), "g2_scalar_mul")
     return out.raw
+
+
+def _words(data, nwords: int, what: str):
+    """uint32 words for the C side: bytes / bytearray (little-endian words), an array('I'), a ctypes array of c_uint32, or
+    a sequence of integers -> a ctypes array of exactly nwords words"""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        _need(data, 4 * nwords, what)
+        return (C.c_uint32 * max(nwords, 1)).from_buffer_copy(bytes(data) if nwords else bytes(4))
+    if isinstance(data, C.Array) and data._type_ is C.c_uint32:
+        if len(data) != nwords:
+            raise ValueError("%s must be exactly %d words (got %d)" % (what, nwords, len(data)))
+        return data
+    if data is None or len(data) != nwords:
+        raise ValueError("%s must be exactly %d words (got %s)" % (what, nwords, "None" if data is None else len(data)))
+    return (C.c_uint32 * max(nwords, 1))(*data)
+
+
+def _perm_shape_ok(m: int, k: int, usable: int) -> bool:
+    """the shapes the library goes on to read buffers for (it refuses the others before it touches one)"""
+    return 0 <= k <= FR_FFT_MAX_K and 1 <= m <= PERM_MAX_COLUMNS and 0 <= usable <= (1 << k)
+
+
+def permutation_assembly(m: int, k: int, usable: int, copies) -> bytes:
+    """h2agg_permutation_assembly: host arithmetic, no context.  copies: quadruples (left column, left row, right column,
+    right row), as a sequence of 4-tuples or flat words (bytes, array('I'), ctypes).  -> the mapping halo2's Assembly holds
+    after copy() on them in order: 2 * m * 2^k little-endian uint32 words, cell (j, i) at pair j * 2^k + i."""
+    flat = isinstance(copies, (bytes, bytearray, memoryview, C.Array))
+    if not flat:
+        copies = list(copies or ())
+        if copies and hasattr(copies[0], "__len__"):
+            if any(len(q) != 4 for q in copies):
+                raise ValueError("a copy is (left column, left row, right column, right row)")
+            copies = [int(x) for q in copies for x in q]
+    per_copy = 16 if isinstance(copies, (bytes, bytearray, memoryview)) else 4
+    if len(copies) % per_copy:
+        raise ValueError("copies must be whole quadruples of uint32 words")
+    nwords = len(copies) // per_copy * 4
+    arr = _words(copies, nwords, "copies")
+    out = (C.c_uint32 * (2 * m << k))() if _perm_shape_ok(m, k, usable) else (C.c_uint32 * 1)()
+    _check_host(load_library().h2agg_permutation_assembly(m, k, usable, arr, nwords // 4, out), "permutation_assembly")
+    return bytes(out)
 
 
 def g2_batch_compress(aff: bytes) -> bytes:
@@ -785,6 +830,28 @@ class H2Agg:
         self._check(self._lib.h2agg_quotient_device(self._ctx, vk._vk, d_advice_ptr, d_fixed_ptr, d_instance_ptr, d_sigma_ptr,
                                                     d_perm_z_ptr, d_lookup_z_ptr, d_lookup_ap_ptr, d_lookup_sp_ptr, challenges,
                                                     theta, beta, gamma, y, delta, d_h_ptr))
+
+    # ------------------------------------------------------------------ keys
+    def permutation_sigmas(self, mapping, m: int, k: int, usable: int, delta: bytes, lagrange: bool = True, coeff: bool = True):
+        """h2agg_permutation_sigmas: the mapping of a permutation over m columns of 2^k rows (2 * m * 2^k words: bytes,
+        array('I') or a ctypes array, as permutation_assembly returns it) -> (lagrange, coeff): the sigma columns as slabs
+        [m][2^k] in Lagrange and in coefficient form.  lagrange=False / coeff=False leaves that output out (None)."""
+        _need(delta, 32, "delta")
+        ok = _perm_shape_ok(m, k, usable)
+        words = _words(mapping, 2 * m << k, "mapping") if ok else (C.c_uint32 * 1)()
+        size = (32 * m << k) if ok else 1
+        lag = C.create_string_buffer(size) if lagrange else None
+        co = C.create_string_buffer(size) if coeff else None
+        self._check(self._lib.h2agg_permutation_sigmas(self._ctx, words, m, k, usable, delta, lag, co))
+        return (None if lag is None else lag.raw[:size], None if co is None else co.raw[:size])
+
+    def commit_columns(self, handle: int, columns, k: int) -> List[bytes]:
+        """h2agg_commit_columns: a slab [m][2^k] of canonical scalars -> the m commitments sum_i columns[j][i] * table[i] as
+        64-byte canonical affine points (the identity: 64 zero bytes), through one staging and the batched MSM"""
+        m = self._slab(columns, k) if 0 <= k <= FR_FFT_MAX_K else 1
+        out = C.create_string_buffer(max(64 * m, 1))
+        self._check(self._lib.h2agg_commit_columns(self._ctx, handle, self._hostptr(columns), m, k, out))
+        return [out.raw[64 * j:64 * j + 64] for j in range(m)]
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

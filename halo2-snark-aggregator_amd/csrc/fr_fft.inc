@@ -6,14 +6,15 @@
 
 namespace {
 
-// d_out[i] = (base^i in the device's Montgomery form), i < n <= 2^12; queued on the context's stream, constants by value
-void fr_powers_launch(h2agg_ctx* c, ph::HFr base, uint32_t n, uint8_t* d_out) {
+// d_out[i] = (base^i in the device's Montgomery form), i < n <= 2^12; queued on the context's stream, constants by value.
+// plain: base^i as a canonical integer instead (k_fr_powers' A = 1: csrc/keygen_kernels.hpp multiplies by such a table).
+void fr_powers_launch(h2agg_ctx* c, ph::HFr base, uint32_t n, uint8_t* d_out, bool plain = false) {
     FrPowersArgs args;
     for (int j = 0; j < FRW_TABLE; ++j) {
         hfr_words(base, args.pw[j]);
         base = ph::mul(base, base);
     }
-    hfr_words(fr_radix(), args.a);
+    hfr_words(plain ? ph::one() : fr_radix(), args.a);
     const uint32_t threads = (n + FRP_CHUNK - 1) / FRP_CHUNK;
     hipLaunchKernelGGL(k_fr_powers, dim3((threads + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, args, n, d_out);
 }

@@ -37,6 +37,7 @@
 #include "prod_kernels.hpp"
 #include "lookup_kernels.hpp"
 #include "quotient_kernels.hpp"
+#include "keygen_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -301,6 +302,10 @@ struct h2agg_ctx {
     // quotient polynomial (csrc/quotient.inc): a coset's value slab with the columns behind it and the extended evaluations
     // (qt_layout), the compiled programs and the permutation columns' places, the two-level table of w^i
     DevBuf qt_work, qt_prog, qt_tab;
+    // keygen (csrc/keygen.inc): one bit per cell of a permutation's mapping, the table of delta^c, the Jacobian commitments of a
+    // slab commit
+    DevBuf kg_bitmap, kg_delta, kg_jac;
+    int dbg_commit_chunk = 0;   // debug key commit_chunk: columns per set of MSM launches of h2agg_commit_columns (0 = by the work-memory budget)
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -422,6 +427,8 @@ int flags_to_status(h2agg_ctx* c, uint32_t f, bool earlier) {
     if (f & FLAG_NONCANONICAL) return fail(c, H2AGG_ERR_NONCANONICAL, std::string(pre) + "input integer >= modulus");
     if (f & FLAG_BAD_POINT) return fail(c, H2AGG_ERR_BAD_POINT, std::string(pre) + "invalid point encoding in proof");
     if (f & FLAG_NOT_IN_TABLE) return fail(c, H2AGG_ERR_NOT_IN_TABLE, std::string(pre) + "a lookup input does not occur in the table");
+    if (f & FLAG_BAD_MAPPING)
+        return fail(c, H2AGG_ERR_INVALID, std::string(pre) + "the permutation mapping is not valid (a repeated target, an unusable row that moves, an entry out of range)");
     return H2AGG_OK;
 }
 
@@ -749,7 +756,7 @@ void h2agg_destroy(h2agg_ctx* c) {
                       &c->frfft_tw[0], &c->frfft_tw[1], &c->frfft_shift, &c->frfft_work,
                       &c->poly_work, &c->poly_desc, &c->poly_slab, &c->poly_jac,
                       &c->prod_num, &c->prod_den, &c->prod_lvl, &c->prod_tab, &c->lk_work, &c->lk_desc,
-                      &c->qt_work, &c->qt_prog, &c->qt_tab};
+                      &c->qt_work, &c->qt_prog, &c->qt_tab, &c->kg_bitmap, &c->kg_delta, &c->kg_jac};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     for (auto& kv : c->tables) {
@@ -1767,6 +1774,10 @@ int h2agg_debug_configure(h2agg_ctx* c, const char* key, int value) try {
         if (value != 0 && (value < (int)LK_TILE_LOG_MIN || value > (int)LK_TILE_LOG)) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: fr_sort_tile must be 0 or 4 .. 11");
         c->dbg_fr_sort_tile = value;
     }
+    else if (k == "commit_chunk") {
+        if (value < 0) return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: commit_chunk must be >= 0");
+        c->dbg_commit_chunk = value;
+    }
     else if (k == "lean_full") c->dbg_lean_full = value;     // 1: the bucket accumulation keeps its identity test and endomorphism select whatever the table / plan
     else if (k == "pre_big") c->dbg_pre_big = value;         // 1: h2agg_bases_precompute takes any explicit width (levels through the two-array sort)
     else return fail(c, H2AGG_ERR_INVALID, "h2agg_debug_configure: unknown key " + k);
@@ -2004,3 +2015,4 @@ int h2agg_final_pair_check(h2agg_ctx* c, const uint8_t left_aff[64], const uint8
 #include "prod.inc"
 #include "lookup.inc"
 #include "quotient.inc"
+#include "keygen.inc"

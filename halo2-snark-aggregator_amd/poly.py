@@ -2,7 +2,9 @@
 the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen);
 and the grand products of the permutation and lookup arguments (h2agg_fr_batch_invert, h2agg_permutation_product,
 h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr_columns_compress, h2agg_lookup_permute);
-and the quotient polynomial h(X) from a verifying key (h2agg_vk_expressions_eval, h2agg_quotient).
+and the quotient polynomial h(X) from a verifying key (h2agg_vk_expressions_eval, h2agg_quotient); and the keys those stages
+take: the permutation's mapping, sigma columns and commitments, the fixed columns' (h2agg_permutation_assembly,
+h2agg_permutation_sigmas, h2agg_commit_columns).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -271,5 +273,39 @@ def quotient_pieces(eng, vk, advice, fixed, instance, sigma, perm_z, lookup_z, l
 
 def commit_quotient(eng, g_handle: int, pieces):
     """the commitments of h's pieces against the monomial table (ParamsKZG.g), in order: commit_coeff of each, as 96-byte
-    Jacobian points (the h commitments a proof carries, vanish.rs:18-72)"""
+    Jacobian points (the h commitments a proof carries, vanish.rs:18-72).  (Not the slab call: that one answers canonical
+    affine points, these stay the Jacobian bytes they were.)"""
     return [commit_coeff(eng, g_handle, p) for p in pieces]
+
+
+# ---------------------------------------------------------------------------------------------- keys
+def commit_columns_lagrange(eng, gl_handle: int, cols, k: int):
+    """commit_lagrange of every column of a list in one call (h2agg_commit_columns against ParamsKZG.g_lagrange) -> a list of
+    canonical affine points, 64 bytes each, the identity as 64 zero bytes"""
+    return eng.commit_columns(gl_handle, _columns(cols, k, "evals"), k)
+
+
+def commit_columns_coeff(eng, g_handle: int, cols, k: int):
+    """commit_coeff of every column of a list in one call (h2agg_commit_columns against ParamsKZG.g) -> affine points"""
+    return eng.commit_columns(g_handle, _columns(cols, k, "coeffs"), k)
+
+
+def permutation_mapping(m: int, k: int, usable: int, copies) -> bytes:
+    """permutation::keygen::Assembly: the copy constraints [(left column, left row, right column, right row), ...] over m
+    columns of 2^k rows, in order -> the mapping (h2agg_permutation_assembly), 2 * m * 2^k uint32 words"""
+    from . import permutation_assembly
+    return permutation_assembly(m, k, usable, copies)
+
+
+def permutation_key(eng, gl_handle: int, mapping, m: int, k: int, usable: int, delta: bytes):
+    """the permutation's share of keygen_vk / keygen_pk from its mapping: -> (lagrange, coeff, commitments) — the sigma columns
+    in Lagrange form (what permutation_products takes), in coefficient form (what quotient_pieces takes), m columns each,
+    and their commitments against g_lagrange as affine points (the permutation commitments of a verifying key)"""
+    lag, coeff = eng.permutation_sigmas(mapping, m, k, usable, delta)
+    return _split(lag, k), _split(coeff, k), eng.commit_columns(gl_handle, lag, k)
+
+
+def fixed_key(eng, gl_handle: int, fixed_cols, k: int):
+    """the fixed columns' share of keygen: Lagrange columns -> (coeff, commitments): columns_lagrange_to_coeff of them and
+    their commitments against g_lagrange as affine points (the fixed commitments of a verifying key)"""
+    return columns_lagrange_to_coeff(eng, fixed_cols, k), commit_columns_lagrange(eng, gl_handle, fixed_cols, k)

@@ -802,6 +802,58 @@ int h2agg_quotient_device(h2agg_ctx* ctx, const h2agg_vk* vk, const void* d_advi
                           const void* d_lookup_sp, const uint8_t* challenges, const uint8_t theta[32], const uint8_t beta[32],
                           const uint8_t gamma[32], const uint8_t y[32], const uint8_t delta[32], void* d_h);
 
+/* ---- Keys: sigma columns from copy constraints, and the commitments of a slab of columns ------------------------------------
+ * Stand for: permutation::keygen::Assembly (new, copy, build_vk, build_pk) and the commit_lagrange loops of keygen_vk /
+ * keygen_pk of halo2_proofs — recalled from upstream, not pinned, like the blocks above; what the entry points compute is
+ * this definition.  What a verifier does with the results IS pinned: the sigma commitments are the permutation commitments
+ * of the H2VK blob (h2agg_vk_create), the sigma columns are the `sigmas` of h2agg_permutation_product and the `sigma` of
+ * h2agg_quotient.
+ *
+ * Definitions.  A permutation over m columns of n = 2^k rows is a `mapping`: m * n pairs of uint32_t {column, row}, cell
+ * (j, i) at index j * n + i (2 * m * n words).
+ *   sigma[j][i] = delta^c * w^r  for {c, r} = mapping[j][i], w the 2^k-th root h2agg_fr_fft uses; delta is an argument
+ *   (callers pass Fr::DELTA, as to h2agg_permutation_product: the library holds no literal for it).
+ *   A mapping is valid when every entry has c < m and r < n, the entries are pairwise distinct (a bijection of the cells),
+ *   and every cell with i >= usable maps to itself.
+ *
+ * h2agg_permutation_assembly — host arithmetic, no context (like h2agg_g2_scalar_mul).  copies holds ncopies quadruples
+ *   {left column, left row, right column, right row}; the result is the mapping Assembly holds after copy() on them in order:
+ *   mapping, aux (a cell's cycle representative) and sizes start as the identity, the cell itself and 1.  For a copy whose two
+ *   cells have different representatives the representative of the smaller cycle is merged into the other one (on a tie the
+ *   right cell's): the sizes add, the merged cycle is walked through mapping, rewriting aux, then mapping[left] and
+ *   mapping[right] are swapped.  A copy within one cycle does nothing.  Cost O(m n + the sum of the merged sizes); work memory
+ *   24 bytes per cell.  The result is a valid mapping whose cycles are the classes of the copies' equivalence relation.
+ *   Refusals, H2AGG_ERR_INVALID with `mapping` untouched: k > 24, m == 0 or m > H2AGG_PERM_MAX_COLUMNS, usable > n, a null
+ *   mapping, null copies with ncopies != 0, a column >= m, a row >= usable (keygen's assembly refuses unusable rows).
+ *
+ * h2agg_permutation_sigmas — host buffers, synchronous.  Writes the slab [m][n] of canonical 32-byte elements in Lagrange
+ *   form to sigma_lagrange and the same columns in coefficient form (h2agg_fr_fft_batch's inverse transform, with its 1/n) to
+ *   sigma_coeff.  Either output may be NULL, not both.  The mapping is checked: its range on the host in front of the copy,
+ *   bijectivity (one bit per cell) and the identity rule on the device.
+ *   Refusals: the limits above, a null mapping or delta, both outputs NULL, an invalid mapping: H2AGG_ERR_INVALID; delta >= r:
+ *   H2AGG_ERR_NONCANONICAL.  On a refusal nothing is written to the outputs and the context stays usable.  Out of memory:
+ *   H2AGG_ERR_NOMEM.  Work memory, kept in the context: the mapping, one or two slabs, m n / 8 bytes of bitmap.  With the
+ *   debug key "phases" h2agg_last_phases gives " stage=ms sigma=ms inverse=ms copy=ms" (empty after a call the host refused,
+ *   without copy= after one the device refused).
+ *
+ * h2agg_commit_columns — host buffers, synchronous.  columns is a slab [m][n] of canonical scalars; out_aff[64 j ..] =
+ *   sum_i columns[j][i] * table[i] as a canonical affine point, the identity as 64 zero bytes (as in h2agg_kzg_multiopen).
+ *   Against g_lagrange of h2agg_params_setup this is commit_lagrange of every column, against g it commits coefficient columns.
+ *   The slab is staged once; the MSMs run through h2agg_g1_msm_device_batch_async in chunks of B columns per call, B =
+ *   max(1, 2^22 / n) — the scalars in flight bound the sort's and the buckets' work memory — or the debug key "commit_chunk";
+ *   that path cuts a chunk further by its own limits (its sort's counters and 32-bit offsets; one MSM at a time from 2^20
+ *   points on).  Whatever the chunk, the points are the same bytes.
+ *   Refusals: an unknown handle, a table shorter than n, m == 0, k > 24, a null buffer: H2AGG_ERR_INVALID.  A scalar >= r:
+ *   H2AGG_ERR_NONCANONICAL through the context's device status, as h2agg_g1_msm_preloaded reports it; out_aff is then
+ *   unspecified.  Out of memory: H2AGG_ERR_NOMEM.  The context stays usable after each.
+ *
+ * These entry points have no device-memory twins yet; the functions behind them take device pointers. */
+#define H2AGG_PERM_MAX_COLUMNS 4096
+int h2agg_permutation_assembly(size_t m, unsigned k, size_t usable, const uint32_t* copies, size_t ncopies, uint32_t* mapping);
+int h2agg_permutation_sigmas(h2agg_ctx* ctx, const uint32_t* mapping, size_t m, unsigned k, size_t usable, const uint8_t delta[32],
+                             uint8_t* sigma_lagrange, uint8_t* sigma_coeff);
+int h2agg_commit_columns(h2agg_ctx* ctx, uint64_t bases_handle, const uint8_t* columns, size_t m, unsigned k, uint8_t* out_aff);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
@@ -863,7 +915,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         (default 1; 0: the three latency measures of round 6 off, for an A/B)
  *       "phases" 0|1      keep every aggregation call's wall-clock split, and every h2agg_kzg_multiopen* call's split by events
  *                         (combine / divide / commit) and every h2agg_quotient* call's (forward / gates / permutation / lookups /
- *                         inverse; the queued form then waits for its own events), for h2agg_last_phases
+ *                         inverse; the queued form then waits for its own events) and every h2agg_permutation_sigmas call's
+ *                         (stage / sigma / inverse / copy), for h2agg_last_phases
  *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
  *                         1024 elements then run the multi-pass paths
  *       "fr_fft_batch_chunk" B  a batched transform (h2agg_fr_fft_batch, the transforms inside h2agg_quotient) runs in chunks of
@@ -877,6 +930,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         below 11 the step of its row scans, the threads that take keys in its byte histogram (both 2^(t-2))
  *                         and that histogram's grid (2 workgroups) shrink with the tile: at t = 4 inputs of 65 to 1024 rows
  *                         then run every multi-tile path, the step loops of both scans and the histogram's stride loop included
+ *       "commit_chunk" B  h2agg_commit_columns hands its columns to the batched MSM B at a time (0 = the default: as many as hold
+ *                         2^22 scalars): a slab of a few short columns then crosses the chunk boundary
  *       "lean_full" 0|1   the bucket accumulation keeps its per-entry identity test and endomorphism select for every table
  *                         and plan (1: A/B and tests of the instantiation for any table)
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)
