@@ -258,13 +258,10 @@ def random_shape(rng, k, degree, n_perm, n_lookups, with_gates, blinding_factors
 
 
 # ---------------------------------------------------------------------------------------------- a satisfied circuit
-def satisfied_circuit(rng, k, degree):
-    """A circuit that holds, with everything a prover hands to the quotient.  Advice a, b, c; fixed q_m, q_a (selectors, 0 on
-    the rows from u up) and t (a table); one instance column.  Gates q_m (a b - c) and q_a (a + b(wX) - c); one lookup
-    (b, 7 b) in (t, 7 t); a permutation over all seven columns — the cycles of equal cells on the usable rows — which is
-    more than chunk_len columns for degree <= 8, so there are at least two sets and the last one is ragged.  Random blinding
-    rows.  Z, a', s' come from tests/grand_product_ref.py and tests/lookup_permute_ref.py.  degree >= 4 (the lookup's
-    identity has degree 4).  -> (cs, lagrange, polys, scalars): columns as rows, the same as coefficient lists, the scalars."""
+def circuit_witness(rng, k, degree):
+    """The challenge-independent part of satisfied_circuit: the shape, the witness a, b, c, the fixed columns, the instance
+    column, and the classes of equal cells of the usable rows (lists of (permutation column, row), in the order the cells
+    are met).  Draws from rng exactly what satisfied_circuit drew in front of its challenges.  -> (cs, lagrange, classes)"""
     assert degree >= 4
     n, bf = 1 << k, 5
     u = n - bf - 1
@@ -289,18 +286,36 @@ def satisfied_circuit(rng, k, degree):
     cs = make_cs(k, degree, 3, 3, 1, advice_queries, fixed_queries, instance_queries, gates, lookups, perm, bf)
     assert cs.num_permutation_sets >= 2 and len(perm) % cs.chunk_len
     lag = {"advice": [a, b, c], "fixed": [q_m, q_a, t], "instance": [inst]}
-    sc = random_scalars(rng)
-    # ---- the permutation: equal cells of the usable rows form one cycle each
+    # ---- the permutation: equal cells of the usable rows form one class each
     columns = [lag[kind][col] for kind, col in perm]
     classes = {}
     for j, colv in enumerate(columns):
         for i in range(u):
             classes.setdefault(colv[i], []).append((j, i))
+    assert any(len(cells) > 1 for cells in classes.values())
+    return cs, lag, list(classes.values())
+
+
+def satisfied_circuit(rng, k, degree):
+    """A circuit that holds, with everything a prover hands to the quotient.  Advice a, b, c; fixed q_m, q_a (selectors, 0 on
+    the rows from u up) and t (a table); one instance column.  Gates q_m (a b - c) and q_a (a + b(wX) - c); one lookup
+    (b, 7 b) in (t, 7 t); a permutation over all seven columns — the cycles of equal cells on the usable rows — which is
+    more than chunk_len columns for degree <= 8, so there are at least two sets and the last one is ragged.  Random blinding
+    rows.  Z, a', s' come from tests/grand_product_ref.py and tests/lookup_permute_ref.py.  degree >= 4 (the lookup's
+    identity has degree 4).  The witness is circuit_witness's; the challenges are drawn behind it.
+    -> (cs, lagrange, polys, scalars): columns as rows, the same as coefficient lists, the scalars."""
+    cs, lag, classes = circuit_witness(rng, k, degree)
+    n, bf = cs.n, cs.blinding_factors
+    u = n - bf - 1
+    rnd = lambda: rng.randrange(R)
+    perm = cs.permutation_columns
+    sc = random_scalars(rng)
+    # ---- the permutation: every class is one cycle
+    columns = [lag[kind][col] for kind, col in perm]
     to = {}
-    for cells in classes.values():
+    for cells in classes:
         for pos, cell in enumerate(cells):
             to[cell] = cells[(pos + 1) % len(cells)]
-    assert any(len(cells) > 1 for cells in classes.values())
     w = cs.omega
     label = lambda j, i: pow(DELTA, j, R) * pow(w, i, R) % R
     sigmas = [[label(*to[(j, i)]) if i < u else label(j, i) for i in range(n)] for j in range(len(perm))]
