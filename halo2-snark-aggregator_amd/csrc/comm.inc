@@ -137,11 +137,7 @@ int h2agg_comm_init_rank(h2agg_ctx* c, const uint8_t id_bytes[128], int rank, in
     c->comm_rank = rank;
     c->comm_size = nranks;
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // one process driving several GPUs: a context per device plus ncclCommInitAll (SURVEY.md 8(b))
 int h2agg_comm_create(const int* devices, int ndev, h2agg_ctx** ctxs_out) try {
@@ -172,11 +168,7 @@ int h2agg_comm_create(const int* devices, int ndev, h2agg_ctx** ctxs_out) try {
         ctxs_out[i]->comm_size = ndev;
     }
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // why the last context-less comm call (h2agg_comm_unique_id / h2agg_comm_create before any context exists) failed
 const char* h2agg_comm_last_error(void) {
@@ -268,10 +260,6 @@ int h2agg_allgather_add_points(h2agg_ctx** ctxs, int nctx, const uint8_t* partia
     }
     if (rc_all != H2AGG_OK && ctxs[0]->err.empty()) ctxs[0]->err = "a rank reported an error";
     return rc_all;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Fourier transform over Fr, host side (included into h2agg.hip: shares the context internals; kernels and the pass plan in
-// fr_fft_kernels.hpp, field constants, checks and staging in fr_host.inc): h2agg_fr_fft, h2agg_fr_fft_device, h2agg_fr_fft_batch.  They stand for
+// fr_fft_kernels.hpp, field constants and checks in fr_host.inc, staging in host.inc): h2agg_fr_fft, h2agg_fr_fft_device, h2agg_fr_fft_batch.  They stand for
 // halo2_proofs' best_fft and EvaluationDomain::{lagrange_to_coeff, coeff_to_lagrange, coeff_to_extended, extended_to_coeff} —
 // an unvendored git dependency of the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition
 // in include/h2agg.h.
@@ -34,7 +34,7 @@ void fr_table_launch(h2agg_ctx* c, const ph::HFr& base, unsigned bits, uint8_t* 
 int fr_fft_ensure_twiddles(h2agg_ctx* c, unsigned k, int inv) {
     if (c->frfft_tw_k[inv] >= (int)k) return H2AGG_OK;
     c->frfft_tw_k[inv] = -1;
-    TRY(fr_ensure(c, c->frfft_tw[inv], fr_table_bytes(k)));   // (a replaced buffer: ensure() drains the device first)
+    TRY(ensure(c, c->frfft_tw[inv], fr_table_bytes(k)));   // (a replaced buffer: ensure() drains the device first)
     const ph::HFr w = fft_omega(k);
     fr_table_launch(c, inv ? ph::inv(w) : w, k, (uint8_t*)c->frfft_tw[inv].p);
     c->frfft_tw_k[inv] = (int)k;
@@ -70,10 +70,10 @@ int fr_fft_queue_batch(h2agg_ctx* c, const FrFftSeg* segs, size_t nseg, size_t m
         for (size_t g = 0; g < nseg; ++g) cols += segs[g].cols;
         if (nseg > (size_t)FR_FFT_SEGS || cols != m) return fail(c, H2AGG_ERR_INVALID, "fr_fft: the source slabs do not make up the batch");
     }
-    if (P > 1) TRY(fr_ensure(c, c->frfft_work, fr_fft_batch_work_bytes(m, k)));
+    if (P > 1) TRY(ensure(c, c->frfft_work, fr_fft_batch_work_bytes(m, k)));
     if (k) TRY(fr_fft_ensure_twiddles(c, k, inv));
     if (shift) {
-        TRY(fr_ensure(c, c->frfft_shift, fr_table_bytes(k)));
+        TRY(ensure(c, c->frfft_shift, fr_table_bytes(k)));
         fr_table_launch(c, inv ? ph::inv(*shift) : *shift, k, (uint8_t*)c->frfft_shift.p);
     }
     FrFftPass p = {};
@@ -171,7 +171,7 @@ int h2agg_fr_fft_device(h2agg_ctx* c, const void* d_in, unsigned k, int inverse,
     ph::HFr s;
     TRY(fr_fft_check(c, k, shift, &s));
     return fr_fft_queue(c, (const uint8_t*)d_in, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)d_out);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_fft(h2agg_ctx* c, const uint8_t* in, unsigned k, int inverse, const uint8_t shift[32], uint8_t* out) try {
     TRY(bind(c));
@@ -179,12 +179,12 @@ int h2agg_fr_fft(h2agg_ctx* c, const uint8_t* in, unsigned k, int inverse, const
     ph::HFr s;
     TRY(fr_fft_check(c, k, shift, &s));
     const size_t bytes = (size_t)32 << k;
-    TRY(fr_ensure(c, c->in_a, bytes));
-    TRY(fr_stage_in(c, c->in_a, in, bytes));
+    TRY(ensure(c, c->in_a, bytes));
+    TRY(stage_in(c, c->in_a, in, bytes));
     TRY(clear_flags(c));
     TRY(fr_fft_queue(c, (const uint8_t*)c->in_a.p, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)c->in_a.p));
-    return fr_stage_out(c, out, c->in_a.p, bytes);
-} FR_API_CATCH
+    return stage_out(c, out, c->in_a.p, bytes);
+} API_CATCH
 
 int h2agg_fr_fft_batch(h2agg_ctx* c, const uint8_t* in, size_t m, unsigned k, int inverse, const uint8_t shift[32],
                        uint8_t* out) try {
@@ -195,12 +195,12 @@ int h2agg_fr_fft_batch(h2agg_ctx* c, const uint8_t* in, size_t m, unsigned k, in
     TRY(fr_fft_check(c, k, shift, &s));
     if (m > (SIZE_MAX >> 1) / ((size_t)32 << k)) return fail(c, H2AGG_ERR_NOMEM, "fr_fft_batch: the slab does not fit the address space");
     const size_t bytes = m * ((size_t)32 << k);
-    TRY(fr_ensure(c, c->in_a, bytes));
-    TRY(fr_stage_in(c, c->in_a, in, bytes));
+    TRY(ensure(c, c->in_a, bytes));
+    TRY(stage_in(c, c->in_a, in, bytes));
     TRY(clear_flags(c));
     const FrFftSeg seg = {(const uint8_t*)c->in_a.p, m};
     TRY(fr_fft_queue_batch(c, &seg, 1, m, k, inverse ? 1 : 0, shift ? &s : nullptr, (uint8_t*)c->in_a.p));
-    return fr_stage_out(c, out, c->in_a.p, bytes);
-} FR_API_CATCH
+    return stage_out(c, out, c->in_a.p, bytes);
+} API_CATCH
 
 }  // extern "C"

@@ -1,7 +1,7 @@
-// The host layer shared by the Fr prover entry points (included into h2agg.hip ahead of params.inc, fr_fft.inc, poly_open.inc
-// and prod.inc: shares the context internals): field constants, the checks every entry point repeats, the growing-buffer
-// rule, the level plan of the chunked sweeps (geometry: fr_chunk.hpp), the staging of a host twin, and the catch blocks
-// behind every extern "C" function.  A new family of entry points starts from here.
+// What the Fr prover entry points share on top of host.inc (included into h2agg.hip ahead of params.inc, fr_fft.inc,
+// poly_open.inc and prod.inc: shares the context internals): field constants, the checks every entry point repeats and the
+// level plan of the chunked sweeps (geometry: fr_chunk.hpp).  The growing-buffer rule, the staging of a host twin and the
+// catch blocks behind every extern "C" function are host.inc's.
 
 namespace {
 
@@ -42,14 +42,6 @@ int fr_check_k(h2agg_ctx* c, unsigned k) {
     return H2AGG_OK;
 }
 
-// ensure(); a failed allocation also leaves HIP's last-error slot set, which the hipGetLastError() behind the next launches
-// would report as that call's failure: taken out here, so that the context stays usable after H2AGG_ERR_NOMEM
-int fr_ensure(h2agg_ctx* c, DevBuf& b, size_t bytes) {
-    const int rc = ensure(c, b, bytes);
-    if (rc == H2AGG_ERR_NOMEM) (void)hipGetLastError();
-    return rc;
-}
-
 // the levels of one chunked sweep: cnt[0] = n0 elements per query, cnt[l + 1] = ceil(cnt[l] / 2^t), down to 1.  Level l >= 1 is
 // [query][cnt[l]] elements at off[l] of the family's level buffer; total: the elements of all levels, over the nq queries.
 // t comes from the caller's debug key (fr_poly_chunk, fr_scan_chunk) or is FR_CHUNK_LOG.
@@ -76,22 +68,4 @@ FrLevelPlan fr_level_plan(unsigned t, size_t n0, size_t nq) {
     return p;
 }
 
-// A host twin of a _device entry point: fr_ensure its staging buffers, fr_stage_in the arguments, clear_flags, queue what the
-// _device call queues, fr_stage_out.
-//   in: `bytes` of `src` to offset `at` of `b`
-int fr_stage_in(h2agg_ctx* c, DevBuf& b, const uint8_t* src, size_t bytes, size_t at = 0) {
-    if (bytes) HIP_TRY(c, hipMemcpyAsync((uint8_t*)b.p + at, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return H2AGG_OK;
-}
-//   out, the tail of the call: `bytes` at d_src back to the host, then finish() synchronises and reports the flags
-int fr_stage_out(h2agg_ctx* c, uint8_t* dst, const void* d_src, size_t bytes) {
-    HIP_TRY(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
-    return finish(c);
-}
-
 }  // namespace
-
-// behind the body of every extern "C" function of the three families: `int h2agg_...(...) try { ... } FR_API_CATCH`
-#define FR_API_CATCH                                                                                   \
-    catch (const std::bad_alloc&) { return H2AGG_ERR_NOMEM; /* no C++ exception crosses the C ABI */ } \
-    catch (...) { return H2AGG_ERR_INVALID; }

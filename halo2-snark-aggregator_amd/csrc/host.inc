@@ -1,0 +1,91 @@
+// The host layer every C-ABI entry point stands on (included into h2agg.hip ahead of msm_run.inc and of every family: shares the
+// context internals): the growing-buffer rule, the launch grid of the element-wise kernels, the binding of a call to its
+// context, the look-up of a base table, the staging of a host twin, and the catch blocks behind every extern "C" function.
+// A new family of entry points starts from here (the Fr families: from fr_host.inc on top of it).
+
+namespace {
+
+int flush_deferred_tail(h2agg_ctx* c, bool behind_sort);   // csrc/msm_run.inc
+int join_tails(h2agg_ctx* c);                               // csrc/msm_run.inc
+
+// A failed allocation also leaves HIP's last-error slot set, which the hipGetLastError() behind the next launches would report
+// as that call's failure: taken out there, so that the context stays usable after H2AGG_ERR_NOMEM.
+int ensure(h2agg_ctx* c, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return H2AGG_OK;
+    if (b.p) {
+        // a grow-only buffer is replaced: nothing queued on ANY stream of the device may still refer to the old one
+        // (nor anything not yet queued: a deferred tail goes out first)
+        TRY(flush_deferred_tail(c, false));
+        HIP_TRY(c, hipDeviceSynchronize());
+        HIP_TRY(c, hipFree(b.p));
+    }
+    b.p = nullptr;
+    b.cap = 0;
+    size_t want = bytes + bytes / 8 + 256;
+    hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, H2AGG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    b.cap = want;
+    return H2AGG_OK;
+}
+
+int grid_for(const h2agg_ctx* c, size_t n) {
+    size_t blocks = (n + BLOCK - 1) / BLOCK;
+    size_t cap = (size_t)c->cu_count * 8;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
+}
+
+// Called from each entry point's own body: the return address is the crash breadcrumb of the call.
+int bind(h2agg_ctx* c) {
+    crumb((uintptr_t)__builtin_return_address(0), 0);
+    if (!c) return H2AGG_ERR_INVALID;
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return fail(c, H2AGG_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    return H2AGG_OK;
+}
+
+int find_table(h2agg_ctx* c, uint64_t handle, Table** out) {
+    auto it = c->tables.find(handle);
+    if (it == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown base-table handle");
+    *out = &it->second;
+    return H2AGG_OK;
+}
+
+// A host twin of a _device entry point: ensure its staging buffers, stage_in the arguments, clear_flags, queue what the
+// _device call queues, stage_out.
+//   in: `bytes` of `src` to offset `at` of `b`
+int stage_in(h2agg_ctx* c, DevBuf& b, const uint8_t* src, size_t bytes, size_t at = 0) {
+    if (bytes) HIP_TRY(c, hipMemcpyAsync((uint8_t*)b.p + at, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return H2AGG_OK;
+}
+//   out, the tail of the call: `bytes` at d_src back to the host, then finish() synchronises and reports the flags
+int stage_out(h2agg_ctx* c, uint8_t* dst, const void* d_src, size_t bytes) {
+    HIP_TRY(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+    return finish(c);
+}
+
+int set_identity_jac(uint8_t out[96]) {
+    memset(out, 0, 96);
+    out[32] = 1;
+    return 0;
+}
+
+// the tail of a call whose result is one Jacobian point at d_res_jac
+int fetch_result_jac(h2agg_ctx* c, uint8_t out[96]) {
+    TRY(join_tails(c));
+    HIP_TRY(c, hipMemcpyAsync(c->h_pinned, c->d_res_jac, 96, hipMemcpyDeviceToHost, c->stream));
+    TRY(finish(c));
+    memcpy(out, c->h_pinned, 96);
+    return H2AGG_OK;
+}
+
+}  // namespace
+
+// behind the body of every extern "C" function: `int h2agg_...(...) try { ... } API_CATCH`
+#define API_CATCH                                                                                      \
+    catch (const std::bad_alloc&) { return H2AGG_ERR_NOMEM; /* no C++ exception crosses the C ABI */ } \
+    catch (...) { return H2AGG_ERR_INVALID; }

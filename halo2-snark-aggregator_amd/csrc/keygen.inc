@@ -1,5 +1,5 @@
 // The permutation half of keygen and the slab commit, host side (included into h2agg.hip behind quotient.inc: shares the
-// context internals; the kernel and its bounds in keygen_kernels.hpp, checks and staging in fr_host.inc, transforms and power
+// context internals; the kernel and its bounds in keygen_kernels.hpp, checks in fr_host.inc, staging in host.inc, transforms and power
 // tables in fr_fft.inc): h2agg_permutation_assembly, h2agg_permutation_sigmas, h2agg_commit_columns.  They stand for
 // halo2_proofs' permutation::keygen::Assembly (copy, build_vk, build_pk) and the commit_lagrange loop of keygen_vk — an
 // unvendored git dependency of the reference, recalled from upstream (DESIGN.md section 2 and 5.15); the yardstick is the
@@ -60,8 +60,8 @@ struct KgPhases {
 int perm_sigma_queue(h2agg_ctx* c, const void* d_mapping, size_t m, unsigned k, size_t usable, const ph::HFr& delta, uint8_t* d_out) {
     const size_t cells = m << k;
     const size_t bitmap_bytes = 4 * ((cells + 31) / 32);
-    TRY(fr_ensure(c, c->kg_bitmap, bitmap_bytes));
-    TRY(fr_ensure(c, c->kg_delta, 32 * m));
+    TRY(ensure(c, c->kg_bitmap, bitmap_bytes));
+    TRY(ensure(c, c->kg_delta, 32 * m));
     if (k) TRY(fr_fft_ensure_twiddles(c, k, 0));
     HIP_TRY(c, hipMemsetAsync(c->kg_bitmap.p, 0, bitmap_bytes, c->stream));
     fr_powers_launch(c, delta, (uint32_t)m, (uint8_t*)c->kg_delta.p, true);   // plain integers: see k_perm_sigma
@@ -120,7 +120,7 @@ int h2agg_permutation_assembly(size_t m, unsigned k, size_t usable, const uint32
         mapping[2 * x + 1] = (uint32_t)(next[x] & (n - 1));
     }
     return H2AGG_OK;
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_permutation_sigmas(h2agg_ctx* c, const uint32_t* mapping, size_t m, unsigned k, size_t usable, const uint8_t delta[32],
                              uint8_t* sigma_lagrange, uint8_t* sigma_coeff) try {
@@ -137,14 +137,14 @@ int h2agg_permutation_sigmas(h2agg_ctx* c, const uint32_t* mapping, size_t m, un
         if (mapping[2 * x] >= m || mapping[2 * x + 1] >= n)
             return fail(c, H2AGG_ERR_INVALID, "permutation_sigmas: a mapping entry is outside the m x 2^k cells");
     const bool both = sigma_lagrange && sigma_coeff;
-    TRY(fr_ensure(c, c->in_a, 8 * cells));
-    TRY(fr_ensure(c, c->out, slab));
-    if (both) TRY(fr_ensure(c, c->in_b, slab));
+    TRY(ensure(c, c->in_a, 8 * cells));
+    TRY(ensure(c, c->out, slab));
+    if (both) TRY(ensure(c, c->in_b, slab));
     uint8_t* d_lag = (uint8_t*)c->out.p;
     uint8_t* d_coeff = both ? (uint8_t*)c->in_b.p : d_lag;   // only the coefficients are wanted: the transform runs in place
     KgPhases phases(c->dbg_phases != 0);
     phases.mark(c);
-    TRY(fr_stage_in(c, c->in_a, (const uint8_t*)mapping, 8 * cells));
+    TRY(stage_in(c, c->in_a, (const uint8_t*)mapping, 8 * cells));
     TRY(clear_flags(c));
     phases.mark(c);
     TRY(perm_sigma_queue(c, c->in_a.p, m, k, usable, d, d_lag));
@@ -166,7 +166,7 @@ int h2agg_permutation_sigmas(h2agg_ctx* c, const uint32_t* mapping, size_t m, un
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->dbg_phases) phases.report(&c->last_phases);
     return H2AGG_OK;
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_commit_columns(h2agg_ctx* c, uint64_t bases_handle, const uint8_t* columns, size_t m, unsigned k, uint8_t* out_aff) try {
     TRY(bind(c));
@@ -174,15 +174,13 @@ int h2agg_commit_columns(h2agg_ctx* c, uint64_t bases_handle, const uint8_t* col
     if (m == 0) return fail(c, H2AGG_ERR_INVALID, "commit_columns: m == 0");
     TRY(fr_check_k(c, k));
     const size_t n = (size_t)1 << k;
-    {
-        auto it = c->tables.find(bases_handle);
-        if (it == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown base-table handle");
-        if (n > it->second.n) return fail(c, H2AGG_ERR_INVALID, "commit_columns: the table is shorter than 2^k");
-    }
+    Table* bases = nullptr;
+    TRY(find_table(c, bases_handle, &bases));
+    if (n > bases->n) return fail(c, H2AGG_ERR_INVALID, "commit_columns: the table is shorter than 2^k");
     if (m > (SIZE_MAX >> 1) / (32 * n)) return fail(c, H2AGG_ERR_NOMEM, "commit_columns: the slab does not fit the address space");
-    TRY(fr_ensure(c, c->in_b, 32 * n * m));
-    TRY(fr_ensure(c, c->kg_jac, 96 * m));
-    TRY(fr_stage_in(c, c->in_b, columns, 32 * n * m));   // one staging of the slab
+    TRY(ensure(c, c->in_b, 32 * n * m));
+    TRY(ensure(c, c->kg_jac, 96 * m));
+    TRY(stage_in(c, c->in_b, columns, 32 * n * m));   // one staging of the slab
     TRY(clear_flags(c));
     // B columns per set of MSM launches: as many as hold 2^KG_COMMIT_WORK_LOG scalars (the sort's and the buckets' work memory
     // grows with the scalars in flight), at least one, or the debug key commit_chunk; the batched MSM cuts further by its own limits
@@ -192,6 +190,6 @@ int h2agg_commit_columns(h2agg_ctx* c, uint64_t bases_handle, const uint8_t* col
         TRY(h2agg_g1_msm_device_batch_async(c, bases_handle, (const uint8_t*)c->in_b.p + 32 * n * q, n, std::min(B, m - q),
                                             (uint8_t*)c->kg_jac.p + 96 * q));
     return h2agg_g1_batch_to_affine_device(c, (const uint8_t*)c->kg_jac.p, m, out_aff);   // joins, synchronises, reports the flags
-} FR_API_CATCH
+} API_CATCH
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // The lookup argument in front of its grand product, host side (included into h2agg.hip behind prod.inc: shares the context
-// internals; kernels, sort plan and bounds in lookup_kernels.hpp, checks and staging in fr_host.inc):
+// internals; kernels, sort plan and bounds in lookup_kernels.hpp, checks in fr_host.inc, staging in host.inc):
 // h2agg_lookup_permute[_device], h2agg_fr_columns_compress[_device].  They stand for halo2_proofs'
 // lookup::prover::permute_expression_pair and the theta-fold of commit_permuted — an unvendored git dependency of the
 // reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.  Which pair a
@@ -106,7 +106,7 @@ void lk_prefix_queue(h2agg_ctx* c, const uint32_t* src, uint32_t* sums, uint32_t
 int lk_permute_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, size_t u, uint8_t* d_ap, uint8_t* d_sp) {
     const LkGeom g = lk_geom(c);
     const LkLayout l = lk_layout(u, g.t);
-    TRY(fr_ensure(c, c->lk_work, l.total));
+    TRY(ensure(c, c->lk_work, l.total));
     uint8_t* w = (uint8_t*)c->lk_work.p;
     TRY(lk_sort_queue(c, d_a, l, 0, u, g));
     TRY(lk_sort_queue(c, d_s, l, 1, u, g));
@@ -155,7 +155,7 @@ int lk_compress_check(h2agg_ctx* c, size_t m, unsigned k, const uint8_t* theta, 
 // out[i] = sum_j theta^(m - 1 - j) cols[j][i]: k_fr_poly_lincomb over one group, the descriptor written on the stream
 int lk_compress_queue(h2agg_ctx* c, const uint8_t* d_cols, size_t m, unsigned k, const ph::HFr& theta, uint8_t* d_out) {
     const size_t n = (size_t)1 << k;
-    TRY(fr_ensure(c, c->lk_desc, 4 * (m + 2)));
+    TRY(ensure(c, c->lk_desc, 4 * (m + 2)));
     uint32_t* desc = (uint32_t*)c->lk_desc.p;
     hipLaunchKernelGGL(k_lk_compress_desc, dim3((unsigned)((m + 2 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, desc, (uint32_t)m);
     FrLincombArgs la;
@@ -185,7 +185,7 @@ int h2agg_lookup_permute_device(h2agg_ctx* c, const void* d_a, const void* d_s, 
         lk_overlap(d_ap, d_sp, bytes))
         return fail(c, H2AGG_ERR_INVALID, "ap / sp must not overlap a, s or each other");
     return lk_permute_queue(c, (const uint8_t*)d_a, (const uint8_t*)d_s, u, (uint8_t*)d_ap, (uint8_t*)d_sp);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_lookup_permute(h2agg_ctx* c, const uint8_t* a, const uint8_t* s, unsigned k, size_t u, uint8_t* ap, uint8_t* sp) try {
     TRY(bind(c));
@@ -193,17 +193,17 @@ int h2agg_lookup_permute(h2agg_ctx* c, const uint8_t* a, const uint8_t* s, unsig
     if (!a || !s || !ap || !sp) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     if (u == 0) return H2AGG_OK;
     const size_t bytes = 32 * u;
-    TRY(fr_ensure(c, c->in_a, 2 * bytes));
-    TRY(fr_ensure(c, c->out, 2 * bytes));
-    TRY(fr_stage_in(c, c->in_a, a, bytes));
-    TRY(fr_stage_in(c, c->in_a, s, bytes, bytes));
+    TRY(ensure(c, c->in_a, 2 * bytes));
+    TRY(ensure(c, c->out, 2 * bytes));
+    TRY(stage_in(c, c->in_a, a, bytes));
+    TRY(stage_in(c, c->in_a, s, bytes, bytes));
     TRY(clear_flags(c));
     const uint8_t* d_in = (const uint8_t*)c->in_a.p;
     uint8_t* d_out = (uint8_t*)c->out.p;
     TRY(lk_permute_queue(c, d_in, d_in + bytes, u, d_out, d_out + bytes));
     HIP_TRY(c, hipMemcpyAsync(ap, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    return fr_stage_out(c, sp, d_out + bytes, bytes);
-} FR_API_CATCH
+    return stage_out(c, sp, d_out + bytes, bytes);
+} API_CATCH
 
 int h2agg_fr_columns_compress_device(h2agg_ctx* c, const void* d_cols, size_t m, unsigned k, const uint8_t theta[32], void* d_out) try {
     TRY(bind(c));
@@ -211,7 +211,7 @@ int h2agg_fr_columns_compress_device(h2agg_ctx* c, const void* d_cols, size_t m,
     TRY(lk_compress_check(c, m, k, theta, &tf));
     if (!d_cols || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return lk_compress_queue(c, (const uint8_t*)d_cols, m, k, tf, (uint8_t*)d_out);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_columns_compress(h2agg_ctx* c, const uint8_t* cols, size_t m, unsigned k, const uint8_t theta[32], uint8_t* out) try {
     TRY(bind(c));
@@ -219,12 +219,12 @@ int h2agg_fr_columns_compress(h2agg_ctx* c, const uint8_t* cols, size_t m, unsig
     TRY(lk_compress_check(c, m, k, theta, &tf));
     if (!cols || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     const size_t col = (size_t)32 << k;
-    TRY(fr_ensure(c, c->in_a, m * col));
-    TRY(fr_ensure(c, c->out, col));
-    TRY(fr_stage_in(c, c->in_a, cols, m * col));
+    TRY(ensure(c, c->in_a, m * col));
+    TRY(ensure(c, c->out, col));
+    TRY(stage_in(c, c->in_a, cols, m * col));
     TRY(clear_flags(c));
     TRY(lk_compress_queue(c, (const uint8_t*)c->in_a.p, m, k, tf, (uint8_t*)c->out.p));
-    return fr_stage_out(c, out, c->out.p, col);
-} FR_API_CATCH
+    return stage_out(c, out, c->out.p, col);
+} API_CATCH
 
 }  // extern "C"

@@ -145,14 +145,14 @@ int h2agg_bases_fft(h2agg_ctx* c, uint64_t in_handle, unsigned k, int inverse, u
     TRY(bind(c));
     if (!out_handle) return fail(c, H2AGG_ERR_INVALID, "null handle pointer");
     if (k > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "k must be <= 24");
-    auto it = c->tables.find(in_handle);
-    if (it == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown base-table handle");
+    Table* in = nullptr;
+    TRY(find_table(c, in_handle, &in));
     const size_t n = (size_t)1 << k;
-    if (n > it->second.n) return fail(c, H2AGG_ERR_INVALID, "the table has fewer than 2^k points");
+    if (n > in->n) return fail(c, H2AGG_ERR_INVALID, "the table has fewer than 2^k points");
     Table t;
     t.n = n;
     if (hipMalloc((void**)&t.d, 64 * n) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(base table)");
-    const int rc = fft_run(c, it->second.d, k, inverse ? 1 : 0, t.d);
+    const int rc = fft_run(c, in->d, k, inverse ? 1 : 0, t.d);
     if (rc != H2AGG_OK) {
         hipFree(t.d);
         return rc;
@@ -162,11 +162,7 @@ int h2agg_bases_fft(h2agg_ctx* c, uint64_t in_handle, unsigned k, int inverse, u
     c->tables[h] = t;
     *out_handle = h;
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_params_setup(h2agg_ctx* c, unsigned k, const uint8_t s[32], uint64_t* g_handle_out, uint64_t* g_lagrange_handle_out) try {
     TRY(bind(c));
@@ -207,11 +203,7 @@ int h2agg_params_setup(h2agg_ctx* c, unsigned k, const uint8_t s[32], uint64_t* 
         *g_lagrange_handle_out = h;
     }
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // s * Q on the twist: double-and-add over the bits of s through the pairing's projective step functions (line values
 // discarded, as g2_in_subgroup does).  For a point of order r and 2 <= s < r no prefix m of s has m * Q == +-Q at an addition.
@@ -239,11 +231,7 @@ int h2agg_g2_scalar_mul(const uint8_t g2_aff[128], const uint8_t s[32], uint8_t 
     const pairing::G2Affine o = {pairing::f2_mul(acc.x, zi), pairing::f2_mul(acc.y, zi), false};
     pairing::g2_to_bytes(o, out_aff);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_g2_batch_compress(const uint8_t* aff, size_t n, uint8_t* out) try {
     if (n && (!aff || !out)) return H2AGG_ERR_INVALID;
@@ -261,10 +249,6 @@ int h2agg_g2_batch_compress(const uint8_t* aff, size_t n, uint8_t* out) try {
         if (!zero) out[64 * i + 63] |= (uint8_t)((b[64] & 1) << 7);   // parity of y.c0 (`y.to_bytes()[0] & 1`)
     }
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // KZG openings, host side (included into h2agg.hip: shares the context internals; kernels and bounds in poly_kernels.hpp,
-// level plan, checks and staging in fr_host.inc, power tables in fr_fft.inc): h2agg_fr_poly_eval[_device],
+// level plan and checks in fr_host.inc, staging in host.inc, power tables in fr_fft.inc): h2agg_fr_poly_eval[_device],
 // h2agg_fr_poly_divide[_device], h2agg_kzg_multiopen[_device].  They stand for halo2_proofs' eval_polynomial, kate_division and
 // the GWC multiopen prover — an unvendored git dependency of the reference, recalled from upstream (DESIGN.md section 2); the
 // yardstick is the definition in include/h2agg.h.  Which W a verifier accepts is pinned by
@@ -119,12 +119,12 @@ int poly_eval_run(h2agg_ctx* c, const uint8_t* d_polys, unsigned k, const uint32
     const FrLevelPlan plan = poly_plan(c, k, nq);
     std::vector<std::vector<FrPolyPoint>> tab;
     poly_point_tables(named, plan, tab);
-    TRY(fr_ensure(c, c->poly_work, 32 * plan.total));
-    TRY(fr_ensure(c, c->poly_desc, 8 * nq));
+    TRY(ensure(c, c->poly_work, 32 * plan.total));
+    TRY(ensure(c, c->poly_desc, 8 * nq));
     HIP_TRY(c, hipMemcpyAsync(c->poly_desc.p, desc.data(), 8 * nq, hipMemcpyHostToDevice, c->stream));
     poly_eval_queue(c, d_polys, (const uint32_t*)c->poly_desc.p, plan, tab);
     HIP_TRY(c, hipGetLastError());
-    return fr_stage_out(c, out, poly_top(c, plan), 32 * nq);
+    return stage_out(c, out, poly_top(c, plan), 32 * nq);
 }
 
 // up-sweep, down-sweep and the remainder of ONE polynomial; nothing synchronises unless the work buffer has to grow
@@ -132,7 +132,7 @@ int poly_divide_queue_one(h2agg_ctx* c, const uint8_t* d_poly, unsigned k, const
     const FrLevelPlan plan = poly_plan(c, k, 1);
     std::vector<std::vector<FrPolyPoint>> tab;
     poly_point_tables(std::vector<ph::HFr>(1, z), plan, tab);
-    TRY(fr_ensure(c, c->poly_work, 32 * plan.total));
+    TRY(ensure(c, c->poly_work, 32 * plan.total));
     poly_eval_queue(c, d_poly, nullptr, plan, tab);
     poly_divide_queue(c, d_poly, nullptr, plan, tab, d_quot);
     HIP_TRY(c, hipGetLastError());
@@ -210,10 +210,10 @@ int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsig
     const FrLevelPlan plan = poly_plan(c, k, groups);
     std::vector<std::vector<FrPolyPoint>> tab;
     poly_point_tables(gz, plan, tab);
-    TRY(fr_ensure(c, c->poly_work, 32 * plan.total));
-    TRY(fr_ensure(c, c->poly_desc, 4 * lists.size()));
-    TRY(fr_ensure(c, c->poly_slab, 32 * n * groups));
-    TRY(fr_ensure(c, c->poly_jac, 96 * groups));
+    TRY(ensure(c, c->poly_work, 32 * plan.total));
+    TRY(ensure(c, c->poly_desc, 4 * lists.size()));
+    TRY(ensure(c, c->poly_slab, 32 * n * groups));
+    TRY(ensure(c, c->poly_jac, 96 * groups));
     HIP_TRY(c, hipMemcpyAsync(c->poly_desc.p, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, c->stream));
     PolyPhases phases(c->dbg_phases != 0);
     phases.mark(c, 0);
@@ -247,9 +247,9 @@ int multiopen_check(h2agg_ctx* c, uint64_t g_handle, unsigned k, size_t npoly, c
     if (!v || !w_aff || !group_points || !ngroups) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     TRY(poly_check_queries(c, k, npoly, queries, nq, points, npoints, pts));
     TRY(fr_parse(c, v, vf));
-    auto it = c->tables.find(g_handle);
-    if (it == c->tables.end()) return fail(c, H2AGG_ERR_INVALID, "unknown base-table handle");
-    if (it->second.n < ((size_t)1 << k)) return fail(c, H2AGG_ERR_INVALID, "the base table is shorter than 2^k");
+    Table* g = nullptr;
+    TRY(find_table(c, g_handle, &g));
+    if (g->n < ((size_t)1 << k)) return fail(c, H2AGG_ERR_INVALID, "the base table is shorter than 2^k");
     return H2AGG_OK;
 }
 
@@ -265,7 +265,7 @@ int h2agg_fr_poly_eval_device(h2agg_ctx* c, const void* d_polys, size_t npoly, u
     TRY(poly_check_queries(c, k, npoly, queries, nq, points, npoints, &pts));
     TRY(clear_flags(c));
     return poly_eval_run(c, (const uint8_t*)d_polys, k, queries, nq, pts, out);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_poly_eval(h2agg_ctx* c, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries, size_t nq,
                        const uint8_t* points, size_t npoints, uint8_t* out) try {
@@ -274,11 +274,11 @@ int h2agg_fr_poly_eval(h2agg_ctx* c, const uint8_t* polys, size_t npoly, unsigne
     std::vector<ph::HFr> pts;
     TRY(poly_check_queries(c, k, npoly, queries, nq, points, npoints, &pts));
     const size_t bytes = ((size_t)32 << k) * npoly;
-    TRY(fr_ensure(c, c->in_a, bytes));
-    TRY(fr_stage_in(c, c->in_a, polys, bytes));
+    TRY(ensure(c, c->in_a, bytes));
+    TRY(stage_in(c, c->in_a, polys, bytes));
     TRY(clear_flags(c));
     return poly_eval_run(c, (const uint8_t*)c->in_a.p, k, queries, nq, pts, out);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_poly_divide_device(h2agg_ctx* c, const void* d_poly, unsigned k, const uint8_t z[32], void* d_quot, void* d_rem) try {
     TRY(bind(c));
@@ -286,7 +286,7 @@ int h2agg_fr_poly_divide_device(h2agg_ctx* c, const void* d_poly, unsigned k, co
     ph::HFr zf;
     TRY(poly_divide_check(c, k, z, &zf));
     return poly_divide_queue_one(c, (const uint8_t*)d_poly, k, zf, (uint8_t*)d_quot, (uint8_t*)d_rem);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_poly_divide(h2agg_ctx* c, const uint8_t* in, unsigned k, const uint8_t z[32], uint8_t* out, uint8_t rem[32]) try {
     TRY(bind(c));
@@ -294,14 +294,14 @@ int h2agg_fr_poly_divide(h2agg_ctx* c, const uint8_t* in, unsigned k, const uint
     ph::HFr zf;
     TRY(poly_divide_check(c, k, z, &zf));
     const size_t bytes = (size_t)32 << k;
-    TRY(fr_ensure(c, c->in_a, bytes + 32));
+    TRY(ensure(c, c->in_a, bytes + 32));
     uint8_t* d = (uint8_t*)c->in_a.p;
-    TRY(fr_stage_in(c, c->in_a, in, bytes));
+    TRY(stage_in(c, c->in_a, in, bytes));
     TRY(clear_flags(c));
     TRY(poly_divide_queue_one(c, d, k, zf, d, d + bytes));
     HIP_TRY(c, hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    return fr_stage_out(c, rem, d + bytes, 32);
-} FR_API_CATCH
+    return stage_out(c, rem, d + bytes, 32);
+} API_CATCH
 
 int h2agg_kzg_multiopen_device(h2agg_ctx* c, uint64_t g_handle, const void* d_polys, size_t npoly, unsigned k,
                                const uint32_t* queries, size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32],
@@ -313,7 +313,7 @@ int h2agg_kzg_multiopen_device(h2agg_ctx* c, uint64_t g_handle, const void* d_po
     TRY(multiopen_check(c, g_handle, k, npoly, queries, nq, points, npoints, v, w_aff, group_points, ngroups, &pts, &vf));
     TRY(clear_flags(c));
     return multiopen_run(c, g_handle, (const uint8_t*)d_polys, k, queries, nq, pts, vf, w_aff, group_points, ngroups);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_kzg_multiopen(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries,
                         size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32], uint8_t* w_aff,
@@ -324,10 +324,10 @@ int h2agg_kzg_multiopen(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, s
     ph::HFr vf;
     TRY(multiopen_check(c, g_handle, k, npoly, queries, nq, points, npoints, v, w_aff, group_points, ngroups, &pts, &vf));
     const size_t bytes = ((size_t)32 << k) * npoly;
-    TRY(fr_ensure(c, c->in_a, bytes));
-    TRY(fr_stage_in(c, c->in_a, polys, bytes));
+    TRY(ensure(c, c->in_a, bytes));
+    TRY(stage_in(c, c->in_a, polys, bytes));
     TRY(clear_flags(c));
     return multiopen_run(c, g_handle, (const uint8_t*)c->in_a.p, k, queries, nq, pts, vf, w_aff, group_points, ngroups);
-} FR_API_CATCH
+} API_CATCH
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Grand products, host side (included into h2agg.hip: shares the context internals; kernels and bounds in prod_kernels.hpp,
-// level plan, checks and staging in fr_host.inc, power tables in fr_fft.inc): h2agg_fr_batch_invert[_device],
+// level plan and checks in fr_host.inc, staging in host.inc, power tables in fr_fft.inc): h2agg_fr_batch_invert[_device],
 // h2agg_fr_grand_product[_device], h2agg_permutation_product[_device], h2agg_lookup_product[_device].  They stand for
 // halo2_proofs' ff::BatchInvert, permutation::prover::commit and lookup::prover::commit_product — an unvendored git dependency
 // of the reference, recalled from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.  Which
@@ -50,7 +50,7 @@ void prod_sweeps_queue(h2agg_ctx* c, uint32_t op, const uint8_t* d_src, const ui
     }
 }
 
-int prod_ensure_levels(h2agg_ctx* c, size_t n) { return fr_ensure(c, c->prod_lvl, 32 * prod_plan(c, n).total); }
+int prod_ensure_levels(h2agg_ctx* c, size_t n) { return ensure(c, c->prod_lvl, 32 * prod_plan(c, n).total); }
 
 // out[i] = 1 / in[i] (montgomery2 = false) or R^2 / in[i] (true: what the scan multiplies num with), 0 for 0; n >= 1
 int prod_invert_queue(h2agg_ctx* c, const uint8_t* d_in, size_t n, bool montgomery2, bool check, uint8_t* d_out) {
@@ -68,7 +68,7 @@ int prod_grand_queue(h2agg_ctx* c, const uint8_t* d_num, const uint8_t* d_den, s
     if (d_den && u) {
         uint8_t* inv = (uint8_t*)c->prod_den.p;
         if (d_den != inv) {
-            TRY(fr_ensure(c, c->prod_den, 32 * u));
+            TRY(ensure(c, c->prod_den, 32 * u));
             inv = (uint8_t*)c->prod_den.p;
         }
         TRY(prod_invert_queue(c, d_den, u, true, check, inv));
@@ -107,9 +107,9 @@ int perm_check(h2agg_ctx* c, size_t m, unsigned k, size_t u, const uint8_t* beta
 int perm_queue(h2agg_ctx* c, const uint8_t* d_values, const uint8_t* d_sigmas, size_t m, unsigned k, size_t u, const PermConsts& pc,
                uint8_t* d_out, uint8_t* d_last) {
     if (u) {
-        TRY(fr_ensure(c, c->prod_num, 32 * u));
-        TRY(fr_ensure(c, c->prod_den, 32 * u));
-        TRY(fr_ensure(c, c->prod_tab, fr_table_bytes(k)));
+        TRY(ensure(c, c->prod_num, 32 * u));
+        TRY(ensure(c, c->prod_den, 32 * u));
+        TRY(ensure(c, c->prod_tab, fr_table_bytes(k)));
         fr_table_launch(c, fft_omega(k), k, (uint8_t*)c->prod_tab.p);
         FrPermArgs a;
         hfr_words(ph::mul(pc.beta, fr_radix()), a.beta);
@@ -148,8 +148,8 @@ int lookup_check(h2agg_ctx* c, unsigned k, size_t u, const uint8_t* beta, const 
 int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uint8_t* d_ap, const uint8_t* d_sp, size_t u,
                  const ph::HFr& beta, const ph::HFr& gamma, uint8_t* d_out, uint8_t* d_last) {
     if (u) {
-        TRY(fr_ensure(c, c->prod_num, 32 * u));
-        TRY(fr_ensure(c, c->prod_den, 32 * u));
+        TRY(ensure(c, c->prod_num, 32 * u));
+        TRY(ensure(c, c->prod_den, 32 * u));
         FrLookupArgs a;
         hfr_words(beta, a.beta);
         hfr_words(gamma, a.gamma);
@@ -168,7 +168,7 @@ int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uin
 
 // the tail of every synchronous product call: out[0 .. u] and `last` back to the host
 int prod_download(h2agg_ctx* c, size_t u, uint8_t* out, uint8_t* last) {
-    TRY(fr_stage_out(c, out, c->out.p, 32 * (u + 1)));
+    TRY(stage_out(c, out, c->out.p, 32 * (u + 1)));
     if (last) memcpy(last, out + 32 * u, 32);
     return H2AGG_OK;
 }
@@ -183,19 +183,19 @@ int h2agg_fr_batch_invert_device(h2agg_ctx* c, const void* d_in, size_t n, void*
     if (n == 0) return H2AGG_OK;
     if (!d_in || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return prod_invert_queue(c, (const uint8_t*)d_in, n, false, true, (uint8_t*)d_out);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_batch_invert(h2agg_ctx* c, const uint8_t* in, size_t n, uint8_t* out) try {
     TRY(bind(c));
     if (n > PROD_MAX_N) return fail(c, H2AGG_ERR_INVALID, "n must be <= 2^24");
     if (n == 0) return H2AGG_OK;
     if (!in || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
-    TRY(fr_ensure(c, c->in_a, 32 * n));
-    TRY(fr_stage_in(c, c->in_a, in, 32 * n));
+    TRY(ensure(c, c->in_a, 32 * n));
+    TRY(stage_in(c, c->in_a, in, 32 * n));
     TRY(clear_flags(c));
     TRY(prod_invert_queue(c, (const uint8_t*)c->in_a.p, n, false, true, (uint8_t*)c->in_a.p));
-    return fr_stage_out(c, out, c->in_a.p, 32 * n);
-} FR_API_CATCH
+    return stage_out(c, out, c->in_a.p, 32 * n);
+} API_CATCH
 
 int h2agg_fr_grand_product_device(h2agg_ctx* c, const void* d_num, const void* d_den, unsigned k, size_t u, const uint8_t init[32],
                                   void* d_out, void* d_last) try {
@@ -205,7 +205,7 @@ int h2agg_fr_grand_product_device(h2agg_ctx* c, const void* d_num, const void* d
     ph::HFr initf;
     TRY(fr_parse(c, init, &initf));
     return prod_grand_queue(c, (const uint8_t*)d_num, (const uint8_t*)d_den, u, initf, true, (uint8_t*)d_out, (uint8_t*)d_last);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_fr_grand_product(h2agg_ctx* c, const uint8_t* num, const uint8_t* den, unsigned k, size_t u, const uint8_t init[32],
                            uint8_t* out, uint8_t last[32]) try {
@@ -214,16 +214,16 @@ int h2agg_fr_grand_product(h2agg_ctx* c, const uint8_t* num, const uint8_t* den,
     if (!num || !out || !init) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     ph::HFr initf;
     TRY(fr_parse(c, init, &initf));
-    TRY(fr_ensure(c, c->in_a, 32 * u + 32));
-    TRY(fr_ensure(c, c->in_b, 32 * u + 32));
-    TRY(fr_ensure(c, c->out, 32 * (u + 1)));
-    TRY(fr_stage_in(c, c->in_a, num, 32 * u));
-    if (den) TRY(fr_stage_in(c, c->in_b, den, 32 * u));
+    TRY(ensure(c, c->in_a, 32 * u + 32));
+    TRY(ensure(c, c->in_b, 32 * u + 32));
+    TRY(ensure(c, c->out, 32 * (u + 1)));
+    TRY(stage_in(c, c->in_a, num, 32 * u));
+    if (den) TRY(stage_in(c, c->in_b, den, 32 * u));
     TRY(clear_flags(c));
     TRY(prod_grand_queue(c, (const uint8_t*)c->in_a.p, den ? (const uint8_t*)c->in_b.p : nullptr, u, initf, true,
                          (uint8_t*)c->out.p, nullptr));
     return prod_download(c, u, out, last);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_permutation_product_device(h2agg_ctx* c, const void* d_values, const void* d_sigmas, size_t m, unsigned k, size_t u,
                                      const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta[32],
@@ -233,7 +233,7 @@ int h2agg_permutation_product_device(h2agg_ctx* c, const void* d_values, const v
     TRY(perm_check(c, m, k, u, beta, gamma, delta, delta_first, init, &pc));
     if (!d_values || !d_sigmas || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return perm_queue(c, (const uint8_t*)d_values, (const uint8_t*)d_sigmas, m, k, u, pc, (uint8_t*)d_out, (uint8_t*)d_last);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_permutation_product(h2agg_ctx* c, const uint8_t* values, const uint8_t* sigmas, size_t m, unsigned k, size_t u,
                               const uint8_t beta[32], const uint8_t gamma[32], const uint8_t delta[32],
@@ -243,15 +243,15 @@ int h2agg_permutation_product(h2agg_ctx* c, const uint8_t* values, const uint8_t
     TRY(perm_check(c, m, k, u, beta, gamma, delta, delta_first, init, &pc));
     if (!values || !sigmas || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     const size_t bytes = ((size_t)32 << k) * m;
-    TRY(fr_ensure(c, c->in_a, bytes));
-    TRY(fr_ensure(c, c->in_b, bytes));
-    TRY(fr_ensure(c, c->out, 32 * (u + 1)));
-    TRY(fr_stage_in(c, c->in_a, values, bytes));
-    TRY(fr_stage_in(c, c->in_b, sigmas, bytes));
+    TRY(ensure(c, c->in_a, bytes));
+    TRY(ensure(c, c->in_b, bytes));
+    TRY(ensure(c, c->out, 32 * (u + 1)));
+    TRY(stage_in(c, c->in_a, values, bytes));
+    TRY(stage_in(c, c->in_b, sigmas, bytes));
     TRY(clear_flags(c));
     TRY(perm_queue(c, (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, m, k, u, pc, (uint8_t*)c->out.p, nullptr));
     return prod_download(c, u, out, last);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_lookup_product_device(h2agg_ctx* c, const void* d_a, const void* d_s, const void* d_ap, const void* d_sp, unsigned k,
                                 size_t u, const uint8_t beta[32], const uint8_t gamma[32], void* d_out, void* d_last) try {
@@ -261,7 +261,7 @@ int h2agg_lookup_product_device(h2agg_ctx* c, const void* d_a, const void* d_s, 
     if (!d_a || !d_s || !d_ap || !d_sp || !d_out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     return lookup_queue(c, (const uint8_t*)d_a, (const uint8_t*)d_s, (const uint8_t*)d_ap, (const uint8_t*)d_sp, u, bf, gf,
                         (uint8_t*)d_out, (uint8_t*)d_last);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_lookup_product(h2agg_ctx* c, const uint8_t* a, const uint8_t* s, const uint8_t* ap, const uint8_t* sp, unsigned k, size_t u,
                          const uint8_t beta[32], const uint8_t gamma[32], uint8_t* out, uint8_t last[32]) try {
@@ -270,14 +270,14 @@ int h2agg_lookup_product(h2agg_ctx* c, const uint8_t* a, const uint8_t* s, const
     TRY(lookup_check(c, k, u, beta, gamma, &bf, &gf));
     if (!a || !s || !ap || !sp || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     const size_t col = (size_t)32 << k;
-    TRY(fr_ensure(c, c->in_a, 4 * col));
-    TRY(fr_ensure(c, c->out, 32 * (u + 1)));
+    TRY(ensure(c, c->in_a, 4 * col));
+    TRY(ensure(c, c->out, 32 * (u + 1)));
     const uint8_t* cols[4] = {a, s, ap, sp};
-    for (int i = 0; i < 4; ++i) TRY(fr_stage_in(c, c->in_a, cols[i], 32 * u, i * col));
+    for (int i = 0; i < 4; ++i) TRY(stage_in(c, c->in_a, cols[i], 32 * u, i * col));
     TRY(clear_flags(c));
     const uint8_t* d = (const uint8_t*)c->in_a.p;
     TRY(lookup_queue(c, d, d + col, d + 2 * col, d + 3 * col, u, bf, gf, (uint8_t*)c->out.p, nullptr));
     return prod_download(c, u, out, last);
-} FR_API_CATCH
+} API_CATCH
 
 }  // extern "C"

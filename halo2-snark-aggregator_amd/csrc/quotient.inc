@@ -1,6 +1,6 @@
 // The quotient polynomial h(X), host side (included into h2agg.hip behind lookup.inc: shares the context internals and reads
-// h2agg_vk, which is verifier.inc's; kernels, number forms and bounds in quotient_kernels.hpp, checks and staging in
-// fr_host.inc, transforms and power tables in fr_fft.inc): h2agg_vk_expressions_eval[_device], h2agg_quotient[_device].
+// h2agg_vk, which is verifier.inc's; kernels, number forms and bounds in quotient_kernels.hpp, checks in
+// fr_host.inc, staging in host.inc, transforms and power tables in fr_fft.inc): h2agg_vk_expressions_eval[_device], h2agg_quotient[_device].
 // They stand for the evaluation of h(X) in halo2_proofs' create_proof — an unvendored git dependency of the reference, recalled
 // from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.  Which expressions h has to satisfy,
 // and in which order, is pinned by halo2-snark-aggregator-api/src/systems/halo2/params.rs:74-224 and vanish.rs:18-72.
@@ -319,11 +319,11 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         return H2AGG_OK;
     }
     // ---- everything that may have to grow, before the first launch
-    TRY(fr_ensure(c, c->qt_work, 32 * l.total));
-    TRY(fr_ensure(c, c->qt_prog, 4 * prog_words + 4));
-    TRY(fr_ensure(c, c->qt_tab, fr_table_bytes(k)));
-    TRY(fr_ensure(c, c->frfft_work, std::max((size_t)32 << K, fr_fft_batch_work_bytes(l.polys, k))));
-    TRY(fr_ensure(c, c->frfft_shift, fr_table_bytes(K)));
+    TRY(ensure(c, c->qt_work, 32 * l.total));
+    TRY(ensure(c, c->qt_prog, 4 * prog_words + 4));
+    TRY(ensure(c, c->qt_tab, fr_table_bytes(k)));
+    TRY(ensure(c, c->frfft_work, std::max((size_t)32 << K, fr_fft_batch_work_bytes(l.polys, k))));
+    TRY(ensure(c, c->frfft_shift, fr_table_bytes(K)));
     if (K) {
         TRY(fr_fft_ensure_twiddles(c, K, 0));
         TRY(fr_fft_ensure_twiddles(c, K, 1));
@@ -442,12 +442,12 @@ int h2agg_vk_expressions_eval_device(h2agg_ctx* c, const h2agg_vk* vk, int which
     TRY(bind(c));
     QeEvalCall call;
     TRY(qe_eval_check(c, vk, which, j, k, d_advice, d_fixed, d_instance, challenges, fold, d_out, &call));
-    TRY(fr_ensure(c, c->qt_prog, 4 * call.prog.words()));
+    TRY(ensure(c, c->qt_prog, 4 * call.prog.words()));
     qe_eval_queue(c, call.prog, (uint32_t*)c->qt_prog.p, true, k, (const uint8_t*)d_advice, (const uint8_t*)d_fixed,
                   (const uint8_t*)d_instance, call.folded ? &call.fold : nullptr, nullptr, true, (uint8_t*)d_out);
     HIP_TRY(c, hipGetLastError());
     return H2AGG_OK;
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_vk_expressions_eval(h2agg_ctx* c, const h2agg_vk* vk, int which, size_t j, unsigned k, const uint8_t* advice,
                               const uint8_t* fixed, const uint8_t* instance, const uint8_t* challenges, const uint8_t fold[32],
@@ -457,19 +457,19 @@ int h2agg_vk_expressions_eval(h2agg_ctx* c, const h2agg_vk* vk, int which, size_
     TRY(qe_eval_check(c, vk, which, j, k, advice, fixed, instance, challenges, fold, out, &call));
     const size_t col = (size_t)32 << k;
     const size_t A = vk->num_advice, F = call.nfixed, I = vk->num_instance, outs = call.folded ? 1 : call.prog.m;
-    TRY(fr_ensure(c, c->in_a, (A + F + I) * col));
-    TRY(fr_ensure(c, c->out, outs * col));
-    TRY(fr_ensure(c, c->qt_prog, 4 * call.prog.words()));
-    TRY(fr_stage_in(c, c->in_a, advice, A * col));
-    TRY(fr_stage_in(c, c->in_a, fixed, F * col, A * col));
-    TRY(fr_stage_in(c, c->in_a, instance, I * col, (A + F) * col));
+    TRY(ensure(c, c->in_a, (A + F + I) * col));
+    TRY(ensure(c, c->out, outs * col));
+    TRY(ensure(c, c->qt_prog, 4 * call.prog.words()));
+    TRY(stage_in(c, c->in_a, advice, A * col));
+    TRY(stage_in(c, c->in_a, fixed, F * col, A * col));
+    TRY(stage_in(c, c->in_a, instance, I * col, (A + F) * col));
     TRY(clear_flags(c));
     const uint8_t* d = (const uint8_t*)c->in_a.p;
     qe_eval_queue(c, call.prog, (uint32_t*)c->qt_prog.p, true, k, d, d + A * col, d + (A + F) * col, call.folded ? &call.fold : nullptr,
                   nullptr, true, (uint8_t*)c->out.p);
     HIP_TRY(c, hipGetLastError());
-    return fr_stage_out(c, out, c->out.p, outs * col);
-} FR_API_CATCH
+    return stage_out(c, out, c->out.p, outs * col);
+} API_CATCH
 
 int h2agg_quotient_device(h2agg_ctx* c, const h2agg_vk* vk, const void* d_advice, const void* d_fixed, const void* d_instance,
                           const void* d_sigma, const void* d_perm_z, const void* d_lookup_z, const void* d_lookup_ap,
@@ -482,7 +482,7 @@ int h2agg_quotient_device(h2agg_ctx* c, const h2agg_vk* vk, const void* d_advice
     QtScalars sc;
     TRY(qt_check(c, vk, s, challenges, theta, beta, gamma, y, delta, d_h, &l, &sc));
     return qt_queue(c, *vk, l, sc, s, (uint8_t*)d_h);
-} FR_API_CATCH
+} API_CATCH
 
 int h2agg_quotient(h2agg_ctx* c, const h2agg_vk* vk, const uint8_t* advice, const uint8_t* fixed, const uint8_t* instance,
                    const uint8_t* sigma, const uint8_t* perm_z, const uint8_t* lookup_z, const uint8_t* lookup_ap,
@@ -499,14 +499,14 @@ int h2agg_quotient(h2agg_ctx* c, const h2agg_vk* vk, const uint8_t* advice, cons
     size_t at[9] = {0};
     for (int i = 0; i < 8; ++i) at[i + 1] = at[i] + count[i] * col;
     const size_t out_bytes = col * (vk->degree - 1);
-    TRY(fr_ensure(c, c->in_a, at[8]));
-    TRY(fr_ensure(c, c->out, out_bytes));
-    for (int i = 0; i < 8; ++i) TRY(fr_stage_in(c, c->in_a, host[i], count[i] * col, at[i]));
+    TRY(ensure(c, c->in_a, at[8]));
+    TRY(ensure(c, c->out, out_bytes));
+    for (int i = 0; i < 8; ++i) TRY(stage_in(c, c->in_a, host[i], count[i] * col, at[i]));
     TRY(clear_flags(c));
     const uint8_t* d = (const uint8_t*)c->in_a.p;
     const QtSlabs ds = {d + at[0], d + at[1], d + at[2], d + at[3], d + at[4], d + at[5], d + at[6], d + at[7]};
     TRY(qt_queue(c, *vk, l, sc, ds, (uint8_t*)c->out.p));
-    return fr_stage_out(c, h, c->out.p, out_bytes);
-} FR_API_CATCH
+    return stage_out(c, h, c->out.p, out_bytes);
+} API_CATCH
 
 }  // extern "C"

@@ -314,11 +314,7 @@ int h2agg_schema_create(h2agg_ctx* c, h2agg_schema** out) try {
     sc->ctx = c;
     *out = sc;
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 void h2agg_schema_destroy(h2agg_schema* sc) {
     if (!sc) return;
     if (sc->ctx->sch_owner == sc) sc->ctx->sch_owner = nullptr;   // device scratch belongs to the context
@@ -328,49 +324,29 @@ int h2agg_schema_node_commitment(h2agg_schema* sc, const char* key, const uint8_
     if (!sc || !key || !point_aff || !node) return H2AGG_ERR_INVALID;
     *node = sc->s.add_commitment(key, point_aff);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_node_eval(h2agg_schema* sc, const uint8_t eval[32], uint32_t* node) try {
     if (!sc || !eval || !node) return H2AGG_ERR_INVALID;
     *node = sc->s.add_leaf_scalar(SchemaNode::EVAL, eval);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_node_scalar(h2agg_schema* sc, const uint8_t scalar[32], uint32_t* node) try {
     if (!sc || !scalar || !node) return H2AGG_ERR_INVALID;
     *node = sc->s.add_leaf_scalar(SchemaNode::SCALAR, scalar);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_node_add(h2agg_schema* sc, uint32_t l, uint32_t r, uint32_t* node) try {
     if (!sc || !node) return H2AGG_ERR_INVALID;
     if (!sc->s.valid(l) || !sc->s.valid(r)) return fail(sc->ctx, H2AGG_ERR_INVALID, "unknown schema node");
     *node = sc->s.add_binary(SchemaNode::ADD, l, r);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_node_mul(h2agg_schema* sc, uint32_t l, uint32_t r, uint32_t* node) try {
     if (!sc || !node) return H2AGG_ERR_INVALID;
     if (!sc->s.valid(l) || !sc->s.valid(r)) return fail(sc->ctx, H2AGG_ERR_INVALID, "unknown schema node");
     *node = sc->s.add_binary(SchemaNode::MUL, l, r);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_evaluation_queries(h2agg_schema* sc, size_t n, const char* const* keys, const uint8_t* commitments,
                                     const uint8_t* evals, uint32_t* nodes_out) try {
     if (!sc) return H2AGG_ERR_INVALID;
@@ -381,11 +357,7 @@ int h2agg_schema_evaluation_queries(h2agg_schema* sc, size_t n, const char* cons
         nodes_out[i] = sc->s.add_evaluation_query(keys[i], commitments + 64 * i, evals + 32 * i);
     }
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_query_set_commitment(h2agg_schema* sc, uint32_t query_node, const uint8_t point_aff[64]) try {
     if (!sc || !point_aff) return H2AGG_ERR_INVALID;
     Schema& S = sc->s;
@@ -394,11 +366,7 @@ int h2agg_schema_query_set_commitment(h2agg_schema* sc, uint32_t query_node, con
         return fail(sc->ctx, H2AGG_ERR_INVALID, "not an EvaluationQuery node ([C] + eval)");
     memcpy(S.points.data() + 64 * (size_t)S.nodes[S.nodes[query_node].l].point, point_aff, 64);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_batch_multi_open(h2agg_schema* sc, const char* key, size_t nq, const int32_t* rotations,
                                   const uint8_t* points, const uint32_t* query_nodes, size_t nw, const uint8_t* w,
                                   const uint8_t v[32], const uint8_t u[32], uint32_t* w_x_out, uint32_t* w_g_out) try {
@@ -408,21 +376,13 @@ int h2agg_schema_batch_multi_open(h2agg_schema* sc, const char* key, size_t nq, 
     if (!sc->s.batch_multi_open(key, nq, rotations, points, query_nodes, nw, w, v, u, *w_x_out, *w_g_out))
         return fail(sc->ctx, H2AGG_ERR_INVALID, sc->s.err);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 int h2agg_schema_estimate(h2agg_schema* sc, uint32_t node, size_t* out) try {
     if (!sc || !out) return H2AGG_ERR_INVALID;
     if (!sc->s.valid(node)) return fail(sc->ctx, H2AGG_ERR_INVALID, "unknown schema node");
     *out = sc->s.estimate(node, false);
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_schema_eval(h2agg_schema* sc, uint32_t node, uint8_t out_jac[96], int* has_scalar, uint8_t out_scalar[32]) try {
     if (!sc) return H2AGG_ERR_INVALID;
@@ -442,11 +402,7 @@ int h2agg_schema_eval(h2agg_schema* sc, uint32_t node, uint8_t out_jac[96], int*
         TRY(fetch_reg_canonical(sc, sc->s.tape.resolve((uint32_t)L.e_reg), out_scalar));
     }
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 namespace {
 // host half of evaluate_multiopen_proof (verify.rs:705-728): both eval_prepare walks recorded on the tape, and the
@@ -588,11 +544,7 @@ int h2agg_evaluate_multiopen_prepare(h2agg_schema* sc, uint32_t w_x, uint32_t w_
     P.consts_n = S.tape.nconst;
     P.valid = true;
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_evaluate_multiopen_proof(h2agg_schema* sc, uint32_t w_x, uint32_t w_g, uint8_t left_aff[64],
                                    uint8_t right_aff[64]) try {
@@ -668,11 +620,7 @@ int h2agg_evaluate_multiopen_proof(h2agg_schema* sc, uint32_t w_x, uint32_t w_g,
     memcpy(right_aff, aff + 64, 64);
     S.names = all_names;  // points_wx ++ points_wg  (verify.rs:711-712)
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // A straight-line Fr program on the device: the interpreter that EvaluationQuerySchema::eval records into, exposed for
 // callers that have their own expressions (SURVEY.md 8(f)-1: the lookup / permutation / vanishing / lagrange expressions of
@@ -718,11 +666,7 @@ int h2agg_fr_tape_eval(h2agg_ctx* c, const uint8_t* consts, size_t nconst, const
                        (uint8_t*)c->sch_scalars[0].p);
     HIP_TRY(c, hipMemcpyAsync(out, c->sch_scalars[0].p, nout * 32, hipMemcpyDeviceToHost, st));
     return finish(c);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 size_t h2agg_schema_name_count(h2agg_schema* sc) { return sc ? sc->s.names.size() : 0; }
 const char* h2agg_schema_name(h2agg_schema* sc, size_t i) {

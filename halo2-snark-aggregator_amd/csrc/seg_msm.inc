@@ -109,10 +109,6 @@ int h2agg_g1_msm_segmented(h2agg_ctx* c, const uint8_t* bases_aff, const uint8_t
     if (rc != H2AGG_OK)
         for (size_t s = 0; s < nseg; ++s) set_identity_jac(out_jac + 96 * s);
     return rc;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 }  // extern "C"

@@ -703,11 +703,7 @@ int h2agg_hash_transcript_read_batch(h2agg_ctx* c, int kind, const uint8_t* proo
     if (!L.upto.empty() && !host)
         HIP_TRY(c, hipMemcpyAsync(challenges_out, c->tr_chal.p, nproofs * L.upto.size() * 32, hipMemcpyDeviceToHost, c->stream));
     return finish(c);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // the host backend on its own: no context, no device (CPU-testable), like h2agg_poseidon_squeeze_batch_host
 int h2agg_hash_transcript_read_batch_host(int kind, const uint8_t* proofs, size_t proof_len, size_t nproofs, const char* script,
@@ -725,11 +721,7 @@ int h2agg_hash_transcript_read_batch_host(int kind, const uint8_t* proofs, size_
                                             max_threads > 0 ? max_threads : 1 << 30);
     // (the order of flags_to_status)
     return (f & FLAG_NONCANONICAL) ? H2AGG_ERR_NONCANONICAL : (f & FLAG_BAD_POINT) ? H2AGG_ERR_BAD_POINT : H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_hash_digest_host(int kind, const uint8_t* msg, size_t len, uint8_t out[32]) {
     if (!hash_kind_ok(kind) || (len && !msg) || !out) return H2AGG_ERR_INVALID;
@@ -769,11 +761,7 @@ int h2agg_poseidon_squeeze_batch(h2agg_ctx* c, const uint8_t* elems, size_t npro
                      (uint8_t*)c->tr_chal.p));
     HIP_TRY(c, hipMemcpyAsync(out, c->tr_chal.p, nproofs * nsq * 32, hipMemcpyDeviceToHost, c->stream));
     return finish(c);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // the host twin of h2agg_poseidon_squeeze_batch: no context, no device (what the host backend runs; CPU-testable)
 int h2agg_poseidon_squeeze_batch_host(const uint8_t* elems, size_t nproofs, size_t nelem, const uint32_t* upto, size_t nsq,
@@ -797,11 +785,7 @@ int h2agg_poseidon_squeeze_batch_host(const uint8_t* elems, size_t nproofs, size
     const int cap = max_threads & 0xffff, kind = (max_threads & 0x10000) ? 0 : (max_threads & 0x20000) ? 1 : -1;
     return poseidon_run_host(elems, stride, upto, (uint32_t)nsq, nproofs, out, cap > 0 ? cap : 1 << 30, kind)
                ? H2AGG_ERR_NONCANONICAL : H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_transcript_configure(h2agg_ctx* c, int backend) {
     if (!c || backend < 0 || backend > 2) return H2AGG_ERR_INVALID;
@@ -840,10 +824,6 @@ int h2agg_transcript_read_batch(h2agg_ctx* c, const uint8_t* proofs, size_t proo
     if (!L.upto.empty() && !host)
         HIP_TRY(c, hipMemcpyAsync(challenges_out, c->tr_chal.p, nproofs * L.upto.size() * 32, hipMemcpyDeviceToHost, c->stream));
     return finish(c, host_flags);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 }  // extern "C"

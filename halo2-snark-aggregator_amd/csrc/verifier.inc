@@ -440,11 +440,7 @@ int h2agg_vk_create(h2agg_ctx* c, const uint8_t* blob, size_t len, h2agg_vk** ou
     vk->uid = next_uid.fetch_add(1);
     *out = vk.release();
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 void h2agg_vk_destroy(h2agg_vk* vk) { delete vk; }
 

@@ -1003,11 +1003,7 @@ int verify_aggregation(h2agg_ctx* c, const AggCall& call) try {
     }
     st.sponges.join();   // (an early return between post() and join(): the chains end before this rank's exchange, as ever)
     return xch.leave(rc);
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 // ---- h2agg_verify_proofs: each proof on its own ---------------------------------------------------------------------------
 // e(left_i, s_g2) * e(right_i, -g2) == 1 for every proof whose status is OK, one proof per job on the host pool; the prepared
@@ -1208,11 +1204,7 @@ int h2agg_verify_proofs(h2agg_ctx* c, const h2agg_circuit_proofs* circuits, size
         }
     }
     return H2AGG_OK;
-} catch (const std::bad_alloc&) {
-    return H2AGG_ERR_NOMEM;   // no C++ exception crosses the C ABI
-} catch (...) {
-    return H2AGG_ERR_INVALID;
-}
+} API_CATCH
 
 int h2agg_verify_plan_stats(h2agg_ctx* c, uint64_t* hits, uint64_t* misses, uint64_t* plans_kept) {
     if (!c) return H2AGG_ERR_INVALID;
