@@ -29,8 +29,10 @@ FR_SORT_TILE_MIN = 4
 FR_COMPRESS_MAX_COLUMNS = 1 << 16   # most columns of one fr_columns_compress (the library's limit: csrc/lookup.inc)
 PERM_MAX_COLUMNS = 4096   # H2AGG_PERM_MAX_COLUMNS: most columns of one permutation (csrc/keygen_kernels.hpp)
 EXPR_MAX_DEPTH = 16  # H2AGG_EXPR_MAX_DEPTH: the operand stack of h2agg_vk_expressions_eval / h2agg_quotient (csrc/quotient_kernels.hpp)
+WC_GATES, WC_PERMUTATION, WC_LOOKUPS = 1, 2, 4   # H2AGG_WC_*: the kinds of constraint h2agg_witness_check checks
+WC_NONE = 0xFFFFFFFF   # "no row" in its report
 
-IDENTITY_JAC = (0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
+IDENTITY_JAC =(0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
 
 class H2AggError(RuntimeError):
@@ -191,6 +193,8 @@ def load_library():
         "h2agg_permutation_assembly": (i32, [sz, C.c_uint, sz, vp, sz, vp]),
         "h2agg_permutation_sigmas": (i32, [ctxp, vp, sz, C.c_uint, sz, u8p, vp, vp]),
         "h2agg_commit_columns": (i32, [ctxp, u64, vp, sz, C.c_uint, vp]),
+        "h2agg_witness_check_layout": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "h2agg_witness_check": (i32, [ctxp, vp, C.c_uint, vp, vp, vp, u8p, u8p, vp, sz, vp, vp, vp, C.POINTER(u64)]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -852,6 +856,40 @@ class H2Agg:
         out = C.create_string_buffer(max(64 * m, 1))
         self._check(self._lib.h2agg_commit_columns(self._ctx, handle, self._hostptr(columns), m, k, out))
         return [out.raw[64 * j:64 * j + 64] for j in range(m)]
+
+    # ------------------------------------------------------------------ witness check
+    def witness_check_layout(self, vk):
+        """h2agg_witness_check_layout: -> (gate polynomials, permutation columns, lookups) of the key: the constraints of
+        witness_check, in that order"""
+        g, p, l = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._check(self._lib.h2agg_witness_check_layout(vk._vk, C.byref(g), C.byref(p), C.byref(l)))
+        return g.value, p.value, l.value
+
+    def witness_check(self, vk, what: int, advice, fixed, instance, challenges, theta: Optional[bytes], mapping,
+                      max_rows: int = 16, want_rows: bool = True):
+        """h2agg_witness_check: Lagrange value slabs [columns][2^k] on the host (None for a slab without columns), the
+        permutation's mapping (2 * P * 2^k words as permutation_assembly returns it, or None) and theta (or None) ->
+        (counts, first_rows, rows, total): per constraint (gate polynomials, then permutation columns, then lookups) the
+        number of failing rows, the lowest one (0xFFFFFFFF: none) and the lowest max_rows of them (rows[c]: a list of
+        max_rows words, 0xFFFFFFFF behind the last; None with want_rows=False), and the sum of the counts.  `what`: WC_GATES |
+        WC_PERMUTATION | WC_LOOKUPS.  The sizes come from vk.shape."""
+        sh = vk.shape
+        k = sh["k"]
+        ncons = sh["gate_polys"] + sh["num_permutation_columns"] + len(sh["lookups"])
+        if theta is not None:
+            _need(theta, 32, "theta")
+        if max_rows < 0:
+            raise ValueError("max_rows must be >= 0")
+        slabs = self._vk_slabs(vk, k, ((advice, sh["num_advice"], "advice"), (fixed, sh["num_fixed"], "fixed"),
+                                       (instance, sh["num_instance"], "instance")))
+        words = None if mapping is None else _words(mapping, 2 * sh["num_permutation_columns"] << k, "mapping")
+        counts, first = (C.c_uint32 * max(ncons, 1))(), (C.c_uint32 * max(ncons, 1))()
+        rows = (C.c_uint32 * max(ncons * max_rows, 1))() if want_rows else None
+        total = C.c_uint64()
+        self._check(self._lib.h2agg_witness_check(self._ctx, vk._vk, what, *slabs, self._vk_challenges(vk, challenges), theta, words,
+                                                  max_rows, counts, first, rows, C.byref(total)))
+        lines = None if rows is None else [list(rows[c * max_rows:(c + 1) * max_rows]) for c in range(ncons)]
+        return list(counts[:ncons]), list(first[:ncons]), lines, total.value
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

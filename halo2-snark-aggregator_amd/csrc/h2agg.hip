@@ -40,6 +40,7 @@
 #include "lookup_kernels.hpp"
 #include "quotient_kernels.hpp"
 #include "keygen_kernels.hpp"
+#include "witness_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -337,6 +338,9 @@ struct h2agg_ctx {
     // keygen (csrc/keygen.inc): one bit per cell of a permutation's mapping, the table of delta^c, the Jacobian commitments of a
     // slab commit
     DevBuf kg_bitmap, kg_delta, kg_jac;
+    // witness check (csrc/witness.inc): the flag lines of a chunk of constraints, the tile sums and minima of its report, a
+    // lookup's two theta-folds, the report (wc_layout); programs go to qt_prog, the sort works in lk_work
+    DevBuf wc_work;
     std::string last_phases;   // debug key phases: the last h2agg_verify_aggregation's wall-clock split (h2agg_last_phases)
     // tuning
     int cfg_c = 0, cfg_seg = 0, cfg_big = 0, cfg_sub_bits = 0, cfg_tile = 0;
@@ -812,3 +816,4 @@ int h2agg_synchronize(h2agg_ctx* c) try {
 #include "lookup.inc"
 #include "quotient.inc"
 #include "keygen.inc"
+#include "witness.inc"

@@ -143,7 +143,9 @@ void qe_eval_queue(h2agg_ctx* c, const QeProgram& p, uint32_t* d_prog, bool uplo
     a.n = n;
     a.folded = fold != nullptr;
     a.check = check;
-    hipLaunchKernelGGL(k_qe_eval, dim3((n + QE_THREADS - 1) / QE_THREADS), dim3(QE_THREADS), 0, c->stream, a);
+    a.zflags = nullptr;
+    a.zwords = a.u = 0;
+    hipLaunchKernelGGL(k_qe_eval<false>, dim3((n + QE_THREADS - 1) / QE_THREADS), dim3(QE_THREADS), 0, c->stream, a);
 }
 
 struct QeEvalCall {

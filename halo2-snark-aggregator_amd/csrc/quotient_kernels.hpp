@@ -14,7 +14,7 @@
 // [slot][limb][thread], so the 64 lanes of the one wave of a workgroup hit 64 different banks and no per-thread array is
 // indexed dynamically (that would be scratch memory).  QE_DEPTH - 1 = 15 slots x 9 limbs x 64 threads x 4 B = 33.75 KiB.
 // QE_END closes an expression: its value is stored to its own column, or folded into an accumulator in registers
-// (acc = acc * fold + value: the first expression ends under the highest power).
+// (acc = acc * fold + value: the first expression ends under the highest power), or — k_qe_eval<true> — only tested for zero.
 //
 // Number forms.  Everything on the stack is in Montgomery form.  A leaf costs one product (x * R^2 / R), the result one
 // (value * 1 / R) and a conditional subtraction: stored values are canonical.  Bounds, in units of r: a leaf < 1.04 (a
@@ -62,13 +62,32 @@ struct QeArgs {
     uint32_t ninstr, n;
     uint32_t folded;
     uint32_t check;           // the slabs are the caller's: elements are checked for < r
+    uint32_t* zflags;         // k_qe_eval<true>: [expressions][zwords], bit (i & 31) of word i >> 5 is row i (witness_kernels.hpp)
+    uint32_t zwords;          //   2 ceil(n / 64): every wave owns the two words of its 64 rows
+    uint32_t u;               //   rows from u up are never flagged
 };
 
 FP_INLINE uint32_t qe_slot(uint32_t slot, uint32_t limb, uint32_t tid) { return (slot * NL + limb) * QE_THREADS + tid; }
 
+// One flag bit per row: the wave that holds the rows [i0, i0 + 64), i0 = i & ~63, stores their bits as the two words
+// 2 (i0 >> 6) and 2 (i0 >> 6) + 1 of `line` — both < 2 ceil(n / 64) because row i0 < n.  Every thread of a workgroup of a
+// multiple of 64 threads with i = blockIdx.x * blockDim.x + threadIdx.x < n calls it from converged code: lane 0 of a wave
+// with a row below n is such a thread (i0 <= i), and a lane that has left (i >= n) votes 0.  No atomics: a word has one writer.
+FP_INLINE void qe_put_flag(bool fails, uint32_t* __restrict__ line, uint32_t i) {
+    const uint64_t m = __ballot(fails);
+    if ((threadIdx.x & 63u) == 0u) {
+        line[2u * (i >> 6)] = (uint32_t)m;
+        line[2u * (i >> 6) + 1u] = (uint32_t)(m >> 32);
+    }
+}
+
 // Program invariants (qe_compile, quotient.inc): every QE_COLUMN has a column inside its slab and b < n; every constant
 // index is inside the pool; an operator finds its operands; at most QE_DEPTH values are live, so `cnt - 1 <= QE_DEPTH - 1`
 // values sit in LDS, slots 0 .. QE_DEPTH - 2; QE_END finds exactly one value.  Rows: i < n, (i + b) & (n - 1) < n.
+// FLAGS (the witness check's ending, witness_kernels.hpp): QE_END stores no value; it reduces the top of the stack (any
+// representative of 0 below 2r — 0, r, 2r — becomes the integer 0) and sets bit i of line e of zflags where the value is not
+// zero and i < u.  Line e < the program's expressions = the lines the host sized zflags for.  Nothing is written to `out`.
+template <bool FLAGS>
 __global__ void __launch_bounds__(QE_THREADS) k_qe_eval(const QeArgs a) {
     __shared__ uint32_t st[(QE_DEPTH - 1) * NL * QE_THREADS];
     const uint32_t tid = threadIdx.x;
@@ -113,13 +132,14 @@ __global__ void __launch_bounds__(QE_THREADS) k_qe_eval(const QeArgs a) {
         } else if (op == QE_SCALED) {
             tos = fp_mul<FrParams>(tos, fp_load<FrParams>(a.consts + 8 * (size_t)wa));
         } else {   // QE_END
-            if (a.folded) acc = fr_fft_reduce2(fp_add<FrParams>(fp_mul<FrParams>(acc, foldM), tos));
+            if constexpr (FLAGS) qe_put_flag(i < a.u && !fp_from_mont<FrParams>(tos).is_zero_int(), a.zflags + (size_t)e * a.zwords, i);
+            else if (a.folded) acc = fr_fft_reduce2(fp_add<FrParams>(fp_mul<FrParams>(acc, foldM), tos));
             else fp_store<FrParams>(a.out + 32 * ((size_t)e * a.n + i), fp_from_mont<FrParams>(tos));
             ++e;
             cnt = 0;
         }
     }
-    if (a.folded) fp_store<FrParams>(a.out + 32 * (size_t)i, fp_from_mont<FrParams>(acc));
+    if (!FLAGS && a.folded) fp_store<FrParams>(a.out + 32 * (size_t)i, fp_from_mont<FrParams>(acc));
 }
 
 // The rows of l_0, l_last and l_blind in Lagrange form: dst[0][i] = (i == 0), dst[1][i] = (i == u), dst[2][i] = (i > u); i < n

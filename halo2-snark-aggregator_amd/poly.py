@@ -4,7 +4,8 @@ and the grand products of the permutation and lookup arguments (h2agg_fr_batch_i
 h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr_columns_compress, h2agg_lookup_permute);
 and the quotient polynomial h(X) from a verifying key (h2agg_vk_expressions_eval, h2agg_quotient); and the keys those stages
 take: the permutation's mapping, sigma columns and commitments, the fixed columns' (h2agg_permutation_assembly,
-h2agg_permutation_sigmas, h2agg_commit_columns).
+h2agg_permutation_sigmas, h2agg_commit_columns); and, in front of all that work, the check whether a witness satisfies the key
+at all, and where it does not (h2agg_witness_check).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -276,6 +277,50 @@ def commit_quotient(eng, g_handle: int, pieces):
     Jacobian points (the h commitments a proof carries, vanish.rs:18-72).  (Not the slab call: that one answers canonical
     affine points, these stay the Jacobian bytes they were.)"""
     return [commit_coeff(eng, g_handle, p) for p in pieces]
+
+
+# ---------------------------------------------------------------------------------------------- witness check
+WC_KINDS = ("gate", "permutation", "lookup")
+
+
+class WitnessReport:
+    """what h2agg_witness_check answers.  counts, first_rows: one entry per constraint (gate polynomials, then permutation
+    columns, then lookups); rows: per constraint the lowest max_rows failing rows, ascending (None if none were asked for);
+    total: the sum of the counts; ok: total == 0; failures: [(kind, index within the kind, row), ...] over the reported rows
+    (with no rows reported: the first row of every failing constraint), in constraint order, rows ascending."""
+
+    def __init__(self, layout, counts, first_rows, rows, total):
+        self.layout, self.counts, self.first_rows, self.rows, self.total = tuple(layout), counts, first_rows, rows, total
+        self.ok = total == 0
+        self.failures = []
+        c = 0
+        for kind, count in zip(WC_KINDS, self.layout):
+            for index in range(count):
+                if rows is not None and rows[c]:
+                    self.failures += [(kind, index, r) for r in rows[c] if r != 0xFFFFFFFF]
+                elif counts[c]:
+                    self.failures.append((kind, index, first_rows[c]))
+                c += 1
+
+    def __repr__(self):
+        return "WitnessReport(ok=%s, total=%d, failures=%r)" % (self.ok, self.total, self.failures)
+
+
+def witness_check(eng, vk, advice, fixed, instance, challenges, theta=None, mapping=None, what=None, max_rows=16):
+    """dev::MockProver::verify's gate, permutation and lookup checks on the device (h2agg_witness_check): does this witness —
+    lists of Lagrange columns per kind, 2^k elements each — satisfy the key, and if not, which constraint fails on which
+    rows?  mapping: the permutation's mapping (permutation_mapping), theta: the lookups' compression challenge.  what: a
+    set of WC_* bits of the package; None: every kind the arguments allow (the permutation needs mapping, the lookups
+    theta).  -> a WitnessReport."""
+    from . import WC_GATES, WC_LOOKUPS, WC_PERMUTATION
+    sh = vk.shape
+    k = sh["k"]
+    if what is None:
+        what = WC_GATES | (WC_PERMUTATION if mapping is not None else 0) | (WC_LOOKUPS if theta is not None else 0)
+    counts, first_rows, rows, total = eng.witness_check(
+        vk, what, _slab(advice, sh["num_advice"], k, "advice"), _slab(fixed, sh["num_fixed"], k, "fixed"),
+        _slab(instance, sh["num_instance"], k, "instance"), _challenges(vk, challenges), theta, mapping, max_rows, max_rows > 0)
+    return WitnessReport(eng.witness_check_layout(vk), counts, first_rows, rows, total)
 
 
 # ---------------------------------------------------------------------------------------------- keys

@@ -854,6 +854,60 @@ int h2agg_permutation_sigmas(h2agg_ctx* ctx, const uint32_t* mapping, size_t m, 
                              uint8_t* sigma_lagrange, uint8_t* sigma_coeff);
 int h2agg_commit_columns(h2agg_ctx* ctx, uint64_t bases_handle, const uint8_t* columns, size_t m, unsigned k, uint8_t* out_aff);
 
+/* ---- Witness check: which gate, lookup or copy constraint a witness fails, and on which rows ------------------------------
+ * Stand for: the gate, lookup and permutation checks of dev::MockProver::verify of halo2_proofs — recalled from upstream, not
+ * pinned, like the blocks above; what the entry points compute is this definition.  The order of the constraints IS pinned:
+ * halo2-snark-aggregator-api/src/systems/halo2/params.rs:74-224 (gates, then the permutation, then every lookup).
+ *
+ * Slabs (advice, fixed, instance: Lagrange values, [columns][n]) and challenges are those of h2agg_vk_expressions_eval; n = 2^k
+ * and u = n - blinding_factors - 1 are the key's.  Host buffers, synchronous.
+ *
+ * Constraints are numbered 0 .. C-1, C = G + P + L (h2agg_witness_check_layout gives the three): first the G gate polynomials
+ * in key order, gate by gate and poly by poly (the list of which = 0), then the P permutation columns g = 0 .. P-1, then the
+ * L lookups.  `what` is a set of H2AGG_WC_* bits: the kinds to check.
+ *   counts[C]           the number of failing rows of each constraint
+ *   first_rows[C]       its lowest failing row, or 0xFFFFFFFF if there is none
+ *   rows[C][max_rows]   the lowest min(count, max_rows) failing rows of each constraint in ascending order, the rest of the
+ *                       line 0xFFFFFFFF; rows may be NULL and max_rows may be 0: no rows are reported
+ *   total               the sum of the counts
+ * A constraint whose kind is not in `what` reports 0 / 0xFFFFFFFF / an empty line.  The call returns H2AGG_OK whether or
+ * not anything fails: the report is the result.
+ * What "fails" means:
+ *   gate polynomial E, row i < u:  E(row i) != 0 in Fr.  Leaves and rotations are exactly those of h2agg_vk_expressions_eval:
+ *     rows wrap mod n, so a rotation may read a blinding row.  Rows from u up are never reported.
+ *   permutation column g, row i < n:  with v(c, r) the value of the key's permutation column c at row r (taken from the
+ *     advice / fixed / instance slab the key names for it) and {c', r'} = mapping[g][i] (the mapping of
+ *     h2agg_permutation_assembly / h2agg_permutation_sigmas over the key's P columns): v(g, i) != v(c', r').  In a cycle
+ *     a -> b -> c -> a with b's value changed, cells a and b fail and c does not.
+ *   lookup j, row i < u:  with A and S the theta-folds of its input and table expressions (h2agg_vk_expressions_eval with
+ *     fold = theta, which = 1 / 2): A[i] does not occur among S[0..u) — the predicate h2agg_lookup_permute refuses on, per
+ *     row.  For a one-expression lookup this is MockProver's tuple test exactly; for a longer tuple it is the test on the
+ *     folds: a row whose tuple is absent passes only if its fold collides with a table row's, which for a theta drawn
+ *     after the witness happens with probability at most (tuple length - 1) u / r per row.
+ * mapping is read iff H2AGG_WC_PERMUTATION is set and P > 0, theta iff H2AGG_WC_LOOKUPS is set and L > 0 (they may be NULL
+ * otherwise).  Every column element a requested check reads is checked for < r.
+ *
+ * Work memory, kept in the context: one BIT per (constraint, row) — never a value per (constraint, row) —
+ * for at most 2^24 flag words (64 MiB) at a time: a key with more than 2^29 / n gate polynomials or permutation columns (32
+ * at k = 24) is run in chunks of that many; the 32-bit sums and minima of 2048-row tiles; two columns per lookup call; the
+ * sort's work memory of h2agg_lookup_permute; the staged slabs and mapping.  Only the report crosses back to the host:
+ * (2 + max_rows) C words and the total.  With the debug key "phases" h2agg_last_phases gives " gates=ms permutation=ms
+ * lookups=ms report=ms".
+ * Refusals, the context stays usable after each: a null vk, context or required buffer (counts, first_rows and total are
+ *   required), what == 0 or an unknown bit in it, a mapping entry with c' >= P or r' >= n (scanned on the host), an expression
+ *   of a requested kind deeper than H2AGG_EXPR_MAX_DEPTH: H2AGG_ERR_INVALID.  A scalar (challenge, theta, a CONST of the key)
+ *   >= r: H2AGG_ERR_NONCANONICAL from the call.  A column element >= r: H2AGG_ERR_NONCANONICAL through the context's device
+ *   status, from the call; the outputs are then unspecified.  Out of memory: H2AGG_ERR_NOMEM.
+ *
+ * These entry points have no device-memory twins yet; the function behind the check takes device pointers. */
+#define H2AGG_WC_GATES 1
+#define H2AGG_WC_PERMUTATION 2
+#define H2AGG_WC_LOOKUPS 4
+int h2agg_witness_check_layout(const h2agg_vk* vk, size_t* n_gate_polys, size_t* n_perm_columns, size_t* n_lookups);
+int h2agg_witness_check(h2agg_ctx* ctx, const h2agg_vk* vk, unsigned what, const uint8_t* advice, const uint8_t* fixed,
+                        const uint8_t* instance, const uint8_t* challenges, const uint8_t theta[32], const uint32_t* mapping,
+                        size_t max_rows, uint32_t* counts, uint32_t* first_rows, uint32_t* rows, uint64_t* total);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;
@@ -916,7 +970,8 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *       "phases" 0|1      keep every aggregation call's wall-clock split, and every h2agg_kzg_multiopen* call's split by events
  *                         (combine / divide / commit) and every h2agg_quotient* call's (forward / gates / permutation / lookups /
  *                         inverse; the queued form then waits for its own events) and every h2agg_permutation_sigmas call's
- *                         (stage / sigma / inverse / copy), for h2agg_last_phases
+ *                         (stage / sigma / inverse / copy) and every h2agg_witness_check call's (gates / permutation / lookups /
+ *                         report), for h2agg_last_phases
  *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
  *                         1024 elements then run the multi-pass paths
  *       "fr_fft_batch_chunk" B  a batched transform (h2agg_fr_fft_batch, the transforms inside h2agg_quotient) runs in chunks of
