@@ -174,6 +174,10 @@ def load_library():
                                       C.POINTER(C.c_uint32), C.POINTER(sz)]),
         "h2agg_kzg_multiopen_device": (i32, [ctxp, u64, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, vp,
                                              C.POINTER(C.c_uint32), C.POINTER(sz)]),
+        "h2agg_kzg_shplonk_begin": (i32, [ctxp, u64, vp, sz, C.c_uint, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, u8p, u8p, vp,
+                                          C.POINTER(vp)]),
+        "h2agg_kzg_shplonk_finish": (i32, [vp, u8p, vp]),
+        "h2agg_kzg_shplonk_destroy": (None, [vp]),
         "h2agg_fr_batch_invert": (i32, [ctxp, vp, sz, vp]),
         "h2agg_fr_batch_invert_device": (i32, [ctxp, vp, sz, vp]),
         "h2agg_fr_grand_product": (i32, [ctxp, vp, vp, C.c_uint, sz, u8p, vp, vp]),
@@ -655,6 +659,35 @@ class H2Agg:
     def kzg_multiopen_device(self, g_handle: int, d_polys_ptr: int, npoly: int, k: int, queries, points: bytes, v: bytes):
         """h2agg_kzg_multiopen_device: as kzg_multiopen over a slab already in device memory"""
         return self._multiopen(self._lib.h2agg_kzg_multiopen_device, g_handle, d_polys_ptr, npoly, k, queries, points, v)
+
+    def kzg_shplonk_begin(self, g_handle: int, polys: bytes, k: int, queries, points: bytes, evals: bytes, y: bytes, v: bytes):
+        """h2agg_kzg_shplonk_begin: round 1 of the Shplonk opening of queries [(poly, point), ...] over a host slab
+        [npoly][2^k], evals = the nq values in query order -> (the canonical affine H1, the object for kzg_shplonk_finish).
+        The object holds device memory of this context: kzg_shplonk_destroy it (before the context closes)."""
+        npoly = self._slab(polys, k)
+        qs, nq, npoints = self._queries(queries, points)
+        _need(evals, 32 * nq, "evals")
+        _need(y, 32, "y")
+        _need(v, 32, "v")
+        h1, obj = C.create_string_buffer(64), C.c_void_p()
+        self._check(self._lib.h2agg_kzg_shplonk_begin(self._ctx, g_handle, self._hostptr(polys), npoly, k, qs, nq, points, npoints,
+                                                      evals, y, v, h1, C.byref(obj)))
+        return h1.raw, obj
+
+    def kzg_shplonk_finish(self, obj, u: bytes) -> bytes:
+        """h2agg_kzg_shplonk_finish: round 2 for the challenge u -> the canonical affine H2; may be called again"""
+        _need(u, 32, "u")
+        if not obj:
+            raise ValueError("obj must be an object of kzg_shplonk_begin that has not been destroyed")
+        h2 = C.create_string_buffer(64)
+        self._check(self._lib.h2agg_kzg_shplonk_finish(obj, u, h2))
+        return h2.raw
+
+    def kzg_shplonk_destroy(self, obj):
+        """h2agg_kzg_shplonk_destroy: frees the object; the handle is cleared, a second call does nothing"""
+        if obj:
+            self._lib.h2agg_kzg_shplonk_destroy(obj)
+            obj.value = None
 
     # ------------------------------------------------------------------ grand products
     def _column(self, data, k: int, u: int, what: str, cols: int = 1):

@@ -36,6 +36,7 @@
 #include "g1_fft_kernels.hpp"
 #include "fr_fft_kernels.hpp"
 #include "poly_kernels.hpp"
+#include "shplonk_kernels.hpp"
 #include "prod_kernels.hpp"
 #include "lookup_kernels.hpp"
 #include "quotient_kernels.hpp"
@@ -812,6 +813,7 @@ int h2agg_synchronize(h2agg_ctx* c) try {
 #include "params.inc"
 #include "fr_fft.inc"
 #include "poly_open.inc"
+#include "shplonk.inc"
 #include "prod.inc"
 #include "lookup.inc"
 #include "quotient.inc"

@@ -63,13 +63,18 @@ void poly_eval_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc
     }
 }
 const uint8_t* poly_top(const h2agg_ctx* c, const FrLevelPlan& plan) { return (const uint8_t*)c->poly_work.p + 32 * plan.off.back(); }
+// the carries into the chunks of the coefficients, [query][plan.cnt[1]], once the levels above are divided; null: one chunk
+const uint8_t* poly_carries(const h2agg_ctx* c, const FrLevelPlan& plan) {
+    return plan.launches() > 1 ? (const uint8_t*)c->poly_work.p + 32 * plan.off[1] : nullptr;
+}
 
 // Queues the down-sweep behind poly_eval_queue of the same plan: the quotients go to d_quot, [query][2^k] (d_quot == d_slab
 // allowed when query q is polynomial q: poly_kernels.hpp says why).  The levels above the coefficients are divided in place.
+// lowest = 1 stops above the coefficients (shplonk.inc: its leaf kernel takes the carries at poly_carries from there).
 void poly_divide_queue(h2agg_ctx* c, const uint8_t* d_slab, const uint32_t* d_desc, const FrLevelPlan& plan,
-                       const std::vector<std::vector<FrPolyPoint>>& tab, uint8_t* d_quot) {
+                       const std::vector<std::vector<FrPolyPoint>>& tab, uint8_t* d_quot, size_t lowest = 0) {
     uint8_t* work = (uint8_t*)c->poly_work.p;
-    for (size_t l = plan.launches(); l-- > 0;) {
+    for (size_t l = plan.launches(); l-- > lowest;) {
         FrPolyArgs a;
         a.src = l == 0 ? d_slab : work + 32 * plan.off[l];
         a.dst = l == 0 ? d_quot : work + 32 * plan.off[l];
@@ -146,35 +151,47 @@ int poly_divide_check(h2agg_ctx* c, unsigned k, const uint8_t* z, ph::HFr* zf) {
     return fr_parse(c, z, zf);
 }
 
-// debug key phases: events on the context's stream around the three phases of one multiopen, for h2agg_last_phases
+// debug key phases: events on the context's stream between the phases of one call, for h2agg_last_phases.  start(), then
+// lap(i) behind the work of phase i (a phase may take several laps: their times add up); report() waits for the last event.
 struct PolyPhases {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<hipEvent_t> ev;
+    std::vector<int> phase;   // of the lap that ends at ev[i + 1]
     bool on = false;
-    explicit PolyPhases(bool want) {
-        on = want;
-        for (int i = 0; on && i < 4; ++i)
-            if (hipEventCreate(&ev[i]) != hipSuccess) {
-                (void)hipGetLastError();
-                ev[i] = nullptr;
-                on = false;
-            }
-    }
+    explicit PolyPhases(bool want) : on(want) {}
     ~PolyPhases() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
-    void mark(h2agg_ctx* c, int i) {
-        if (on && hipEventRecord(ev[i], c->stream) != hipSuccess) on = false;
+    PolyPhases(const PolyPhases&) = delete;
+    PolyPhases& operator=(const PolyPhases&) = delete;
+    bool record(h2agg_ctx* c) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        ev.push_back(e);
+        return hipEventRecord(e, c->stream) == hipSuccess;
     }
-    void report(std::string* line) {
-        static const char* const names[3] = {"combine", "divide", "commit"};
+    void start(h2agg_ctx* c) {
+        if (on) on = record(c);
+    }
+    void lap(h2agg_ctx* c, int i) {
+        if (!on) return;
+        on = record(c);
+        phase.push_back(i);
+    }
+    void report(std::string* line, const char* const* names, int count) {
         line->clear();
-        if (!on || hipEventSynchronize(ev[3]) != hipSuccess) return;
-        for (int i = 0; i < 3; ++i) {
+        if (!on || ev.empty() || hipEventSynchronize(ev.back()) != hipSuccess) return;
+        std::vector<double> total((size_t)count, 0.0);
+        for (size_t i = 0; i < phase.size(); ++i) {
             float ms = 0;
             if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) return;
+            total[(size_t)phase[i]] += ms;
+        }
+        for (int i = 0; i < count; ++i) {
             char buf[48];
-            snprintf(buf, sizeof buf, " %s=%.4f", names[i], ms);
+            snprintf(buf, sizeof buf, " %s=%.4f", names[i], total[(size_t)i]);
             *line += buf;
         }
     }
@@ -216,7 +233,7 @@ int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsig
     TRY(ensure(c, c->poly_jac, 96 * groups));
     HIP_TRY(c, hipMemcpyAsync(c->poly_desc.p, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, c->stream));
     PolyPhases phases(c->dbg_phases != 0);
-    phases.mark(c, 0);
+    phases.start(c);
     FrLincombArgs la;
     hfr_words(ph::mul(v, fr_radix()), la.v);
     la.polys = d_polys;
@@ -226,16 +243,17 @@ int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsig
     la.flags = c->d_flags;
     la.n = (uint32_t)n;
     hipLaunchKernelGGL(k_fr_poly_lincomb, dim3((unsigned)((n + BLOCK - 1) / BLOCK), (unsigned)groups), dim3(BLOCK), 0, c->stream, la);
-    phases.mark(c, 1);
+    phases.lap(c, 0);
     poly_eval_queue(c, la.dst, nullptr, plan, tab);
     poly_divide_queue(c, la.dst, nullptr, plan, tab, la.dst);
-    phases.mark(c, 2);
+    phases.lap(c, 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // `lists` has crossed: pageable memory may still be read until here
     TRY(h2agg_g1_msm_device_batch_async(c, g_handle, c->poly_slab.p, n, groups, c->poly_jac.p));
     TRY(h2agg_g1_batch_to_affine_device(c, (const uint8_t*)c->poly_jac.p, groups, w_aff));   // joins, synchronises, reports the flags
-    phases.mark(c, 3);
-    if (c->dbg_phases) phases.report(&c->last_phases);
+    phases.lap(c, 2);
+    static const char* const names[3] = {"combine", "divide", "commit"};
+    if (c->dbg_phases) phases.report(&c->last_phases, names, 3);
     for (size_t g = 0; g < groups; ++g) group_points[g] = gpoint[g];
     *ngroups = groups;
     return H2AGG_OK;

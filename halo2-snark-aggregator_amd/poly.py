@@ -1,5 +1,6 @@
 """EvaluationDomain's conversions over the engine's Fr transform (h2agg_fr_fft), the two ways to commit to a polynomial, and
-the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen);
+the ways to open one: eval_polynomial, kate_division and the GWC multiopen prover (h2agg_fr_poly_* / h2agg_kzg_multiopen),
+the Shplonk multiopen prover and its verifier's pair (h2agg_kzg_shplonk_begin / _finish; shplonk_final_pair);
 and the grand products of the permutation and lookup arguments (h2agg_fr_batch_invert, h2agg_permutation_product,
 h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr_columns_compress, h2agg_lookup_permute);
 and the quotient polynomial h(X) from a verifying key (h2agg_vk_expressions_eval, h2agg_quotient); and the keys those stages
@@ -103,6 +104,103 @@ def multiopen_prove(eng, g_handle: int, polys: bytes, k: int, queries, points: b
     if [pt for pt, _ in groups] != group_points:
         raise RuntimeError("the library grouped the queries differently from group_queries")
     return [evals[32 * q:32 * q + 32] for q in range(len(queries))], groups, ws
+
+
+# ---------------------------------------------------------------------------------------------- Shplonk
+def shplonk_sets(queries):
+    """[(poly, point), ...] -> [(points, polys), ...], the sets of the Shplonk prover (include/h2agg.h): a polynomial's point
+    set is what its queries name, a repeated pair counting once; polynomials with equal point sets share a set; sets in
+    first-seen order of their first polynomial, `polys` in first-seen order of their first query, `points` in the order the
+    set's first polynomial first names them"""
+    order, named = [], {}
+    for poly, point in queries:
+        poly, point = int(poly), int(point)
+        if poly not in named:
+            named[poly] = []
+            order.append(poly)
+        if point not in named[poly]:
+            named[poly].append(point)
+    sets = []
+    for poly in order:
+        for points, polys in sets:
+            if set(points) == set(named[poly]):
+                polys.append(poly)
+                break
+        else:
+            sets.append((list(named[poly]), [poly]))
+    return sets
+
+
+def shplonk_prove(eng, g_handle: int, polys: bytes, k: int, queries, points: bytes, y: bytes, v: bytes, squeeze_u):
+    """the Shplonk multiopen prover over a slab [npoly][2^k] of coefficients: evaluates the queries, runs round 1, asks
+    squeeze_u(h1) for the challenge u (the caller writes H1 to its transcript there), runs round 2.  -> (evals, h1, h2):
+    evals[q] the 32-byte value of query q, h1 and h2 canonical affine points (64 bytes)"""
+    queries = [(int(p), int(z)) for p, z in queries]
+    evals = eng.fr_poly_eval(polys, k, queries, points)
+    h1, obj = eng.kzg_shplonk_begin(g_handle, polys, k, queries, points, evals, y, v)
+    try:
+        h2 = eng.kzg_shplonk_finish(obj, squeeze_u(h1))
+    finally:
+        eng.kzg_shplonk_destroy(obj)
+    return [evals[32 * q:32 * q + 32] for q in range(len(queries))], h1, h2
+
+
+def _interpolate_at(zs, es, u):
+    """the value at u of the polynomial of degree < len(zs) through (zs[i], es[i]): Lagrange's formula in integers mod r"""
+    acc = 0
+    for i, zi in enumerate(zs):
+        num = den = 1
+        for j, zj in enumerate(zs):
+            if j != i:
+                num = num * (u - zj) % R_MOD
+                den = den * (zi - zj) % R_MOD
+        acc = (acc + es[i] * num * pow(den, R_MOD - 2, R_MOD)) % R_MOD
+    return acc
+
+
+def shplonk_final_pair(eng, commits, queries, points: bytes, evals, y: bytes, v: bytes, u: bytes, h1: bytes, h2: bytes):
+    """the Shplonk verifier's pair (include/h2agg.h): commits[m] the canonical affine commitment of polynomial m (64 bytes),
+    evals[q] the value of query q.  The scalars in Python integers, one g1_msm over {C_m, G, H1, H2}.
+    -> (left, right) as canonical affine points: accepted iff final_pair_check(left, right, s_g2, g2)."""
+    queries = [(int(p), int(z)) for p, z in queries]
+    num = lambda b: int.from_bytes(b, "little")
+    zs = [num(points[at:at + 32]) for at in range(0, len(points), 32)]
+    yi, vi, ui = num(y), num(v), num(u)
+    value = {}
+    for (poly, point), e in zip(queries, evals):
+        value.setdefault((poly, point), num(e))
+    sets = shplonk_sets(queries)
+    named = []
+    for _poly, point in queries:
+        if point not in named:
+            named.append(point)
+
+    def vanishing(pts):
+        out = 1
+        for p in pts:
+            out = out * (ui - zs[p]) % R_MOD
+        return out
+
+    d = [vanishing([p for p in named if p not in pts]) for pts, _polys in sets]
+    if d[0] == 0:
+        raise ValueError("u is a point of another set than the first (d_0 == 0)")
+    d0_inv = pow(d[0], R_MOD - 2, R_MOD)
+    scalar = {}                                # polynomial -> its scalar
+    g_scalar, vpow = 0, 1
+    for (pts, members), di in zip(sets, d):
+        w = vpow * di * d0_inv % R_MOD         # v^i c_i
+        for poly in members:
+            scalar[poly] = w
+            g_scalar = (g_scalar - w * _interpolate_at([zs[p] for p in pts], [value[(poly, p)] for p in pts], ui)) % R_MOD
+            w = w * yi % R_MOD
+        vpow = vpow * vi % R_MOD
+    t = vanishing(named) * d0_inv % R_MOD
+    members = sorted(scalar)
+    gen = (1).to_bytes(32, "little") + (2).to_bytes(32, "little")   # G = g[0] of ParamsKZG: the curve's generator (1, 2)
+    bases = b"".join(bytes(commits[m]) for m in members) + gen + bytes(h1) + bytes(h2)
+    scalars = [scalar[m] for m in members] + [g_scalar, (-t) % R_MOD, ui]
+    right = eng.g1_msm(bases, b"".join(s.to_bytes(32, "little") for s in scalars))
+    return bytes(h2), eng.g1_batch_to_affine(right)
 
 
 # ---------------------------------------------------------------------------------------------- grand products

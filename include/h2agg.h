@@ -467,7 +467,10 @@ int h2agg_verify_proofs(h2agg_ctx* ctx, const h2agg_circuit_proofs* circuits, si
  * " combine=ms divide=ms commit=ms" — the linear combinations, the up- and down-sweep over all groups, and the batch MSM with
  * the conversion to affine (this one includes the host's wait between the two).
  * After an h2agg_quotient* call it is that call's split, also from events on the stream and summed over the cosets:
- * " forward=ms gates=ms permutation=ms lookups=ms inverse=ms". */
+ * " forward=ms gates=ms permutation=ms lookups=ms inverse=ms".
+ * After h2agg_kzg_shplonk_begin / _finish it is that call's split, from events on the stream: " stage=ms numerators=ms divide=ms
+ * commit=ms" (the slab's copy, the N_i, the sweeps and the set division summed over the sets, the MSM with its conversion) /
+ * " combine=ms divide=ms commit=ms". */
 const char* h2agg_last_phases(h2agg_ctx* ctx);
 
 /* ---- multi-GPU exchange -----------------------------------------------------------
@@ -633,6 +636,54 @@ int h2agg_kzg_multiopen(h2agg_ctx* ctx, uint64_t g_handle, const uint8_t* polys,
 int h2agg_kzg_multiopen_device(h2agg_ctx* ctx, uint64_t g_handle, const void* d_polys, size_t npoly, unsigned k,
                                const uint32_t* queries, size_t nq, const uint8_t* points, size_t npoints, const uint8_t v[32],
                                uint8_t* w_aff, uint32_t* group_points, size_t* ngroups);
+
+/* ---- KZG openings, Shplonk: the BDFG20 multiopen prover -------------------------------------------------------------------
+ * Stand for: the prover of poly/kzg/multiopen/shplonk (prover.rs) and construct_intermediate_sets of halo2_proofs — an
+ * unvendored git dependency of the reference: recalled from upstream, not pinned; what the entry points
+ * compute is this definition, and what is pinned is its algebra and the verifier equation at its end.
+ *
+ * Inputs as for h2agg_kzg_multiopen: npoly polynomials of one k <= 24 as a slab [npoly][2^k] in host memory, npoints points, nq
+ * queries {polynomial index, point index}; and evals, nq x 32 bytes, the value of each query as the caller wrote it to its
+ * transcript; challenges y and v, and later u.
+ *   Sets.   A polynomial's point set is the set of point indices its queries name (a repeated pair counts once).  Polynomials
+ *           with equal point sets form set i; sets are numbered in first-seen order of their first polynomial, the polynomials
+ *           p_{i,0}, p_{i,1}, ... inside a set in first-seen order of their first query.  S_i: the set's points; T: the union of
+ *           all named points.  (halo2's own ordering of the sets belongs to construct_intermediate_sets: a caller that needs
+ *           it orders its queries accordingly.)  Points and polynomials that no query names are ignored.
+ *   Round 1 r_{i,j}: the polynomial of degree < |S_i| with r_{i,j}(z) = evals at z in S_i (interpolated on the host).
+ *             N_i(X) = sum_j y^j (p_{i,j}(X) - r_{i,j}(X))
+ *             h(X)   = sum_i v^i N_i(X) / Z_{S_i}(X),      Z_S(X) = prod_{z in S} (X - z)
+ *             H1     = sum_j h[j] g[j]
+ *           Powers ascend, the first term at power 0 (as in the GWC definition above).
+ *   Round 2 With d_i = Z_{T \ S_i}(u), c_i = d_i / d_0 and t = Z_T(u) / d_0:
+ *             L(X)  = sum_i v^i c_i sum_j y^j (p_{i,j}(X) - r_{i,j}(u))  -  t h(X)
+ *             h2(X) = L(X) / (X - u),      H2 = sum_j h2[j] g[j]
+ *   Verifier equation, C_{i,j} the commitment of p_{i,j} and G = g[0]:
+ *             F = sum_i v^i c_i sum_j y^j (C_{i,j} - r_{i,j}(u) G) - t H1;   left = H2;   right = F + u H2
+ *           accepted iff e(left, s_g2) e(right, -g2) = 1: what h2agg_final_pair_check takes.
+ * y, v, u and points equal to 0 are legal, and so is u in S_0.  A zero h or h2 gives the identity, 64 zero bytes.
+ *
+ * h2agg_kzg_shplonk_begin: stages the slab once, runs round 1, writes H1 (canonical affine) to h1_aff and the object to *out;
+ *   synchronous.  The object keeps, in device memory, the slab with h behind it ((npoly + 1) 2^k elements) and one more array of
+ *   2^k; it refers to ctx and g_handle, which must outlive it, and is used from the context's thread.
+ * h2agg_kzg_shplonk_finish: runs round 2 for u, writes H2 to h2_aff; synchronous; may be called again with another u.
+ * h2agg_kzg_shplonk_destroy: frees the object (NULL: nothing).
+ * With the debug key phases, h2agg_last_phases gives " stage=ms numerators=ms divide=ms commit=ms" after begin and
+ * " combine=ms divide=ms commit=ms" after finish, from events on the context's stream.  The key fr_poly_chunk is honoured.
+ * Refusals, the context stays usable after each and begin leaves no object (*out = NULL): those of h2agg_kzg_multiopen (k > 24,
+ *   a null buffer, nq == 0 or nq > 65535, an index out of range, a table shorter than 2^k or an unknown handle:
+ *   H2AGG_ERR_INVALID; a point, a value, y, v or u >= r: H2AGG_ERR_NONCANONICAL; a coefficient >= r of a polynomial some query
+ *   names: H2AGG_ERR_NONCANONICAL through the context's device status, from the call; out of memory: H2AGG_ERR_NOMEM), and, all
+ *   H2AGG_ERR_INVALID: a repeated (polynomial, point) pair with two different values; two named point indices holding equal
+ *   values; a set of more than 32 points; some N_i(z) != 0 for a z in S_i, i.e. a value that is not its polynomial's (the
+ *   message names the query); in finish, d_0 == 0: u is a point of T \ S_0.  A non-zero remainder L(u), which values that
+ *   begin accepted cannot give: H2AGG_ERR_HIP (the library's code for a failure of the device). */
+typedef struct h2agg_shplonk h2agg_shplonk;
+int h2agg_kzg_shplonk_begin(h2agg_ctx* ctx, uint64_t g_handle, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries,
+                            size_t nq, const uint8_t* points, size_t npoints, const uint8_t* evals, const uint8_t y[32],
+                            const uint8_t v[32], uint8_t h1_aff[64], h2agg_shplonk** out);
+int h2agg_kzg_shplonk_finish(h2agg_shplonk* obj, const uint8_t u[32], uint8_t h2_aff[64]);
+void h2agg_kzg_shplonk_destroy(h2agg_shplonk* obj);
 
 /* ---- Grand products: batch inversion, the permutation and lookup Z columns ------------------------------------------------
  * Stand for: ff::BatchInvert, permutation::prover::commit and lookup::prover::commit_product of halo2_proofs — an unvendored
@@ -971,13 +1022,15 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         (combine / divide / commit) and every h2agg_quotient* call's (forward / gates / permutation / lookups /
  *                         inverse; the queued form then waits for its own events) and every h2agg_permutation_sigmas call's
  *                         (stage / sigma / inverse / copy) and every h2agg_witness_check call's (gates / permutation / lookups /
- *                         report), for h2agg_last_phases
+ *                         report) and every h2agg_kzg_shplonk_begin / _finish call's (stage / numerators / divide / commit;
+ *                         combine / divide / commit), for h2agg_last_phases
  *       "fr_fft_local" L  h2agg_fr_fft / _device fuse L radix-2 stages per pass, 1 .. 11 (0 = the default, 10): inputs of 8 to
  *                         1024 elements then run the multi-pass paths
  *       "fr_fft_batch_chunk" B  a batched transform (h2agg_fr_fft_batch, the transforms inside h2agg_quotient) runs in chunks of
  *                         B columns, every pass of a chunk one launch (0 = the default: as many columns as the work array holds)
  *       "fr_poly_chunk" t the KZG opening kernels cut a polynomial into chunks of 2^t coefficients per workgroup, 3 .. 11 (0 = the
- *                         default, 11): inputs of 64 to 1024 coefficients then run the three- and four-level plans
+ *                         default, 11): inputs of 64 to 1024 coefficients then run the three- and four-level plans (the
+ *                         Shplonk prover's sweeps and set division take the same cut)
  *       "fr_scan_chunk" t the grand-product kernels (batch inversion, running product) cut an array into chunks of 2^t elements
  *                         per workgroup, 3 .. 11 (0 = the default, 11): inputs of 64 to 1024 rows then run the three- and
  *                         four-level plans
