@@ -24,7 +24,7 @@ int comb_generate_launch(h2agg_ctx* c, const uint8_t* d_k, size_t n, uint8_t* ou
 // beta * x column of a resident table, made once
 int table_endo(h2agg_ctx* c, Table& t, const uint8_t** out) {
     if (!t.endo_x) {
-        if (hipMalloc((void**)&t.endo_x, 32 * t.n) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(endo table)");
+        TRY(dev_alloc(c, t.endo_x, 32 * t.n, "endo table"));
         hipLaunchKernelGGL(k_bases_endo_x, dim3(grid_for(c, t.n)), dim3(BLOCK), 0, c->stream, (const uint8_t*)t.d, t.n,
                            t.endo_x);
     }
@@ -65,14 +65,13 @@ int comb_msm_run(h2agg_ctx* c, Table& t, const uint8_t* d_scalars, size_t n, siz
         while (nb < n) nb *= 2;
         if (nb > cap_n) nb = cap_n;
         const size_t entries = nb * (size_t)COMB_WINDOWS * COMB_ROW;
-        uint8_t* fresh = nullptr;
-        if (hipMalloc((void**)&fresh, entries * 64) != hipSuccess) {
-            (void)hipGetLastError();
+        DevMem fresh;
+        if (fresh.alloc(entries * 64) != hipSuccess) {
             *done = false;
             return H2AGG_OK;
         }
-        if (t.comb) t.comb_retired.push_back(t.comb);
-        t.comb = fresh;
+        if (t.comb) t.comb_retired.push_back(std::move(t.comb));
+        t.comb = std::move(fresh);
         size_t grid = (entries + SM_GROUPS - 1) / SM_GROUPS;
         const size_t cap = (size_t)c->cu_count * 16;
         if (grid > cap) grid = cap;
@@ -86,6 +85,22 @@ int comb_msm_run(h2agg_ctx* c, Table& t, const uint8_t* d_scalars, size_t n, siz
     return H2AGG_OK;
 }
 
+// A table of n points whose column is allocated and nothing else: what every creating call fills.  A call that returns
+// before table_register leaves it to its destructor, whose hipFree waits for whatever the call had queued.
+int table_new(h2agg_ctx* c, size_t n, Table* t) {
+    t->n = n;
+    return dev_alloc(c, t->d, 64 * n, "base table");
+}
+
+// The finished table of a creating call, behind that call's finish(): into the context, under a new handle.  The word
+// finish() read says whether the call stored an identity base.
+uint64_t table_register(h2agg_ctx* c, Table&& t) {
+    t.no_identity = table_word_clear(c->table_word);
+    const uint64_t h = c->next_handle++;
+    c->tables.emplace(h, std::move(t));
+    return h;
+}
+
 }  // namespace
 
 extern "C" {
@@ -95,27 +110,14 @@ int h2agg_bases_upload(h2agg_ctx* c, const uint8_t* bases, size_t n, uint64_t* h
     TRY(bind(c));
     if (!bases || !handle_out || n == 0) return fail(c, H2AGG_ERR_INVALID, "null buffer or n == 0");
     Table t;
-    t.n = n;
-    if (hipMalloc((void**)&t.d, 64 * n) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(base table)");
-    int rc = ensure(c, c->tmp_bases, 64 * n);
-    if (rc == H2AGG_OK) {
-        hipError_t e = hipMemcpyAsync(c->tmp_bases.p, bases, 64 * n, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) rc = fail(c, H2AGG_ERR_HIP, hipGetErrorString(e));
-    }
-    if (rc == H2AGG_OK) rc = clear_flags(c);
-    if (rc == H2AGG_OK) {
-        hipLaunchKernelGGL(k_bases_to_mont, dim3(grid_for(c, n)), dim3(BLOCK), 0, c->stream,
-                           (const uint8_t*)c->tmp_bases.p, n, t.d, c->d_flags);
-        rc = finish(c);
-    }
-    if (rc != H2AGG_OK) {
-        t.release();
-        return rc;
-    }
-    t.no_identity = table_word_clear(c->table_word);
-    uint64_t h = c->next_handle++;
-    c->tables[h] = t;
-    *handle_out = h;
+    TRY(table_new(c, n, &t));
+    TRY(ensure(c, c->tmp_bases, 64 * n));
+    TRY(stage_in(c, c->tmp_bases, bases, 64 * n));
+    TRY(clear_flags(c));
+    hipLaunchKernelGGL(k_bases_to_mont, dim3(grid_for(c, n)), dim3(BLOCK), 0, c->stream,
+                       (const uint8_t*)c->tmp_bases.p, n, t.d, c->d_flags);
+    TRY(finish(c));
+    *handle_out = table_register(c, std::move(t));
     return H2AGG_OK;
 } API_CATCH
 
@@ -123,29 +125,19 @@ int h2agg_bases_generate(h2agg_ctx* c, const void* d_k, size_t n, uint64_t* hand
     TRY(bind(c));
     if (!d_k || !handle_out || n == 0) return fail(c, H2AGG_ERR_INVALID, "null buffer or n == 0");
     Table t;
-    t.n = n;
-    if (hipMalloc((void**)&t.d, 64 * n) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(base table)");
-    int rc = clear_flags(c);
-    if (rc == H2AGG_OK) {
-        static const bool ladder = knob("H2AGG_SCALAR_MUL") && !strcmp(knob("H2AGG_SCALAR_MUL"), "ladder");
-        if (ladder) {
-            size_t blocks = (n + BLOCK - 1) / BLOCK;
-            if (blocks > 65535 * 16) blocks = 65535 * 16;
-            hipLaunchKernelGGL(k_bases_generate, dim3((unsigned)blocks), dim3(BLOCK), 0, c->stream, (const uint8_t*)d_k, n, t.d,
-                               c->d_flags);
-        } else {
-            rc = comb_generate_launch(c, (const uint8_t*)d_k, n, t.d);
-        }
-        if (rc == H2AGG_OK) rc = finish(c);
+    TRY(table_new(c, n, &t));
+    TRY(clear_flags(c));
+    static const bool ladder = knob("H2AGG_SCALAR_MUL") && !strcmp(knob("H2AGG_SCALAR_MUL"), "ladder");
+    if (ladder) {
+        size_t blocks = (n + BLOCK - 1) / BLOCK;
+        if (blocks > 65535 * 16) blocks = 65535 * 16;
+        hipLaunchKernelGGL(k_bases_generate, dim3((unsigned)blocks), dim3(BLOCK), 0, c->stream, (const uint8_t*)d_k, n, t.d,
+                           c->d_flags);
+    } else {
+        TRY(comb_generate_launch(c, (const uint8_t*)d_k, n, t.d));
     }
-    if (rc != H2AGG_OK) {
-        t.release();
-        return rc;
-    }
-    t.no_identity = table_word_clear(c->table_word);
-    uint64_t h = c->next_handle++;
-    c->tables[h] = t;
-    *handle_out = h;
+    TRY(finish(c));
+    *handle_out = table_register(c, std::move(t));
     return H2AGG_OK;
 } API_CATCH
 
@@ -169,7 +161,6 @@ int h2agg_bases_free(h2agg_ctx* c, uint64_t handle) try {
     TRY(find_table(c, handle, &t));
     TRY(join_tails(c));   // tails and accumulations on the context's other streams (and a deferred tail) may still read the table
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    t->release();
     c->tables.erase(handle);
     return H2AGG_OK;
 } API_CATCH
@@ -203,13 +194,9 @@ int h2agg_bases_precompute(h2agg_ctx* c, uint64_t handle, int window_bits) try {
     }
     TRY(join_tails(c));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (t.pre) {
-        hipFree(t.pre);
-        t.pre = nullptr;
-    }
+    t.pre.reset();
     t.free_combs();
-    if (hipMalloc((void**)&t.pre, (size_t)W * t.n * 64) != hipSuccess)
-        return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(fixed-base levels)");
+    TRY(dev_alloc(c, t.pre, (size_t)W * t.n * 64, "fixed-base levels"));
     HIP_TRY(c, hipMemcpyAsync(t.pre, t.d, t.n * 64, hipMemcpyDeviceToDevice, c->stream));
     for (int w = 1; w < W; ++w)
         hipLaunchKernelGGL(k_bases_shift, dim3(grid_for(c, t.n)), dim3(BLOCK), 0, c->stream,

@@ -139,7 +139,7 @@ int h2agg_profile_enable(h2agg_ctx* c, int enable) try {
     if (enable && !c->prof_events_created) {
         for (int r = 0; r < h2agg_ctx::PROF_RING; ++r)
             for (int s = 0; s < ST_N; ++s)
-                for (int k = 0; k < 2; ++k) HIP_TRY(c, hipEventCreateWithFlags(&c->prof[r].ev[s][k], EV_TIME_FLAGS));
+                for (int k = 0; k < 2; ++k) HIP_TRY(c, c->prof[r].ev[s][k].create(EV_TIME_FLAGS));
         c->prof_events_created = true;
     }
     if (!enable) profile_harvest_all(c);

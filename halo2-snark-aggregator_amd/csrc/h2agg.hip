@@ -30,6 +30,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "hip_owners.hpp"
 #include "scalar_mul_kernels.hpp"
 #include "lp_kernels.hpp"
 #include "seg_msm_kernels.hpp"
@@ -80,17 +81,6 @@ static const bool ev_scope_system = knob("H2AGG_EVENT_SCOPE") && !strcmp(knob("H
 #define EV_SYNC_FLAGS (ev_scope_system ? hipEventDisableTiming : (hipEventDisableTiming | hipEventReleaseToDevice))
 #define EV_TIME_FLAGS (ev_scope_system ? hipEventDefault : hipEventReleaseToDevice)
 
-struct DevBuf {   // a grow-only device buffer (ensure, csrc/host.inc); freed with its owner
-    void* p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    ~DevBuf() {
-        if (p) hipFree(p);
-    }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
 enum Stage {
     ST_PART_COUNT = 0, ST_PART_SCATTER, ST_BUCKET_SORT, ST_ORDER, ST_ACCUM, ST_ACCUM_BIG, ST_REDUCE, ST_WINDOW_SUM,
     ST_FINAL, ST_N
@@ -99,36 +89,28 @@ const char* const STAGE_NAMES[ST_N] = {"msm_part_count", "msm_part_scatter",   "
                                        "msm_order",      "msm_accumulate",     "msm_accumulate_big",
                                        "msm_reduce",     "msm_window_sum",     "msm_final"};
 
-struct Table {
-    uint8_t* d = nullptr;       // Montgomery affine, 64 B / point
-    uint8_t* endo_x = nullptr;  // beta * x, 32 B / point (made on the first GLV MSM over this table)
+struct Table {   // owns its device buffers: they go with it, behind a synchronisation of whatever may still read them
+    DevMem d;        // Montgomery affine, 64 B / point
+    DevMem endo_x;   // beta * x, 32 B / point (made on the first GLV MSM over this table)
     size_t n = 0;
     // the call that wrote the table stored no identity base (flags[1], batch_kernels.hpp): MSMs over it take the bucket
     // accumulation without the per-entry identity test.  false = not known: "may hold one" (msm_lean_variant)
     bool no_identity = false;
     // fixed-base levels (h2agg_bases_precompute): pre[(w * n + i) * 64] = 2^(pre_c * w) * P_i, w < pre_W
-    uint8_t* pre = nullptr;
+    DevMem pre;
     int pre_c = 0, pre_W = 0;
     // comb of the first comb_n bases (k_comb_table_build with bases; made on the first small MSM over a table that has
     // fixed-base levels, i.e. one its owner declared constant): comb[((b * 32 + w) * 255 + d - 1) * 64] = d * 2^(8w) * P_b
-    uint8_t* comb = nullptr;
+    DevMem comb;
     size_t comb_n = 0;
-    std::vector<uint8_t*> comb_retired;   // smaller combs this one replaced: kernels in flight may still read them, so they
-                                          // are freed where the table's other buffers are (behind a synchronisation)
+    std::vector<DevMem> comb_retired;   // smaller combs this one replaced: kernels in flight may still read them, so they
+                                        // are freed where the table's other buffers are (behind a synchronisation)
+    Table() = default;
+    Table(Table&&) = default;
     void free_combs() {
-        if (comb) hipFree(comb);
-        for (uint8_t* p : comb_retired) hipFree(p);
-        comb = nullptr;
+        comb.reset();
         comb_n = 0;
         comb_retired.clear();
-    }
-    // every device buffer of the table; behind a synchronisation of whatever may still read them
-    void release() {
-        if (d) hipFree(d);
-        if (endo_x) hipFree(endo_x);
-        if (pre) hipFree(pre);
-        d = endo_x = pre = nullptr;
-        free_combs();
     }
 };
 struct PreTable {   // what msm_run needs of it
@@ -233,6 +215,29 @@ constexpr int MSM_MAX_SLICES = 16;
 
 struct h2agg_ctx {
     int device = 0;
+    // ---- The handles the context owns (csrc/hip_owners.hpp).  h2agg_destroy synchronises every stream that may hold work and
+    // then deletes the context; members die in reverse order of declaration.  So everything declared BELOW this block goes
+    // first: the base tables, the grow-only buffers and the pinned blocks, and each hipFree among them waits for the device
+    // once more.  Then the events, then the streams, the context's own stream last: memory goes while the streams that
+    // ordered its users still exist, an event goes before the streams it was recorded on.  (h2agg_create's failure path
+    // deletes a context behind nothing but place_streams' probes, in the same order.)
+    static constexpr int TAIL_SLOTS = 3;    // tail streams (see below)
+    static constexpr int PROF_RING = 32;    // per-call event sets of the profile (see below)
+    static constexpr int N_STREAMS = 1 + TAIL_SLOTS + 3 + 4;
+    Stream streams[N_STREAMS];   // in the order h2agg_create makes them: own, tails, accumulation, aux, copy, four spares.
+                                 // The role members below are plain handles into this array (place_streams permutes them)
+    Event ev_aux, ev_aux_go;
+    Event ev_copy[MSM_MAX_SLICES], ev_copy_s[MSM_MAX_SLICES], ev_ready;
+    Event ev_bulk[TAIL_SLOTS], ev_tail[TAIL_SLOTS];
+    Event ev_sortdone, ev_sorted[2], ev_accdone[2];
+    struct ProfSlot {
+        Event ev[ST_N][2];   // made by the first h2agg_profile_enable
+        bool used[ST_N] = {};
+        bool pending = false;
+    };
+    ProfSlot prof[PROF_RING];
+    // ---- end of the owned handles
+
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string err;
@@ -260,15 +265,13 @@ struct h2agg_ctx {
     uint32_t* d_flags = nullptr;      // in `small`: [0] status flags, [1] big_count
     uint8_t* d_res_xyzz = nullptr;    // in `small` + 1024 + 144 * slot of the LAST msm_run (see msm_run)
     uint8_t* d_res_jac = nullptr;     // in `small` + 256
-    uint8_t* h_pinned = nullptr;      // 4 KiB pinned staging for small results / flags
+    PinnedBuf h_pinned;               // pinned staging for small results / flags (its first 4 KiB are used)
 
     // schema-layer scratch (grow-only; the schema API is synchronous, one evaluation is in flight per context):
     // the Fr register file, the uploaded staging block, per-side MSM scalars / Montgomery bases, pinned staging
     DevBuf sch_regs, sch_in, sch_scalars[2], sch_bases[2], sch_endo;
-    uint8_t* h_stage = nullptr;
-    size_t h_stage_cap = 0;
-    uint8_t* h_down = nullptr;        // page-locked landing block of the from-bytes call's downloads (csrc/verify_run.inc)
-    size_t h_down_cap = 0;
+    PinnedBuf h_stage;
+    PinnedBuf h_down;                 // page-locked landing block of the from-bytes call's downloads (csrc/verify_run.inc)
     const void* sch_owner = nullptr;  // the schema whose tape sch_regs reflects
     struct AggPlanCache* agg_plans = nullptr;   // recorded aggregations kept for the next call of the same shape (csrc/verifier.inc)
 
@@ -277,8 +280,6 @@ struct h2agg_ctx {
     hipStream_t spare_streams[4] = {};   // what place_streams() did not give a role (see there)
     // verifier pipeline: point decompression of a circuit's proofs runs here, beside the instance-column MSMs
     hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_aux = nullptr, ev_aux_go = nullptr;
-    hipEvent_t ev_copy[MSM_MAX_SLICES] = {}, ev_copy_s[MSM_MAX_SLICES] = {}, ev_ready = nullptr;
 
     std::map<uint64_t, Table> tables;
     uint64_t next_handle = 1;
@@ -355,13 +356,11 @@ struct h2agg_ctx {
     // TAIL_SLOTS tail streams used round-robin, each with its own buckets / segsum / wsum set: the latency-shaped
     // tails of consecutive MSMs overlap one another as well as the next MSMs' bulk (small MSMs are otherwise
     // bound by one tail chain: ~0.7 ms per MSM at 2^14 points against 0.5 ms of bulk).
-    static constexpr int TAIL_SLOTS = 3;
     // what a tail reads: one independent allocation per slot, so MSMs with DIFFERENT plans (bucket counts, segment
     // counts, window counts) in flight on different slots can never alias one another, whatever their sizes
     DevBuf r2d_ticket[TAIL_SLOTS];
     DevBuf buckets[TAIL_SLOTS], segsum[TAIL_SLOTS], wsum[TAIL_SLOTS];
     hipStream_t tail_streams[TAIL_SLOTS] = {};
-    hipEvent_t ev_bulk[TAIL_SLOTS] = {}, ev_tail[TAIL_SLOTS] = {};
     bool tail_pending[TAIL_SLOTS] = {};
     int parity = 0;   // slot of the next MSM
     // called by msm_run on the stream of the accumulation, behind the sort and in front of the first kernel that reads the
@@ -374,24 +373,15 @@ struct h2agg_ctx {
     // Whoever needs the results first (join_tails) launches it at once.
     MsmTailJob deferred_job;      // valid while tail_deferred (flush_deferred_tail)
     bool tail_deferred = false;
-    hipEvent_t ev_sortdone = nullptr;
     hipStream_t acc_stream = nullptr;
-    hipEvent_t ev_sorted[2] = {}, ev_accdone[2] = {};
     bool accdone_pending[2] = {};
     int sort_par = 0;
 
-    // profiling: a ring of per-call event sets, harvested lazily so that measuring does not serialise
+    // profiling: a ring of per-call event sets (prof[PROF_RING]), harvested lazily so that measuring does not serialise
     // back-to-back asynchronous MSMs
-    static constexpr int PROF_RING = 32;
-    struct ProfSlot {
-        hipEvent_t ev[ST_N][2] = {};
-        bool used[ST_N] = {};
-        bool pending = false;
-    };
     bool profiling = false;
     int prof_only = -1;   // >= 0: only this stage is bracketed (one event pair per MSM instead of nine)
     bool prof_events_created = false;
-    ProfSlot prof[PROF_RING];
     int prof_cur = 0;
     double stage_ms[ST_N] = {};
     uint64_t stage_launches[ST_N] = {};
@@ -640,82 +630,63 @@ int h2agg_create(int device_ordinal, h2agg_ctx** out) try {
     if (device_ordinal < 0 || hipGetDeviceCount(&count) != hipSuccess || device_ordinal >= count)
         return H2AGG_ERR_HIP;  // no CPU mode: a HIP device is required
     if (hipSetDevice(device_ordinal) != hipSuccess) return H2AGG_ERR_HIP;
-    h2agg_ctx* c = new h2agg_ctx();
+    std::unique_ptr<h2agg_ctx> ctx(new h2agg_ctx());   // every failure below is a plain return: the owners release what was made
+    h2agg_ctx* c = ctx.get();
     c->device = device_ordinal;
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) {
-        delete c;
-        return H2AGG_ERR_HIP;
-    }
+    if (hipGetDeviceProperties(&prop, device_ordinal) != hipSuccess) return H2AGG_ERR_HIP;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     char buf[256];
     snprintf(buf, sizeof buf, "h2agg 0.1 %s cu=%d", prop.gcnArchName, c->cu_count);
     c->desc = buf;
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void**)&c->h_pinned, 4096) != hipSuccess || ensure(c, c->small, 4096) != H2AGG_OK) {
-        h2agg_destroy(c);
+    // The streams, in a fixed order: the own stream, the tail streams, the accumulation's, then the auxiliary stream, the copy
+    // stream and four spares.  The last six are made HERE, behind the others, not at their first use: where the runtime places
+    // a stream depends on how many streams the process has made before it (profiles/r03_sweeps.txt section 18: back-to-back
+    // MSMs run at 1.25 or at 1.55 ms per step depending on the number of streams made between the main stream and the tail
+    // streams), and a placement that changes with what else the process did first is not reproducible.
+    // H2AGG_TAIL_PRIO / H2AGG_ACC_PRIO (experiments): -1 = lowest, 1 = highest priority for the tail / accumulation streams
+    static const int tail_prio = knob("H2AGG_TAIL_PRIO") ? atoi(knob("H2AGG_TAIL_PRIO")) : 0;
+    static const int acc_prio = knob("H2AGG_ACC_PRIO") ? atoi(knob("H2AGG_ACC_PRIO")) : 0;
+    int pr_lo = 0, pr_hi = 0;
+    hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);   // lo = least (numerically greatest)
+    const int tail_pr = tail_prio < 0 ? pr_lo : pr_hi, acc_pr = acc_prio < 0 ? pr_lo : pr_hi;
+    Stream* s = c->streams;
+    if (s->create(hipStreamNonBlocking) != hipSuccess || ensure_pinned(c, c->h_pinned, 4096, "result staging") != H2AGG_OK ||
+        ensure(c, c->small, 4096) != H2AGG_OK)
         return H2AGG_ERR_HIP;
+    for (int i = 1; i < h2agg_ctx::N_STREAMS; ++i) {
+        const int* pr = i <= h2agg_ctx::TAIL_SLOTS ? (tail_prio ? &tail_pr : nullptr)
+                                                   : (i == h2agg_ctx::TAIL_SLOTS + 1 && acc_prio ? &acc_pr : nullptr);
+        if (s[i].create(hipStreamNonBlocking, pr) != hipSuccess) return H2AGG_ERR_HIP;
     }
-    c->stream = c->own_stream;
-    for (int k = 0; k < h2agg_ctx::TAIL_SLOTS; ++k) {
-        // H2AGG_TAIL_PRIO (experiment): -1 = lowest, 1 = highest stream priority for the tail streams
-        static const int tail_prio = knob("H2AGG_TAIL_PRIO") ? atoi(knob("H2AGG_TAIL_PRIO")) : 0;
-        int pr_lo = 0, pr_hi = 0;
-        hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);   // lo = least (numerically greatest)
-        if ((tail_prio ? hipStreamCreateWithPriority(&c->tail_streams[k], hipStreamNonBlocking, tail_prio < 0 ? pr_lo : pr_hi)
-                       : hipStreamCreateWithFlags(&c->tail_streams[k], hipStreamNonBlocking)) != hipSuccess) {
-            h2agg_destroy(c);
-            return H2AGG_ERR_HIP;
-        }
-        hipEventCreateWithFlags(&c->ev_bulk[k], EV_SYNC_FLAGS);
-        hipEventCreateWithFlags(&c->ev_tail[k], EV_SYNC_FLAGS);
-    }
-    int apr_lo = 0, apr_hi = 0;
-    hipDeviceGetStreamPriorityRange(&apr_lo, &apr_hi);
-    static const int acc_prio = knob("H2AGG_ACC_PRIO") ? atoi(knob("H2AGG_ACC_PRIO")) : 0;   // experiment: -1 lowest
-    if ((acc_prio ? hipStreamCreateWithPriority(&c->acc_stream, hipStreamNonBlocking, acc_prio < 0 ? apr_lo : apr_hi)
-                  : hipStreamCreateWithFlags(&c->acc_stream, hipStreamNonBlocking)) != hipSuccess) {
-        h2agg_destroy(c);
-        return H2AGG_ERR_HIP;
-    }
-    // The auxiliary and the copy stream are made HERE, in a fixed order behind the others, not at their first use: where the
-    // runtime places a stream depends on how many streams the process has made before it (profiles/r03_sweeps.txt section 18:
-    // back-to-back MSMs run at 1.25 or at 1.55 ms per step depending on the number of streams made between the main stream and
-    // the tail streams), and a placement that changes with what else the process did first is not reproducible.
-    if (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) {
-        h2agg_destroy(c);
-        return H2AGG_ERR_HIP;
-    }
-    for (int k = 0; k < 4; ++k)
-        if (hipStreamCreateWithFlags(&c->spare_streams[k], hipStreamNonBlocking) != hipSuccess) {
-            h2agg_destroy(c);
-            return H2AGG_ERR_HIP;
-        }
-    hipEventCreateWithFlags(&c->ev_aux, hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_aux_go, hipEventDisableTiming);
-    for (int k = 0; k < MSM_MAX_SLICES; ++k) {
-        hipEventCreateWithFlags(&c->ev_copy[k], hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->ev_copy_s[k], hipEventDisableTiming);
-    }
-    hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming);
-    hipEventCreateWithFlags(&c->ev_sortdone, EV_SYNC_FLAGS);
-    for (int q = 0; q < 2; ++q) {
-        hipEventCreateWithFlags(&c->ev_sorted[q], EV_SYNC_FLAGS);
-        hipEventCreateWithFlags(&c->ev_accdone[q], EV_SYNC_FLAGS);
-    }
+    c->stream = c->own_stream = *s++;
+    for (hipStream_t& t : c->tail_streams) t = *s++;
+    c->acc_stream = *s++;
+    c->aux_stream = *s++;
+    c->copy_stream = *s++;
+    for (hipStream_t& t : c->spare_streams) t = *s++;
+    // the events, each with the flags of its use: device-scope ordering between the MSM's streams, plain ordering for the rest
+    bool ok = c->ev_aux.create(hipEventDisableTiming) == hipSuccess && c->ev_aux_go.create(hipEventDisableTiming) == hipSuccess &&
+              c->ev_ready.create(hipEventDisableTiming) == hipSuccess && c->ev_sortdone.create(EV_SYNC_FLAGS) == hipSuccess;
+    for (int k = 0; k < MSM_MAX_SLICES; ++k)
+        ok = ok && c->ev_copy[k].create(hipEventDisableTiming) == hipSuccess && c->ev_copy_s[k].create(hipEventDisableTiming) == hipSuccess;
+    for (int k = 0; k < h2agg_ctx::TAIL_SLOTS; ++k)
+        ok = ok && c->ev_bulk[k].create(EV_SYNC_FLAGS) == hipSuccess && c->ev_tail[k].create(EV_SYNC_FLAGS) == hipSuccess;
+    for (int q = 0; q < 2; ++q)
+        ok = ok && c->ev_sorted[q].create(EV_SYNC_FLAGS) == hipSuccess && c->ev_accdone[q].create(EV_SYNC_FLAGS) == hipSuccess;
+    if (!ok) return H2AGG_ERR_HIP;
     c->d_flags = (uint32_t*)c->small.p;
     c->d_res_xyzz = (uint8_t*)c->small.p + 1024;   // 144 B
     c->d_res_jac = (uint8_t*)c->small.p + 256;   // 96 B
     hipMemset(c->small.p, 0, 4096);
-    if (place_streams(c) != H2AGG_OK) {
-        h2agg_destroy(c);
-        return H2AGG_ERR_HIP;
-    }
-    *out = c;
+    if (place_streams(c) != H2AGG_OK) return H2AGG_ERR_HIP;
+    *out = ctx.release();
     return H2AGG_OK;
 } API_CATCH
 
+// What no destructor can do: the communicator and the recorded plans go, a tail that still waits is launched, and every
+// stream that may hold work is waited for (c->stream may be the caller's).  The owners do the rest, in the order the
+// context's declaration states.
 void h2agg_destroy(h2agg_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
@@ -723,47 +694,9 @@ void h2agg_destroy(h2agg_ctx* c) {
     agg_plans_release(c);
     flush_deferred_tail(c, false);
     if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->acc_stream) hipStreamSynchronize(c->acc_stream);
-    for (int k = 0; k < h2agg_ctx::TAIL_SLOTS; ++k)
-        if (c->tail_streams[k]) hipStreamSynchronize(c->tail_streams[k]);
-    for (auto& kv : c->tables) kv.second.release();
-    if (c->h_pinned) hipHostFree(c->h_pinned);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->h_down) hipHostFree(c->h_down);
-    if (c->copy_stream) {
-        hipStreamSynchronize(c->copy_stream);
-        for (int k = 0; k < MSM_MAX_SLICES; ++k) {
-            if (c->ev_copy[k]) hipEventDestroy(c->ev_copy[k]);
-            if (c->ev_copy_s[k]) hipEventDestroy(c->ev_copy_s[k]);
-        }
-        if (c->ev_ready) hipEventDestroy(c->ev_ready);
-        hipStreamDestroy(c->copy_stream);
-    }
-    if (c->aux_stream) {
-        hipStreamSynchronize(c->aux_stream);
-        if (c->ev_aux) hipEventDestroy(c->ev_aux);
-        if (c->ev_aux_go) hipEventDestroy(c->ev_aux_go);
-        hipStreamDestroy(c->aux_stream);
-    }
-    for (int r = 0; r < h2agg_ctx::PROF_RING; ++r)
-        for (int s = 0; s < ST_N; ++s)
-            for (int k = 0; k < 2; ++k)
-                if (c->prof[r].ev[s][k]) hipEventDestroy(c->prof[r].ev[s][k]);
-    for (int k = 0; k < h2agg_ctx::TAIL_SLOTS; ++k) {
-        if (c->ev_bulk[k]) hipEventDestroy(c->ev_bulk[k]);
-        if (c->ev_tail[k]) hipEventDestroy(c->ev_tail[k]);
-        if (c->tail_streams[k]) hipStreamDestroy(c->tail_streams[k]);
-    }
-    if (c->ev_sortdone) hipEventDestroy(c->ev_sortdone);
-    for (int q = 0; q < 2; ++q) {
-        if (c->ev_sorted[q]) hipEventDestroy(c->ev_sorted[q]);
-        if (c->ev_accdone[q]) hipEventDestroy(c->ev_accdone[q]);
-    }
-    if (c->acc_stream) hipStreamDestroy(c->acc_stream);
-    for (int k = 0; k < 4; ++k)
-        if (c->spare_streams[k]) hipStreamDestroy(c->spare_streams[k]);
-    if (c->own_stream) hipStreamDestroy(c->own_stream);
-    delete c;   // frees every DevBuf
+    for (Stream& s : c->streams)
+        if (s) hipStreamSynchronize(s);
+    delete c;
 }
 
 const char* h2agg_last_error(const h2agg_ctx* c) { return c ? c->err.c_str() : "null context"; }

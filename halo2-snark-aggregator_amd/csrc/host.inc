@@ -1,6 +1,7 @@
 // The host layer every C-ABI entry point stands on (included into h2agg.hip ahead of msm_run.inc and of every family: shares the
-// context internals): the growing-buffer rule, the launch grid of the element-wise kernels, the binding of a call to its
-// context, the look-up of a base table, the staging of a host twin, and the catch blocks behind every extern "C" function.
+// context internals): the growing-buffer rules and the exact-size allocation over the owners of csrc/hip_owners.hpp, the launch
+// grid of the element-wise kernels, the binding of a call to its context, the look-up of a base table, the staging of a host
+// twin, the phase clock of the debug key phases, and the catch blocks behind every extern "C" function.
 // A new family of entry points starts from here (the Fr families: from fr_host.inc on top of it).
 
 namespace {
@@ -28,6 +29,28 @@ int ensure(h2agg_ctx* c, DevBuf& b, size_t bytes) {
         return fail(c, H2AGG_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
     }
     b.cap = want;
+    return H2AGG_OK;
+}
+
+// the same for a page-locked host block: the caller has joined whatever copied through the old one
+int ensure_pinned(h2agg_ctx* c, PinnedBuf& b, size_t bytes, const char* what) {
+    if (bytes <= b.cap) return H2AGG_OK;
+    if (b.p) HIP_TRY(c, hipHostFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    const size_t want = bytes + bytes / 2 + 4096;
+    const hipError_t e = hipHostMalloc((void**)&b.p, want, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return fail(c, H2AGG_ERR_NOMEM, std::string("hipHostMalloc(") + what + "): " + hipGetErrorString(e));
+    }
+    b.cap = want;
+    return H2AGG_OK;
+}
+
+// an allocation of exactly `bytes` (a base table's column, the work memory of one call)
+int dev_alloc(h2agg_ctx* c, DevMem& m, size_t bytes, const char* what) {
+    if (m.alloc(bytes) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, std::string("hipMalloc(") + what + ")");
     return H2AGG_OK;
 }
 
@@ -82,6 +105,50 @@ int fetch_result_jac(h2agg_ctx* c, uint8_t out[96]) {
     memcpy(out, c->h_pinned, 96);
     return H2AGG_OK;
 }
+
+// Debug key phases: the split of one call by events on the context's stream, for h2agg_last_phases.  mark(i): phase i starts
+// here, the phase before it ends; mark(END) behind the last one.  A phase may be entered several times: its laps add up.  A
+// failed create or record switches the clock off for the rest of the call.  Without the key nothing is recorded and the line
+// of the last keyed call stays.
+struct PhaseClock {
+    enum { END = -1 };
+    h2agg_ctx* c;
+    const bool want;
+    bool on;
+    std::vector<std::pair<int, Event>> marks;
+    explicit PhaseClock(h2agg_ctx* c_) : c(c_), want(c_->dbg_phases != 0), on(want) {}
+    void mark(int phase) {
+        if (!on) return;
+        Event e;
+        if (e.create(hipEventDefault) != hipSuccess || hipEventRecord(e, c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            on = false;
+            return;
+        }
+        marks.emplace_back(phase, std::move(e));
+    }
+    // waits for the last event; c->last_phases = " name=%.4f" for each of the `count` phases, or with only_entered for those
+    // among them that were entered and left
+    void report(const char* const* names, int count, bool only_entered = false) {
+        if (!want) return;
+        c->last_phases.clear();
+        if (!on || marks.empty() || hipEventSynchronize(marks.back().second) != hipSuccess) return;
+        std::vector<double> ms((size_t)count, 0.0);
+        std::vector<bool> entered((size_t)count, false);
+        for (size_t i = 0; i + 1 < marks.size(); ++i) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, marks[i].second, marks[i + 1].second) != hipSuccess) return;
+            ms[(size_t)marks[i].first] += t;
+            entered[(size_t)marks[i].first] = true;
+        }
+        for (int i = 0; i < count; ++i) {
+            if (only_entered && !entered[(size_t)i]) continue;
+            char buf[48];
+            snprintf(buf, sizeof buf, " %s=%.4f", names[i], ms[(size_t)i]);
+            c->last_phases += buf;
+        }
+    }
+};
 
 }  // namespace
 

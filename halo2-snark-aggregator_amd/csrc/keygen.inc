@@ -22,38 +22,6 @@ int perm_check_shape(h2agg_ctx* c, size_t m, unsigned k, size_t usable) {
     return H2AGG_OK;
 }
 
-// debug key phases: events on the context's stream around the phases of one h2agg_permutation_sigmas, for h2agg_last_phases
-struct KgPhases {
-    enum { STAGE = 0, SIGMA, INVERSE, COPY, STAGES };
-    hipEvent_t ev[STAGES + 1] = {};
-    int marks = 0;
-    bool on;
-    explicit KgPhases(bool want) : on(want) {}
-    ~KgPhases() {
-        for (int i = 0; i < marks; ++i) (void)hipEventDestroy(ev[i]);
-    }
-    void mark(h2agg_ctx* c) {   // the next phase starts here; the last mark is the end
-        if (!on || marks > STAGES) return;
-        if (hipEventCreate(&ev[marks]) != hipSuccess) {
-            (void)hipGetLastError();
-            on = false;
-            return;
-        }
-        if (hipEventRecord(ev[marks++], c->stream) != hipSuccess) on = false;
-    }
-    void report(std::string* line) {   // the phases between the marks made so far
-        static const char* const names[STAGES] = {"stage", "sigma", "inverse", "copy"};
-        if (!on || marks < 2 || hipEventSynchronize(ev[marks - 1]) != hipSuccess) return;
-        for (int i = 0; i + 1 < marks; ++i) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) return;
-            char buf[48];
-            snprintf(buf, sizeof buf, " %s=%.4f", names[i], ms);
-            *line += buf;
-        }
-    }
-};
-
 // Queues the sigma columns of the mapping at d_mapping ([m * n] pairs) into the slab d_out[m][n], canonical: the bitmap's
 // clear, the delta table, k_perm_sigma.  Nothing synchronises unless a workspace has to grow.  An invalid mapping raises
 // FLAG_BAD_MAPPING in the context's device status.
@@ -142,29 +110,32 @@ int h2agg_permutation_sigmas(h2agg_ctx* c, const uint32_t* mapping, size_t m, un
     if (both) TRY(ensure(c, c->in_b, slab));
     uint8_t* d_lag = (uint8_t*)c->out.p;
     uint8_t* d_coeff = both ? (uint8_t*)c->in_b.p : d_lag;   // only the coefficients are wanted: the transform runs in place
-    KgPhases phases(c->dbg_phases != 0);
-    phases.mark(c);
+    // debug key phases: only the phases that finished are named (a refused mapping has no copy)
+    enum { STAGE, SIGMA, INVERSE, COPY, PHASES };
+    static const char* const names[PHASES] = {"stage", "sigma", "inverse", "copy"};
+    PhaseClock phases(c);
+    phases.mark(STAGE);
     TRY(stage_in(c, c->in_a, (const uint8_t*)mapping, 8 * cells));
     TRY(clear_flags(c));
-    phases.mark(c);
+    phases.mark(SIGMA);
     TRY(perm_sigma_queue(c, c->in_a.p, m, k, usable, d, d_lag));
-    phases.mark(c);
+    phases.mark(INVERSE);
     if (sigma_coeff) {
         const FrFftSeg seg = {d_lag, m};
         TRY(fr_fft_queue_batch(c, &seg, 1, m, k, 1, nullptr, d_coeff));
     }
-    phases.mark(c);
+    phases.mark(COPY);
     // the verdict first: on a refusal nothing is written to the outputs
     const int rc = finish(c);
     if (rc != H2AGG_OK) {
-        if (c->dbg_phases) phases.report(&c->last_phases);
+        phases.report(names, PHASES, true);
         return rc;
     }
     if (sigma_lagrange) HIP_TRY(c, hipMemcpyAsync(sigma_lagrange, d_lag, slab, hipMemcpyDeviceToHost, c->stream));
     if (sigma_coeff) HIP_TRY(c, hipMemcpyAsync(sigma_coeff, d_coeff, slab, hipMemcpyDeviceToHost, c->stream));
-    phases.mark(c);
+    phases.mark(PhaseClock::END);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->dbg_phases) phases.report(&c->last_phases);
+    phases.report(names, PHASES, true);
     return H2AGG_OK;
 } API_CATCH
 

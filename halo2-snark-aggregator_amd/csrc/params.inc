@@ -6,20 +6,6 @@
 
 namespace {
 
-struct DevTmp {   // a device allocation that lives for one call
-    void* p = nullptr;
-    ~DevTmp() {
-        if (p) hipFree(p);   // (synchronises: nothing queued still uses it afterwards)
-    }
-    int alloc(h2agg_ctx* c, size_t bytes, const char* what) {
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
-            p = nullptr;
-            return fail(c, H2AGG_ERR_NOMEM, std::string("hipMalloc(") + what + ")");
-        }
-        return H2AGG_OK;
-    }
-};
-
 constexpr size_t FRP_CST_BYTES = 32 * (FRP_TABLE + 2);
 
 // d_out[i] = A * base^i + B, i < n (canonical), queued on the context's stream; d_cst: FRP_CST_BYTES of device memory
@@ -42,9 +28,9 @@ int fr_affine_powers_launch(h2agg_ctx* c, ph::HFr base, const ph::HFr& A, const 
 int fft_ensure_twiddles(h2agg_ctx* c, unsigned k, int inv) {
     if (c->fft_tw_k[inv] >= (int)k) return H2AGG_OK;
     const size_t cnt = (size_t)1 << (k - 1);
-    DevTmp pw, cst;
-    TRY(pw.alloc(c, 32 * cnt, "twiddles"));
-    TRY(cst.alloc(c, FRP_CST_BYTES, "twiddle constants"));
+    DevMem pw, cst;   // for this call (their hipFree synchronises: nothing queued still uses them afterwards)
+    TRY(dev_alloc(c, pw, 32 * cnt, "twiddles"));
+    TRY(dev_alloc(c, cst, FRP_CST_BYTES, "twiddle constants"));
     c->fft_tw_k[inv] = -1;
     TRY(ensure(c, c->fft_tw[inv], 4 * (size_t)FFT_REC_WORDS * cnt));
     const ph::HFr w = fft_omega(k);
@@ -67,8 +53,8 @@ int fft_ensure_scale(h2agg_ctx* c) {
         hfr_bytes(cur, sc + 32 * k);
         cur = ph::mul(cur, half);
     }
-    DevTmp d;
-    TRY(d.alloc(c, sizeof sc, "scale"));
+    DevMem d;
+    TRY(dev_alloc(c, d, sizeof sc, "scale"));
     TRY(ensure(c, c->fft_scale, 4 * (size_t)FFT_REC_WORDS * cnt));
     HIP_TRY(c, hipMemcpy(d.p, sc, sizeof sc, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_fft_twiddle_digits, dim3(1), dim3(BLOCK), 0, c->stream, (const uint8_t*)d.p, cnt, (uint32_t*)c->fft_scale.p,
@@ -81,9 +67,9 @@ int fft_ensure_scale(h2agg_ctx* c) {
 // the transform of the first 2^k points of d_in (Montgomery affine) into d_out (Montgomery affine); synchronous
 int fft_run(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, uint8_t* d_out) {
     const size_t n = (size_t)1 << k;
-    DevTmp work, jac;
-    TRY(work.alloc(c, XYZZ_BYTES * n, "FFT work array"));
-    TRY(jac.alloc(c, 96 * n, "FFT result"));
+    DevMem work, jac;
+    TRY(dev_alloc(c, work, XYZZ_BYTES * n, "FFT work array"));
+    TRY(dev_alloc(c, jac, 96 * n, "FFT result"));
     TRY(clear_flags(c));
     if (k) TRY(fft_ensure_twiddles(c, k, inv));
     const uint32_t* scale = nullptr;
@@ -114,10 +100,10 @@ int fft_run(h2agg_ctx* c, const uint8_t* d_in, unsigned k, int inv, uint8_t* d_o
 // g = s^i * G and / or g_lagrange = L_i(s) * G, i < 2^k, into d_g / d_gl (either may be null); synchronous
 int params_setup_run(h2agg_ctx* c, unsigned k, const ph::HFr& s, const ph::HFr& s_n, uint8_t* d_g, uint8_t* d_gl) {
     const size_t n = (size_t)1 << k;
-    DevTmp scal, invs, cst;
-    TRY(scal.alloc(c, 32 * n, "setup scalars"));
-    TRY(cst.alloc(c, 2 * FRP_CST_BYTES, "setup constants"));
-    if (d_gl) TRY(invs.alloc(c, 32 * n, "setup scalars"));
+    DevMem scal, invs, cst;
+    TRY(dev_alloc(c, scal, 32 * n, "setup scalars"));
+    TRY(dev_alloc(c, cst, 2 * FRP_CST_BYTES, "setup constants"));
+    if (d_gl) TRY(dev_alloc(c, invs, 32 * n, "setup scalars"));
     TRY(clear_flags(c));
     if (d_g) {
         TRY(fr_affine_powers_launch(c, s, ph::one(), ph::zero(), n, (uint8_t*)cst.p, (uint8_t*)scal.p));
@@ -150,17 +136,9 @@ int h2agg_bases_fft(h2agg_ctx* c, uint64_t in_handle, unsigned k, int inverse, u
     const size_t n = (size_t)1 << k;
     if (n > in->n) return fail(c, H2AGG_ERR_INVALID, "the table has fewer than 2^k points");
     Table t;
-    t.n = n;
-    if (hipMalloc((void**)&t.d, 64 * n) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(base table)");
-    const int rc = fft_run(c, in->d, k, inverse ? 1 : 0, t.d);
-    if (rc != H2AGG_OK) {
-        hipFree(t.d);
-        return rc;
-    }
-    t.no_identity = table_word_clear(c->table_word);
-    const uint64_t h = c->next_handle++;
-    c->tables[h] = t;
-    *out_handle = h;
+    TRY(table_new(c, n, &t));
+    TRY(fft_run(c, in->d, k, inverse ? 1 : 0, t.d));
+    *out_handle = table_register(c, std::move(t));
     return H2AGG_OK;
 } API_CATCH
 
@@ -179,29 +157,12 @@ int h2agg_params_setup(h2agg_ctx* c, unsigned k, const uint8_t s[32], uint64_t* 
         return fail(c, H2AGG_ERR_INVALID, "setup: s^n == 1 (halo2: (s - w^i).invert().unwrap() panics)");
     const size_t n = (size_t)1 << k;
     Table tg, tl;
-    tg.n = tl.n = n;
-    if (g_handle_out && hipMalloc((void**)&tg.d, 64 * n) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(base table)");
-    if (g_lagrange_handle_out && hipMalloc((void**)&tl.d, 64 * n) != hipSuccess) {
-        if (tg.d) hipFree(tg.d);
-        return fail(c, H2AGG_ERR_NOMEM, "hipMalloc(base table)");
-    }
-    const int rc = (tg.d || tl.d) ? params_setup_run(c, k, sm, s_n, tg.d, tl.d) : H2AGG_OK;
-    if (rc != H2AGG_OK) {
-        if (tg.d) hipFree(tg.d);
-        if (tl.d) hipFree(tl.d);
-        return rc;
-    }
-    tg.no_identity = tl.no_identity = table_word_clear(c->table_word);   // (one word for the two tables of the call)
-    if (tg.d) {
-        const uint64_t h = c->next_handle++;
-        c->tables[h] = tg;
-        *g_handle_out = h;
-    }
-    if (tl.d) {
-        const uint64_t h = c->next_handle++;
-        c->tables[h] = tl;
-        *g_lagrange_handle_out = h;
-    }
+    if (g_handle_out) TRY(table_new(c, n, &tg));
+    if (g_lagrange_handle_out) TRY(table_new(c, n, &tl));
+    if (tg.d || tl.d) TRY(params_setup_run(c, k, sm, s_n, tg.d, tl.d));
+    // (one word for the two tables of the call: table_register reads it for each)
+    if (tg.d) *g_handle_out = table_register(c, std::move(tg));
+    if (tl.d) *g_lagrange_handle_out = table_register(c, std::move(tl));
     return H2AGG_OK;
 } API_CATCH
 

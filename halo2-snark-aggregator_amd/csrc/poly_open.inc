@@ -151,52 +151,6 @@ int poly_divide_check(h2agg_ctx* c, unsigned k, const uint8_t* z, ph::HFr* zf) {
     return fr_parse(c, z, zf);
 }
 
-// debug key phases: events on the context's stream between the phases of one call, for h2agg_last_phases.  start(), then
-// lap(i) behind the work of phase i (a phase may take several laps: their times add up); report() waits for the last event.
-struct PolyPhases {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;   // of the lap that ends at ev[i + 1]
-    bool on = false;
-    explicit PolyPhases(bool want) : on(want) {}
-    ~PolyPhases() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    PolyPhases(const PolyPhases&) = delete;
-    PolyPhases& operator=(const PolyPhases&) = delete;
-    bool record(h2agg_ctx* c) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        ev.push_back(e);
-        return hipEventRecord(e, c->stream) == hipSuccess;
-    }
-    void start(h2agg_ctx* c) {
-        if (on) on = record(c);
-    }
-    void lap(h2agg_ctx* c, int i) {
-        if (!on) return;
-        on = record(c);
-        phase.push_back(i);
-    }
-    void report(std::string* line, const char* const* names, int count) {
-        line->clear();
-        if (!on || ev.empty() || hipEventSynchronize(ev.back()) != hipSuccess) return;
-        std::vector<double> total((size_t)count, 0.0);
-        for (size_t i = 0; i < phase.size(); ++i) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) != hipSuccess) return;
-            total[(size_t)phase[i]] += ms;
-        }
-        for (int i = 0; i < count; ++i) {
-            char buf[48];
-            snprintf(buf, sizeof buf, " %s=%.4f", names[i], total[(size_t)i]);
-            *line += buf;
-        }
-    }
-};
-
 int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsigned k, const uint32_t* queries, size_t nq,
                   const std::vector<ph::HFr>& pts, const ph::HFr& v, uint8_t* w_aff, uint32_t* group_points, size_t* ngroups) {
     const size_t n = (size_t)1 << k;
@@ -232,8 +186,9 @@ int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsig
     TRY(ensure(c, c->poly_slab, 32 * n * groups));
     TRY(ensure(c, c->poly_jac, 96 * groups));
     HIP_TRY(c, hipMemcpyAsync(c->poly_desc.p, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, c->stream));
-    PolyPhases phases(c->dbg_phases != 0);
-    phases.start(c);
+    enum { COMBINE, DIVIDE, COMMIT };
+    PhaseClock phases(c);
+    phases.mark(COMBINE);
     FrLincombArgs la;
     hfr_words(ph::mul(v, fr_radix()), la.v);
     la.polys = d_polys;
@@ -243,17 +198,17 @@ int multiopen_run(h2agg_ctx* c, uint64_t g_handle, const uint8_t* d_polys, unsig
     la.flags = c->d_flags;
     la.n = (uint32_t)n;
     hipLaunchKernelGGL(k_fr_poly_lincomb, dim3((unsigned)((n + BLOCK - 1) / BLOCK), (unsigned)groups), dim3(BLOCK), 0, c->stream, la);
-    phases.lap(c, 0);
+    phases.mark(DIVIDE);
     poly_eval_queue(c, la.dst, nullptr, plan, tab);
     poly_divide_queue(c, la.dst, nullptr, plan, tab, la.dst);
-    phases.lap(c, 1);
+    phases.mark(COMMIT);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // `lists` has crossed: pageable memory may still be read until here
     TRY(h2agg_g1_msm_device_batch_async(c, g_handle, c->poly_slab.p, n, groups, c->poly_jac.p));
     TRY(h2agg_g1_batch_to_affine_device(c, (const uint8_t*)c->poly_jac.p, groups, w_aff));   // joins, synchronises, reports the flags
-    phases.lap(c, 2);
+    phases.mark(PhaseClock::END);
     static const char* const names[3] = {"combine", "divide", "commit"};
-    if (c->dbg_phases) phases.report(&c->last_phases, names, 3);
+    phases.report(names, 3);
     for (size_t g = 0; g < groups; ++g) group_points[g] = gpoint[g];
     *ngroups = groups;
     return H2AGG_OK;

@@ -234,43 +234,6 @@ struct QtSlabs {
     const uint8_t *advice, *fixed, *instance, *sigma, *perm_z, *lookup_z, *lookup_ap, *lookup_sp;
 };
 
-// debug key phases: the call's split by events on the context's stream, for h2agg_last_phases
-struct QtPhases {
-    enum { FORWARD = 0, GATES, PERMUTATION, LOOKUPS, INVERSE, STAGES };
-    std::vector<std::pair<int, hipEvent_t>> marks;
-    bool on;
-    explicit QtPhases(bool want) : on(want) {}
-    ~QtPhases() {
-        for (auto& m : marks) (void)hipEventDestroy(m.second);
-    }
-    void mark(h2agg_ctx* c, int stage) {   // `stage` starts here; STAGES: the end
-        if (!on) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess || hipEventRecord(ev, c->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            on = false;
-            return;
-        }
-        marks.emplace_back(stage, ev);
-    }
-    void report(std::string* line) {
-        static const char* const names[STAGES] = {"forward", "gates", "permutation", "lookups", "inverse"};
-        line->clear();
-        if (!on || marks.empty() || hipEventSynchronize(marks.back().second) != hipSuccess) return;
-        double ms[STAGES] = {0, 0, 0, 0, 0};
-        for (size_t i = 0; i + 1 < marks.size(); ++i) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, marks[i].second, marks[i + 1].second) != hipSuccess) return;
-            ms[marks[i].first] += t;
-        }
-        for (int s = 0; s < STAGES; ++s) {
-            char buf[48];
-            snprintf(buf, sizeof buf, " %s=%.4f", names[s], ms[s]);
-            *line += buf;
-        }
-    }
-};
-
 int qt_check(h2agg_ctx* c, const h2agg_vk* vk, const QtSlabs& s, const uint8_t* challenges, const uint8_t* theta, const uint8_t* beta,
              const uint8_t* gamma, const uint8_t* y, const uint8_t* delta, const void* h, QtLayout* l, QtScalars* sc) {
     if (!vk) return fail(c, H2AGG_ERR_INVALID, "null verifying key");
@@ -338,7 +301,8 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     uint8_t* ltab = w + 32 * l.ltab;
     uint8_t* ext = w + 32 * l.ext;
     uint32_t* d_prog = (uint32_t*)c->qt_prog.p;
-    QtPhases phases(c->dbg_phases != 0);
+    enum { FORWARD, GATES, PERMUTATION, LOOKUPS, INVERSE, PHASES };   // of h2agg_last_phases (debug key phases)
+    PhaseClock phases(c);
     // ---- once per call: the programs, the permutation columns' places, w^i, the coefficients of l_0 / l_last / l_blind
     for (size_t p = 0; p < progs.size(); ++p) {
         qe_put_queue(c, progs[p].code.data(), progs[p].code.size(), d_prog + prog_at[p]);
@@ -351,7 +315,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         qe_put_queue(c, cols.data(), cols.size(), d_prog + cols_at);
         fr_table_launch(c, fft_omega(k), k, (uint8_t*)c->qt_tab.p);
     }
-    phases.mark(c, QtPhases::FORWARD);
+    phases.mark(FORWARD);
     const uint32_t u = (uint32_t)n - vk.blinding_factors - 1u;
     hipLaunchKernelGGL(k_qe_lagrange_rows, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, lcoef, (uint32_t)n, u);
     {
@@ -365,7 +329,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     const dim3 rows((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
     ph::HFr s = zeta;
     for (uint32_t cs = 0; cs < cosets; ++cs, s = ph::mul(s, w_ext)) {
-        if (cs) phases.mark(c, QtPhases::FORWARD);
+        if (cs) phases.mark(FORWARD);
         TRY(fr_fft_queue_batch(c, src, FR_FFT_SEGS, l.polys, k, 0, &s, cos));
         QeCoset q;
         q.cos = cos;
@@ -374,13 +338,13 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         q.n = (uint32_t)n;
         q.l0 = l.l0;
         const uint8_t* acc_in = nullptr;
-        phases.mark(c, QtPhases::GATES);
+        phases.mark(GATES);
         if (progs[0].m) {
             qe_eval_queue(c, progs[0], d_prog + prog_at[0], false, k, cos, cos + l.fixed0 * col, cos + l.instance0 * col, &sc.y, nullptr,
                           false, acc);
             acc_in = acc;
         }
-        phases.mark(c, QtPhases::PERMUTATION);
+        phases.mark(PERMUTATION);
         if (l.sets) {
             QePermArgs a;
             a.q = q;
@@ -402,7 +366,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
             hipLaunchKernelGGL(k_qe_permutation, rows, block, 0, c->stream, a);
             acc_in = acc;
         }
-        phases.mark(c, QtPhases::LOOKUPS);
+        phases.mark(LOOKUPS);
         for (uint32_t j = 0; j < l.L; ++j) {
             for (int t = 0; t < 2; ++t)
                 qe_eval_queue(c, progs[1 + 2 * j + t], d_prog + prog_at[1 + 2 * j + t], false, k, cos, cos + l.fixed0 * col,
@@ -425,12 +389,13 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         hfr_words(ph::mul(ph::inv(ph::sub(hfr_pow(s, n), ph::one())), fr_radix()), inv.w);
         hipLaunchKernelGGL(k_qe_store_extended, rows, block, 0, c->stream, (const uint8_t*)acc, inv, (uint32_t)n, (uint32_t)l.e, cs, ext);
     }
-    phases.mark(c, QtPhases::INVERSE);
+    phases.mark(INVERSE);
     TRY(fr_fft_queue(c, ext, K, 1, &zeta, ext));
     HIP_TRY(c, hipMemcpyAsync(d_h, ext, col * (vk.degree - 1), hipMemcpyDeviceToDevice, c->stream));
-    phases.mark(c, QtPhases::STAGES);
+    phases.mark(PhaseClock::END);
     HIP_TRY(c, hipGetLastError());
-    if (c->dbg_phases) phases.report(&c->last_phases);   // (waits for the last event: with the key set the queued form is not asynchronous)
+    static const char* const names[PHASES] = {"forward", "gates", "permutation", "lookups", "inverse"};
+    phases.report(names, PHASES);   // (waits for the last event: with the key set the queued form is not asynchronous)
     return H2AGG_OK;
 }
 

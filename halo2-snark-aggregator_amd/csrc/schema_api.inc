@@ -66,18 +66,6 @@ int eval_lists(h2agg_schema* sc, uint32_t node, EvalLists& L) {
     return H2AGG_OK;
 }
 
-int ensure_stage(h2agg_ctx* c, size_t bytes) {
-    if (bytes <= c->h_stage_cap) return H2AGG_OK;
-    if (c->h_stage) HIP_TRY(c, hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->h_stage_cap = 0;
-    const size_t want = bytes + bytes / 2 + 4096;
-    hipError_t e = hipHostMalloc((void**)&c->h_stage, want, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    c->h_stage_cap = want;
-    return H2AGG_OK;
-}
-
 // The tape's part of a staging block and of the launches behind it: every caller packs what the device needs into ONE pinned
 // block (256-byte aligned regions; the tape's four first, the caller's own behind them), uploads it with ONE copy, then runs the
 // tape.
@@ -198,7 +186,7 @@ int eval_launch_sides(h2agg_schema* sc, EvalLists* L, int nsides, const uint8_t*
         }
     }
     const size_t total = off;
-    TRY(ensure_stage(c, total));
+    TRY(ensure_pinned(c, c->h_stage, total, "staging block"));
     TRY(ensure(c, c->sch_in, total));
     if (need_tape) TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
     uint8_t* h = c->h_stage;
@@ -472,7 +460,7 @@ int evaluate_multiopen_many(h2agg_schema* sc, const std::vector<std::pair<uint32
     const size_t off_seg = off;     off = stage_align(off + (nsides + 1) * 4);
     const size_t off_pseg = off;    off = stage_align(off + (nsides + 1) * 4);
     const size_t total = off;
-    TRY(ensure_stage(c, total));
+    TRY(ensure_pinned(c, c->h_stage, total, "staging block"));
     TRY(ensure(c, c->sch_in, total));
     TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
     TRY(ensure(c, c->sch_scalars[0], M * 32 + 32));
@@ -648,7 +636,7 @@ int h2agg_fr_tape_eval(h2agg_ctx* c, const uint8_t* consts, size_t nconst, const
     size_t off = 0;
     const TapeOffsets to = tape_layout(off, ct, (uint32_t)nconst);
     const size_t off_idx = off, total = stage_align(off + nout * 4);
-    TRY(ensure_stage(c, total));
+    TRY(ensure_pinned(c, c->h_stage, total, "staging block"));
     TRY(ensure(c, c->sch_in, total));
     TRY(ensure(c, c->sch_regs, (size_t)nreg * REG_WORDS * 4 + 64));
     TRY(ensure(c, c->sch_scalars[0], nout * 32));

@@ -221,19 +221,20 @@ int shplonk_begin_run(h2agg_ctx* c, h2agg_shplonk* o, const uint8_t* polys, cons
     TRY(ensure(c, o->num, bytes));
     TRY(ensure(c, o->lists, 4 * blob.w.size()));
     TRY(ensure(c, c->poly_work, 32 * poly_plan(c, o->k, most_points).total));
-    PolyPhases phases(c->dbg_phases != 0);
-    phases.start(c);
+    enum { STAGE, NUMERATORS, DIVIDE, COMMIT };
+    PhaseClock phases(c);
+    phases.mark(STAGE);
     TRY(stage_in(c, o->slab, polys, bytes * o->npoly));
     TRY(stage_in(c, o->lists, (const uint8_t*)blob.w.data(), 4 * blob.w.size()));
     TRY(clear_flags(c));
-    phases.lap(c, 0);
     const uint32_t* d_lists = (const uint32_t*)o->lists.p;
     ph::HFr vi = ph::one();
     for (size_t i = 0; i < o->sets.size(); ++i) {
         const ShplonkSet& s = o->sets[i];
         const size_t m = s.points.size();
+        phases.mark(NUMERATORS);
         shplonk_wsum_launch(c, o, at[i].idx, at[i].w, at[i].ncorr, s.polys.size());
-        phases.lap(c, 1);
+        phases.mark(DIVIDE);
         const FrLevelPlan plan = poly_plan(c, o->k, m);
         std::vector<ph::HFr> z(m);
         for (size_t q = 0; q < m; ++q) z[q] = o->pts[s.points[q]];
@@ -262,18 +263,18 @@ int shplonk_begin_run(h2agg_ctx* c, h2agg_shplonk* o, const uint8_t* polys, cons
             a.accumulate = i > 0 || q0 > 0;   // the first launch of the call writes h
             hipLaunchKernelGGL(k_fr_shplonk_leaf, dim3(a.chunks), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
         }
-        phases.lap(c, 2);
         vi = ph::mul(vi, o->v);
     }
+    phases.mark(COMMIT);   // (with the read-back of the divisions' remainders)
     HIP_TRY(c, hipGetLastError());
     std::vector<uint8_t> top(32 * tops);
     TRY(stage_out(c, top.data(), (const uint8_t*)o->lists.p + 4 * top_at, 32 * tops));   // synchronises: `blob` has crossed
     for (uint8_t b : top)
         if (b) return shplonk_name_mismatch(c, o, queries, nq, evals);
     TRY(shplonk_commit(c, o, o->h(), h1_aff));
-    phases.lap(c, 3);
+    phases.mark(PhaseClock::END);
     static const char* const names[4] = {"stage", "numerators", "divide", "commit"};
-    if (c->dbg_phases) phases.report(&c->last_phases, names, 4);
+    phases.report(names, 4);
     return H2AGG_OK;
 }
 
@@ -315,23 +316,24 @@ int shplonk_finish_run(h2agg_ctx* c, h2agg_shplonk* o, const ph::HFr& u, uint8_t
     blob.put_mont(w_at + 8 * term, ph::sub(ph::zero(), ph::mul(zt, d0_inv)));
     blob.put(ncorr_at, ph::sub(ph::zero(), constant));
     TRY(ensure(c, o->lists, 4 * blob.w.size()));
-    PolyPhases phases(c->dbg_phases != 0);
+    enum { COMBINE, DIVIDE, COMMIT };
+    PhaseClock phases(c);
     TRY(stage_in(c, o->lists, (const uint8_t*)blob.w.data(), 4 * blob.w.size()));
     TRY(clear_flags(c));
-    phases.start(c);
+    phases.mark(COMBINE);
     shplonk_wsum_launch(c, o, idx_at, w_at, ncorr_at, nterms);
-    phases.lap(c, 0);
+    phases.mark(DIVIDE);
     uint8_t* d_rem = (uint8_t*)o->lists.p + 4 * rem_at;
     TRY(poly_divide_queue_one(c, (const uint8_t*)o->num.p, o->k, u, (uint8_t*)o->num.p, d_rem));
-    phases.lap(c, 1);
+    phases.mark(COMMIT);
     uint8_t rem[32];
     TRY(stage_out(c, rem, d_rem, 32));   // synchronises: `blob` has crossed
     for (uint8_t b : rem)
         if (b) return fail(c, H2AGG_ERR_HIP, "shplonk: internal: L(u) != 0 for values that begin accepted");
     TRY(shplonk_commit(c, o, o->num.p, h2_aff));
-    phases.lap(c, 2);
+    phases.mark(PhaseClock::END);
     static const char* const names[3] = {"combine", "divide", "commit"};
-    if (c->dbg_phases) phases.report(&c->last_phases, names, 3);
+    phases.report(names, 3);
     return H2AGG_OK;
 }
 

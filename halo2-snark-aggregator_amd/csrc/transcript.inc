@@ -453,7 +453,7 @@ void transcript_elements_launch(h2agg_ctx* c, const TrLayout& L, const TrBlock& 
 }
 // Early half of a transcript batch, on `st` (an auxiliary stream): stage + upload the layout and the proof bytes, decompress
 // every proof point and lay out everything that does not need the external points.  The staging block is written at
-// c->h_stage + stage_off (the caller has sized it with ensure_stage and keeps other data elsewhere in it).
+// c->h_stage + stage_off (the caller has sized it with ensure_pinned and keeps other data elsewhere in it).
 int transcript_begin(h2agg_ctx* c, const TrLayout& L, const TrBlock& b, const uint8_t* const* proofs, size_t nproofs,
                      const uint8_t* consts, hipStream_t st, size_t stage_off) {
     TRY(ensure(c, c->tr_in, b.total));
@@ -475,7 +475,7 @@ int transcript_run(h2agg_ctx* c, const TrLayout& L, const uint8_t* proofs, size_
                    uint8_t* host_chal = nullptr, uint32_t* host_flags = nullptr, std::vector<uint8_t>* host_elems = nullptr) {
     const TrBlock b = transcript_block(L, nproofs);
     const size_t nsq = b.nsq, elem_stride = b.elem_stride, hdr = b.hdr, hdr2 = b.hdr2, hdr3 = b.hdr3, total = b.total;
-    TRY(ensure_stage(c, total));
+    TRY(ensure_pinned(c, c->h_stage, total, "staging block"));
     TRY(ensure(c, c->tr_in, total));
     TRY(ensure(c, c->tr_points, nproofs * (size_t)(L.npoints ? L.npoints : 1) * 64));
     TRY(ensure(c, c->tr_elems, nproofs * elem_stride));
@@ -693,7 +693,7 @@ int h2agg_hash_transcript_read_batch(h2agg_ctx* c, int kind, const uint8_t* proo
     }
     TRY(clear_flags(c));
     const TrBlock b = transcript_block(L, nproofs);
-    TRY(ensure_stage(c, b.total));
+    TRY(ensure_pinned(c, c->h_stage, b.total, "staging block"));
     TRY(hash_transcript_begin(c, L, b, nullptr, proofs, nproofs, consts, c->stream));
     if (next) hash_stream_launch(c, L, b, nproofs, d_ext, c->stream, 2);
     const bool host = hash_backend(c, nproofs) == 2;

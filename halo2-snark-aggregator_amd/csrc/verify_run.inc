@@ -315,7 +315,7 @@ struct AggState {
         bool on = false;
         size_t ci = 0, off_points = 0, off_inst = 0;
     } late;                           // split download: circuit `ci`'s points / instance commitments are still on their way
-                                      // into c->h_down at these offsets (valid until the next call's ensure_down)
+                                      // into c->h_down at these offsets (valid until the next call grows the block)
     uint8_t lambda[32] = {0};         // the aggregation challenge
     std::string sig;                  // the call's shape (agg_signature)
     AggPlan fresh;                    // the recording of this call, when no kept one fits
@@ -485,7 +485,7 @@ int agg_instance_commitments(const AggCall& call, h2agg_ctx* c, AggState& st, si
     // latency) and everything else that depends on the proof bytes only run BESIDE the instance-column MSMs; only the
     // instance commitments' own two elements per proof wait for those (k_transcript_elements `which` = 1 / 2).
     const size_t inst_off = (h.tb.total + 255) & ~(size_t)255;
-    TRY(ensure_stage(c, inst_off + h.total_vals * 32 + 32));
+    TRY(ensure_pinned(c, c->h_stage, inst_off + h.total_vals * 32 + 32, "staging block"));
     trace.mark("entry");
     HIP_TRY(c, hipEventRecord(c->ev_aux_go, c->stream));                 // (the previous users of tr_* are behind us)
     HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_aux_go, 0));
@@ -526,18 +526,6 @@ int agg_instance_commitments(const AggCall& call, h2agg_ctx* c, AggState& st, si
     return H2AGG_OK;
 }
 
-// the context's page-locked landing block of the split download, grown on demand
-int ensure_down(h2agg_ctx* c, size_t bytes) {
-    if (bytes <= c->h_down_cap) return H2AGG_OK;
-    if (c->h_down) HIP_TRY(c, hipHostFree(c->h_down));
-    c->h_down = nullptr;
-    c->h_down_cap = 0;
-    const size_t want = bytes + bytes / 2 + 4096;
-    if (hipHostMalloc((void**)&c->h_down, want, hipHostMallocDefault) != hipSuccess) return fail(c, H2AGG_ERR_NOMEM, "hipHostMalloc(download block)");
-    c->h_down_cap = want;
-    return H2AGG_OK;
-}
-
 // ShaRead: no square roots and no sponge — the on-curve checks and the message streams are done; the chains run now (device
 // or host threads, csrc/transcript.inc hash_backend) and this circuit's challenges are complete when its turn ends
 int agg_hashed_transcripts(h2agg_ctx* c, AggState& st, const h2agg_circuit_proofs& cp, CircuitHost& h) {
@@ -564,7 +552,7 @@ int agg_split_download(h2agg_ctx* c, AggState& st, const h2agg_circuit_proofs& c
     const size_t ncol = cp.vk->num_instance;
     const size_t nb_el = cp.nproofs * h.tb.elem_stride, nb_pt = h.points.size(), nb_in = ncol ? cp.nproofs * ncol * 64 : 0;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    TRY(ensure_down(c, al(nb_el) + al(nb_pt) + al(nb_in) + 256));
+    TRY(ensure_pinned(c, c->h_down, al(nb_el) + al(nb_pt) + al(nb_in) + 256, "download block"));
     st.late.on = true;
     st.late.ci = ci;
     st.late.off_points = al(nb_el);

@@ -67,43 +67,6 @@ WcLayout wc_layout(const h2agg_vk& vk, unsigned what, size_t max_rows) {
     return l;
 }
 
-// debug key phases: the call's split by events on the context's stream, for h2agg_last_phases
-struct WcPhases {
-    enum { GATES = 0, PERMUTATION, LOOKUPS, REPORT, STAGES };
-    std::vector<std::pair<int, hipEvent_t>> marks;
-    bool on;
-    explicit WcPhases(bool want) : on(want) {}
-    ~WcPhases() {
-        for (auto& m : marks) (void)hipEventDestroy(m.second);
-    }
-    void mark(h2agg_ctx* c, int stage) {   // `stage` starts here; STAGES: the end
-        if (!on) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess || hipEventRecord(ev, c->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            on = false;
-            return;
-        }
-        marks.emplace_back(stage, ev);
-    }
-    void report(std::string* line) {
-        static const char* const names[STAGES] = {"gates", "permutation", "lookups", "report"};
-        line->clear();
-        if (!on || marks.empty() || hipEventSynchronize(marks.back().second) != hipSuccess) return;
-        double ms[STAGES] = {0, 0, 0, 0};
-        for (size_t i = 0; i + 1 < marks.size(); ++i) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, marks[i].second, marks[i + 1].second) != hipSuccess) return;
-            ms[marks[i].first] += t;
-        }
-        for (int s = 0; s < STAGES; ++s) {
-            char buf[48];
-            snprintf(buf, sizeof buf, " %s=%.4f", names[s], ms[s]);
-            *line += buf;
-        }
-    }
-};
-
 // everything a call needs that does not depend on where the buffers live: the compiled programs and the parsed scalars
 struct WcCall {
     WcLayout l;
@@ -201,7 +164,8 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
     uint8_t* w = (uint8_t*)c->wc_work.p;
     uint32_t* d_prog = (uint32_t*)c->qt_prog.p;
     uint32_t* zflags = (uint32_t*)(w + l.zflags);
-    WcPhases phases(c->dbg_phases != 0);
+    enum { GATES, PERMUTATION, LOOKUPS, REPORT, PHASES };   // of h2agg_last_phases (debug key phases)
+    PhaseClock phases(c);
     // ---- the report of a constraint nobody checks: 0 failing rows, no first row, no rows
     HIP_TRY(c, hipMemsetAsync(w + l.counts, 0, l.first_rows - l.counts, c->stream));
     HIP_TRY(c, hipMemsetAsync(w + l.first_rows, 0xFF, l.total_at - l.first_rows, c->stream));
@@ -225,7 +189,7 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
         qe_put_queue(c, cols.data(), cols.size(), d_prog + cols_at);
     }
     // ---- gates: the interpreter with the zero test as its ending, a chunk of polynomials per launch
-    phases.mark(c, WcPhases::GATES);
+    phases.mark(GATES);
     uint32_t c0 = 0;
     for (size_t p = 0; p < call.gate_progs.size(); ++p) {
         const QeProgram& prog = call.gate_progs[p];
@@ -244,13 +208,13 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
         a.zwords = l.zwords;
         a.u = l.u;
         hipLaunchKernelGGL(k_qe_eval<true>, dim3((n + QE_THREADS - 1) / QE_THREADS), dim3(QE_THREADS), 0, c->stream, a);
-        phases.mark(c, WcPhases::REPORT);
+        phases.mark(REPORT);
         wc_report_queue(c, l, w, c0, prog.m);
-        phases.mark(c, WcPhases::GATES);
+        phases.mark(GATES);
         c0 += prog.m;
     }
     // ---- permutation: a chunk of columns per launch
-    phases.mark(c, WcPhases::PERMUTATION);
+    phases.mark(PERMUTATION);
     if (call.permutation)
         for (size_t g0 = 0; g0 < l.P; g0 += l.chunk) {
             const uint32_t lines = (uint32_t)std::min<size_t>(l.chunk, l.P - g0);
@@ -267,12 +231,12 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
             a.g0 = (uint32_t)g0;
             a.zwords = l.zwords;
             hipLaunchKernelGGL(k_wc_permutation, dim3((n + BLOCK - 1) / BLOCK, lines), dim3(BLOCK), 0, c->stream, a);
-            phases.mark(c, WcPhases::REPORT);
+            phases.mark(REPORT);
             wc_report_queue(c, l, w, (uint32_t)(l.G + g0), lines);
-            phases.mark(c, WcPhases::PERMUTATION);
+            phases.mark(PERMUTATION);
         }
     // ---- lookups: the two theta-folds, the sort of the table's usable rows, a search per input row
-    phases.mark(c, WcPhases::LOOKUPS);
+    phases.mark(LOOKUPS);
     if (call.lookups)
         for (size_t j = 0; j < l.L; ++j) {
             uint8_t* fold[2] = {w + l.fold_a, w + l.fold_s};
@@ -291,16 +255,17 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
             a.n = n;
             a.u = l.u;
             hipLaunchKernelGGL(k_wc_lookup, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, a);
-            phases.mark(c, WcPhases::REPORT);
+            phases.mark(REPORT);
             wc_report_queue(c, l, w, (uint32_t)(l.G + l.P + j), 1);
-            phases.mark(c, WcPhases::LOOKUPS);
+            phases.mark(LOOKUPS);
         }
-    phases.mark(c, WcPhases::REPORT);
+    phases.mark(REPORT);
     hipLaunchKernelGGL(k_wc_total, dim3(1), dim3(WC_WAVE), 0, c->stream, (const uint32_t*)(w + l.counts), (uint32_t)l.C,
                        (uint32_t*)(w + l.total_at));
-    phases.mark(c, WcPhases::STAGES);
+    phases.mark(PhaseClock::END);
     HIP_TRY(c, hipGetLastError());
-    if (c->dbg_phases) phases.report(&c->last_phases);   // (waits for the last event)
+    static const char* const names[PHASES] = {"gates", "permutation", "lookups", "report"};
+    phases.report(names, PHASES);   // (waits for the last event)
     return H2AGG_OK;
 }
 
