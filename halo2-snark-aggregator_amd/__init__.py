@@ -121,6 +121,9 @@ def load_library():
         "h2agg_schema_batch_multi_open": (i32, [C.c_void_p, C.c_char_p, sz, C.POINTER(C.c_int32), u8p,
                                                 C.POINTER(C.c_uint32), sz, u8p, u8p, u8p,
                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "h2agg_schema_shplonk_multi_open": (i32, [C.c_void_p, C.c_char_p, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), u8p,
+                                                  C.POINTER(C.c_uint32), u8p, u8p, u8p, u8p, u8p,
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "h2agg_schema_eval": (i32, [C.c_void_p, C.c_uint32, vp, C.POINTER(i32), vp]),
         "h2agg_evaluate_multiopen_proof": (i32, [C.c_void_p, C.c_uint32, C.c_uint32, vp, vp]),
         "h2agg_evaluate_multiopen_prepare": (i32, [C.c_void_p, C.c_uint32, C.c_uint32]),
@@ -135,6 +138,7 @@ def load_library():
         "h2agg_transcript_read_batch": (i32, [ctxp, u8p, sz, sz, C.c_char_p, sz, u8p, sz, u8p, sz, vp, vp]),
         "h2agg_vk_create": (i32, [ctxp, u8p, sz, C.POINTER(C.c_void_p)]),
         "h2agg_vk_set_transcript": (i32, [C.c_void_p, i32]),
+        "h2agg_vk_set_multiopen": (i32, [C.c_void_p, i32]),
         "h2agg_hash_transcript_read_batch": (i32, [ctxp, i32, u8p, sz, sz, C.c_char_p, sz, u8p, sz, u8p, sz, vp, vp]),
         "h2agg_hash_transcript_read_batch_host": (i32, [i32, u8p, sz, sz, C.c_char_p, sz, u8p, sz, u8p, sz, vp, vp, i32]),
         "h2agg_hash_digest_host": (i32, [i32, u8p, sz, vp]),
@@ -1338,6 +1342,30 @@ class SchemaBuilder:
         self.eng._check(self._lib.h2agg_schema_batch_multi_open(self._s, key.encode(), nq, rot, points, qn,
                                                                 len(w) // 64, w, v, u, C.byref(wx), C.byref(wg)))
         return EvaluationQuerySchema(self, wx.value), EvaluationQuerySchema(self, wg.value)
+
+    def shplonk_multi_open(self, key: str, poly_ids: Sequence[int], rotations: Sequence[int], points: bytes, query_nodes,
+                           h1: bytes, h2: bytes, y: bytes, v: bytes, u: bytes):
+        """the Shplonk verifier of include/h2agg.h (h2agg_schema_shplonk_multi_open) in the C++ host layer -> (left, right)
+        schema nodes for evaluate_multiopen_proof: left = commit(H2), right = F + u H2."""
+        nq = len(rotations)
+        _need(points, 32 * nq, "points")
+        _need(h1, 64, "h1")
+        _need(h2, 64, "h2")
+        _need(y, 32, "y")
+        _need(v, 32, "v")
+        _need(u, 32, "u")
+        if len(query_nodes) != nq or len(poly_ids) != nq:
+            raise ValueError("one polynomial id and one query node per rotation")
+        ids = poly_ids if isinstance(poly_ids, C.Array) else (C.c_uint32 * max(nq, 1))(*poly_ids)
+        rot = rotations if isinstance(rotations, C.Array) else (C.c_int32 * max(nq, 1))(*rotations)
+        if isinstance(query_nodes, C.Array):
+            qn = query_nodes
+        else:
+            qn = (C.c_uint32 * max(nq, 1))(*[q.node if isinstance(q, EvaluationQuerySchema) else int(q) for q in query_nodes])
+        left, right = C.c_uint32(), C.c_uint32()
+        self.eng._check(self._lib.h2agg_schema_shplonk_multi_open(self._s, key.encode(), nq, ids, rot, points, qn, h1, h2, y, v, u,
+                                                                  C.byref(left), C.byref(right)))
+        return EvaluationQuerySchema(self, left.value), EvaluationQuerySchema(self, right.value)
 
     def evaluate_multiopen_proof(self, w_x: "EvaluationQuerySchema", w_g: "EvaluationQuerySchema"):
         """verify.rs:705-731 -> (left_aff, right_aff, names)"""

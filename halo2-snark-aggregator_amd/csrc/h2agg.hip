@@ -59,6 +59,7 @@
 #include "poseidon_sponge_host.hpp"
 #include "poseidon_ifma_host.hpp"
 #include "poseidon_kernels.hpp"
+#include "schema_shplonk.hpp"   // (behind schema.hpp, which poseidon_kernels.hpp brings in)
 #include "hash_transcript_host.hpp"
 #include "hash_transcript_kernels.hpp"
 

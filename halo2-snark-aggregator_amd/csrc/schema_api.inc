@@ -365,6 +365,17 @@ int h2agg_schema_batch_multi_open(h2agg_schema* sc, const char* key, size_t nq, 
         return fail(sc->ctx, H2AGG_ERR_INVALID, sc->s.err);
     return H2AGG_OK;
 } API_CATCH
+int h2agg_schema_shplonk_multi_open(h2agg_schema* sc, const char* key, size_t nq, const uint32_t* poly_ids, const int32_t* rotations,
+                                    const uint8_t* points, const uint32_t* query_nodes, const uint8_t h1[64], const uint8_t h2[64],
+                                    const uint8_t y[32], const uint8_t v[32], const uint8_t u[32], uint32_t* left_out,
+                                    uint32_t* right_out) try {
+    if (!sc) return H2AGG_ERR_INVALID;
+    if (!key || !poly_ids || !rotations || !points || !query_nodes || !h1 || !h2 || !y || !v || !u || !left_out || !right_out || nq == 0)
+        return fail(sc->ctx, H2AGG_ERR_INVALID, "null buffer or no queries");
+    if (!shplonk_multi_open(sc->s, key, nq, poly_ids, rotations, points, query_nodes, h1, h2, y, v, u, *left_out, *right_out))
+        return fail(sc->ctx, H2AGG_ERR_INVALID, sc->s.err);
+    return H2AGG_OK;
+} API_CATCH
 int h2agg_schema_estimate(h2agg_schema* sc, uint32_t node, size_t* out) try {
     if (!sc || !out) return H2AGG_ERR_INVALID;
     if (!sc->s.valid(node)) return fail(sc->ctx, H2AGG_ERR_INVALID, "unknown schema node");

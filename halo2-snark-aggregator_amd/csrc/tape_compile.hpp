@@ -140,6 +140,9 @@ struct CompiledTape {
     bool lds = false;                // run by k_tape_run_lds; otherwise k_tape_load_consts + k_tape_run
 };
 // ops: resolved (dst / a / b are final register numbers; registers 0 .. nconst - 1 are the constants, op k writes nconst + k).
+// EVERY operation is kept and run, read or not: a TAPE_INV has a side effect (FLAG_DIV_ZERO on a zero operand) that callers
+// record on purpose without reading the inverse (schema_shplonk.hpp: rotations with equal points).  A pass that drops unread
+// operations must keep the inversions.
 // want_lds: take the LDS register file if the tape's live values fit (a tape without operations never does).
 // false: an operand is not defined before its use.
 inline bool compile_tape(const std::vector<TapeOp>& ops, uint32_t nconst, bool want_lds, CompiledTape& out) {

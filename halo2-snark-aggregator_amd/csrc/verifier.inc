@@ -41,6 +41,7 @@ struct h2agg_vk {
     std::vector<uint8_t> fixed_commitments, perm_commitments;   // 64 B each
     uint8_t vk_scalar[32] = {0};
     int transcript_kind = H2AGG_TRANSCRIPT_KIND_POSEIDON;   // how the key's proofs are written (h2agg_vk_set_transcript)
+    int multiopen_kind = H2AGG_MULTIOPEN_GWC;               // ... and opened (h2agg_vk_set_multiopen)
     typedef std::vector<uint8_t> Expr;   // postfix bytecode
     std::vector<std::vector<Expr>> gates;
     struct Lookup {
@@ -228,6 +229,7 @@ struct ProofRegs {
     };
     std::vector<Lk> lookups;
     uint32_t theta = 0, beta = 0, gamma = 0, y = 0, x = 0, v = 0, u = 0;
+    uint32_t y_open = 0;   // Shplonk: the challenge squeezed before v (the y of include/h2agg.h's Shplonk section)
 };
 
 // Evaluable::chip_evaluate (expression.rs:19-113) as a stack machine over tape registers
@@ -272,7 +274,8 @@ uint32_t eval_expr(Rec& R, const h2agg_vk::Expr& e, const ProofRegs& P, uint32_t
     return st.back();
 }
 
-// the transcript script of one proof (build_params' reading order, verify.rs:342-571), n_w W points at the end
+// the transcript script of one proof (build_params' reading order, verify.rs:342-571), n_w W points at the end; a Shplonk
+// key's proofs end in y, v, H1, u, H2 instead (n_w is not read)
 std::string proof_script(const h2agg_vk& vk, size_t n_w) {
     std::string s = "C";                                                       // init_transcript :57-75
     s.append(vk.num_instance, 'X');                                            // squeeze_instance_commitment :77-97
@@ -294,6 +297,10 @@ std::string proof_script(const h2agg_vk& vk, size_t n_w) {
     const size_t n_evals = vk.instance_q.size() + vk.advice_q.size() + vk.fixed_q.size() + 1 + vk.perm_commitments.size() / 64 +
                            (vk.n_sets ? 3 * (size_t)vk.n_sets - 1 : 0) + 5 * vk.lookups.size();
     s.append(n_evals, 'S');
+    if (vk.multiopen_kind == H2AGG_MULTIOPEN_SHPLONK) {
+        s += "QQPQPQ";                                                         // y, v, H1, u, H2, the per-proof squeeze
+        return s;
+    }
     s += 'Q';                                                                  // v
     s.append(n_w, 'P');                                                        // `while let Ok(p) = self.load_point()`
     s += 'Q';                                                                  // u
@@ -308,9 +315,14 @@ size_t script_fixed_bytes(const h2agg_vk& vk) {   // proof bytes other than the 
     for (char ch : s) n += ch == 'P' ? proof_point_bytes(vk) : ch == 'S' ? 32 : 0;
     return n;
 }
-// does a proof of `plen` bytes fit the key?  The W points are whatever is left (verify.rs:487-490).
+// does a proof of `plen` bytes fit the key?  The W points are whatever is left (verify.rs:487-490); a Shplonk proof ends in
+// exactly two points, H1 and H2, which its script holds already.
 bool proof_len_fits(const h2agg_vk& vk, size_t plen, size_t* n_w) {
     const size_t fixed = script_fixed_bytes(vk), pt = proof_point_bytes(vk);
+    if (vk.multiopen_kind == H2AGG_MULTIOPEN_SHPLONK) {
+        if (n_w) *n_w = 0;
+        return plen == fixed;
+    }
     if (plen % 32 != 0 || plen < fixed || (plen - fixed) % pt != 0) return false;
     if (n_w) *n_w = (plen - fixed) / pt;
     return true;
@@ -452,6 +464,14 @@ int h2agg_vk_set_transcript(h2agg_vk* vk, int kind) {
     return H2AGG_OK;
 }
 
+int h2agg_vk_set_multiopen(h2agg_vk* vk, int kind) {
+    if (!vk) return H2AGG_ERR_INVALID;
+    if (kind != H2AGG_MULTIOPEN_GWC && kind != H2AGG_MULTIOPEN_SHPLONK)
+        return fail(vk->ctx, H2AGG_ERR_INVALID, "unknown multiopen kind (H2AGG_MULTIOPEN_*)");
+    vk->multiopen_kind = kind;
+    return H2AGG_OK;
+}
+
 }  // extern "C"
 
 // ---- recorded aggregations ------------------------------------------------------------------------------------------
@@ -513,7 +533,9 @@ struct Query {
     int32_t rotation;
     uint32_t point_reg;
     uint32_t node;
+    uint32_t poly;   // which polynomial is opened: the interned key of the query's commitment (Shplonk groups by it)
 };
+constexpr uint32_t POLY_VANISHING = 0xffffffffu;   // the vanishing query's polynomial
 
 // where each advice column's commitment stands among a proof's points: the script reads them phase by phase (verify.rs:360-377)
 std::vector<uint32_t> advice_point_order(const h2agg_vk& vk) {
@@ -607,7 +629,7 @@ int build_queries(h2agg_ctx* c, Schema& S, const h2agg_vk& vk, const std::string
     auto evq = [&](int32_t rot, const std::string& name, uint32_t point, const uint8_t* commitment, uint32_t eval_reg) {
         const uint32_t cn = S.add_commitment(name.c_str(), commitment);
         const uint32_t en = S.add_leaf_reg(SchemaNode::EVAL, eval_reg);
-        out.push_back(Query{rot, point, S.add_binary(SchemaNode::ADD, cn, en)});
+        out.push_back(Query{rot, point, S.add_binary(SchemaNode::ADD, cn, en), S.nodes[cn].key});
     };
     S.grow_nodes(8 * (vk.instance_q.size() + vk.advice_q.size() + vk.fixed_q.size() + 16 + 5 * vk.lookups.size() + 3 * vk.n_sets));
     // proof point order (script): advice (by phase) | lookups permuted (2 each) | permutation products | lookup products |
@@ -659,7 +681,8 @@ int build_queries(h2agg_ctx* c, Schema& S, const h2agg_vk& vk, const std::string
             const uint32_t cq = S.add_commitment((key + "_h_commitment" + std::to_string(i)).c_str(), PT(pt_h + (vk.quotient_deg - 1 - i)));
             h = i == 0 ? cq : S.add_binary(SchemaNode::ADD, S.add_binary(SchemaNode::MUL, S.add_leaf_reg(SchemaNode::SCALAR, xn), h), cq);
         }
-        out.push_back(Query{0, x, S.add_binary(SchemaNode::ADD, h, S.add_leaf_reg(SchemaNode::SCALAR, expected_h_eval))});
+        // (the vanishing query opens the h pieces folded with x^n: a polynomial of its own, under an id no interned key has)
+        out.push_back(Query{0, x, S.add_binary(SchemaNode::ADD, h, S.add_leaf_reg(SchemaNode::SCALAR, expected_h_eval)), POLY_VANISHING});
         evq(0, key + "_random_commitment", x, PT(pt_random), P.random_eval);
     }
     (void)c;

@@ -336,6 +336,10 @@ int agg_check_call(h2agg_ctx* c, const AggCall& call) {
     if (call.pairing_ok) *call.pairing_ok = 0;
     memset(call.left_aff, 0, 64);
     memset(call.right_aff, 0, 64);
+    if (call.shard)   // before the point of commitment: no exchange is entered (include/h2agg.h: out of scope for now)
+        for (size_t ci = 0; ci < call.ncircuits; ++ci)
+            if (call.circuits[ci].vk && call.circuits[ci].vk->multiopen_kind != H2AGG_MULTIOPEN_GWC)
+                return fail(c, H2AGG_ERR_INVALID, "the sharded aggregation does not take Shplonk keys yet: aggregate them with h2agg_verify_aggregation(_ex)");
     if (!call.each)   // the reference never folds ShaRead proofs under an aggregation transcript (include/h2agg.h)
         for (size_t ci = 0; ci < call.ncircuits; ++ci)
             if (call.circuits[ci].vk && call.circuits[ci].vk->transcript_kind != H2AGG_TRANSCRIPT_KIND_POSEIDON)
@@ -663,7 +667,8 @@ std::string agg_signature(const AggCall& call, const AggState& st) {
     for (size_t ci = 0; ci < call.ncircuits; ++ci) {
         const h2agg_circuit_proofs& cp = call.circuits[ci];
         char buf[96];
-        snprintf(buf, sizeof buf, "%llu:%zu:%zu:", (unsigned long long)cp.vk->uid, cp.nproofs, cp.nproofs ? cp.transcript_lens[0] : (size_t)0);
+        snprintf(buf, sizeof buf, "%llu:%d:%zu:%zu:", (unsigned long long)cp.vk->uid, cp.vk->multiopen_kind, cp.nproofs,
+                 cp.nproofs ? cp.transcript_lens[0] : (size_t)0);   // (the kind: a key may be switched between two calls)
         sig += buf;
         sig += cp.name;
         sig += ';';
@@ -746,6 +751,7 @@ void read_proof_regs(Schema& S, const h2agg_vk& vk, const CircuitHost& h, size_t
     P.gamma = next_chal();
     P.y = next_chal();
     P.x = next_chal();
+    if (vk.multiopen_kind == H2AGG_MULTIOPEN_SHPLONK) P.y_open = next_chal();
     P.v = next_chal();
     P.u = next_chal();
     for (size_t q = 0; q < vk.instance_q.size(); ++q) P.instance_evals.push_back(next_scalar());
@@ -793,15 +799,21 @@ int agg_record(const AggCall& call, h2agg_ctx* c, AggState& st) {
             std::vector<Query> qs;
             TRY(build_queries(c, S, vk, key, P, h.inst_aff.data() + 64 * vk.num_instance * i, pts, qs));
             std::vector<int32_t> rot(qs.size());
-            std::vector<uint32_t> preg(qs.size()), qnode(qs.size());
+            std::vector<uint32_t> preg(qs.size()), qnode(qs.size()), poly(qs.size());
             for (size_t q = 0; q < qs.size(); ++q) {
                 rot[q] = qs[q].rotation;
                 preg[q] = qs[q].point_reg;
                 qnode[q] = qs[q].node;
+                poly[q] = qs[q].poly;
             }
-            const uint8_t* w = pts + 64 * (h.npoints - h.n_w);
+            const bool shplonk = vk.multiopen_kind == H2AGG_MULTIOPEN_SHPLONK;   // its H1, H2: the proof's last two points
+            const uint8_t* w = pts + 64 * (h.npoints - (shplonk ? 2 : h.n_w));
             uint32_t w_x = 0, w_g = 0;
-            if (!S.batch_multi_open_regs(key.c_str(), qs.size(), rot.data(), preg.data(), qnode.data(), h.n_w, w, P.v, P.u, w_x, w_g)) {
+            const bool ok = shplonk ? shplonk_multi_open_regs(S, key.c_str(), qs.size(), poly.data(), rot.data(), preg.data(), qnode.data(), w,
+                                                              w + 64, P.y_open, P.v, P.u, w_x, w_g)
+                                    : S.batch_multi_open_regs(key.c_str(), qs.size(), rot.data(), preg.data(), qnode.data(), h.n_w, w, P.v,
+                                                              P.u, w_x, w_g);
+            if (!ok) {
                 if (!call.each) return fail(c, H2AGG_ERR_INVALID, S.err);
                 call.each_status[h.first_proof + i] = H2AGG_ERR_INVALID;   // (this proof only: the others go on)
                 continue;

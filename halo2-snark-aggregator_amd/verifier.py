@@ -16,6 +16,7 @@ from typing import Any, List, Optional, Sequence, Tuple
 _KIND = {"advice": 0, "fixed": 1, "instance": 2}
 _OPS = {"const": 0, "fixed": 1, "advice": 2, "instance": 3, "challenge": 4, "neg": 5, "sum": 6, "product": 7, "scaled": 8}
 TRANSCRIPT_KINDS = {"poseidon": 0, "sha256": 1, "keccak256": 2}   # H2AGG_TRANSCRIPT_KIND_*
+MULTIOPEN_KINDS = {"gwc": 0, "shplonk": 1}                        # H2AGG_MULTIOPEN_*
 R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 
@@ -123,9 +124,11 @@ class _CircuitProofs(C.Structure):
 class VerifyingKey:
     """h2agg_vk: a parsed verifying-key description bound to one engine"""
 
-    def __init__(self, eng, blob: bytes, transcript: str = "poseidon"):
+    def __init__(self, eng, blob: bytes, transcript: str = "poseidon", multiopen: str = "gwc"):
         """transcript: what the key's proofs are written with — "poseidon" (PoseidonTranscriptRead), "sha256" or "keccak256"
-        (ShaRead, transcript/sha.rs; verify_proofs only: the aggregation entry points refuse such a key)"""
+        (ShaRead, transcript/sha.rs; verify_proofs only: the aggregation entry points refuse such a key).
+        multiopen: the scheme the proofs end in — "gwc" (v, one W per rotation group, u) or "shplonk" (y, v, H1, u, H2;
+        verify_proofs and verify_aggregation, not the sharded call); set_multiopen switches it later"""
         self.eng = eng
         self._lib = eng._lib
         self._vk = C.c_void_p()
@@ -135,10 +138,20 @@ class VerifyingKey:
         self.transcript = transcript
         if transcript != "poseidon":
             eng._check(self._lib.h2agg_vk_set_transcript(self._vk, TRANSCRIPT_KINDS[transcript]))
+        self.multiopen = "gwc"
+        if multiopen != "gwc":
+            self.set_multiopen(multiopen)
         # header words of the accepted blob (include/h2agg.h): magic, version, k, num_advice, num_instance, ...
         self.k, self.num_advice_columns, self.num_instance_columns = (
             int.from_bytes(blob[8 + 4 * i:12 + 4 * i], "little") for i in range(3))
         self.shape = vk_shape(blob)
+
+    def set_multiopen(self, multiopen: str):
+        """h2agg_vk_set_multiopen: "gwc" or "shplonk" """
+        if multiopen not in MULTIOPEN_KINDS:
+            raise ValueError("multiopen must be one of %s" % sorted(MULTIOPEN_KINDS))
+        self.eng._check(self._lib.h2agg_vk_set_multiopen(self._vk, MULTIOPEN_KINDS[multiopen]))
+        self.multiopen = multiopen
 
     def close(self):
         if self._vk:

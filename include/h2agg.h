@@ -238,6 +238,32 @@ int h2agg_schema_query_set_commitment(h2agg_schema* s, uint32_t query_node, cons
 int h2agg_schema_batch_multi_open(h2agg_schema* s, const char* key, size_t nq, const int32_t* rotations,
                                   const uint8_t* points, const uint32_t* query_nodes, size_t nw, const uint8_t* w,
                                   const uint8_t v[32], const uint8_t u[32], uint32_t* w_x_out, uint32_t* w_g_out);
+/* The Shplonk twin of h2agg_schema_batch_multi_open: the VERIFIER of the BDFG20 multiopen whose prover is
+ * h2agg_kzg_shplonk_begin / _finish below, as a pair of schema nodes for h2agg_evaluate_multiopen_proof / _prepare.
+ * Stands for: the verifier of poly/kzg/multiopen/shplonk (verifier.rs) and construct_intermediate_sets of halo2_proofs — an
+ * unvendored git dependency of the reference: the set ordering and the order y, v, H1, u, H2 of a proof's tail are recalled
+ * from upstream, not pinned; what is pinned is the definition in the Shplonk section below, which the
+ * prover follows, and the verifier equation at its end.
+ * Inputs: nq queries in VerifierParams::queries order, query q = (poly_ids[q], rotations[q], points + 32 q, query_nodes[q]);
+ * the nodes are opaque, as for the GWC fold; H1, H2 canonical affine; y, v, u canonical scalars.
+ *   A rotation names a point: the one the FIRST query of that rotation carries.  A polynomial's point set is the set of
+ *   rotations its queries name; polynomials with equal point sets form set i, sets numbered in first-seen order of their first
+ *   polynomial, polynomials p_{i,0}, p_{i,1}, ... inside a set in first-seen order of their first query; T: all rotations.
+ *     l_{i,a}(u) = prod_{b in S_i, b != a} (u - z_b) / (z_a - z_b)                    (1 when |S_i| = 1)
+ *     d_i = prod_{b in T \ S_i} (u - z_b),   c_i = d_i / d_0,   t = prod_{b in S_0} (u - z_b)   (= Z_T(u) / d_0)
+ *     right = sum_i v^i c_i sum_j y^j sum_{a in S_i} l_{i,a}(u) * node(p_{i,j}, a)  +  (0 - t) * commit(H1)  +  u * commit(H2)
+ *     left  = 1 * commit(H2)        (a scalar-carrying commitment: multi_exp of zero pairs is the reference's panic)
+ *   Powers ascend from 0.  sum_a l_{i,a}(u) = 1: the commitment of p_{i,j} keeps the scalar v^i c_i y^j, the eval! parts of its
+ *   nodes add up to r_{i,j}(u), which h2agg_evaluate_multiopen_proof subtracts as e G — the header's F + u H2.  Every scalar is
+ *   recorded on the schema's Fr tape and computed on the device.  Keys of the two proof points: "{key}_shplonk_h1",
+ *   "{key}_shplonk_h2".
+ * Refusals (H2AGG_ERR_INVALID, the schema stays usable): an unknown node, nq == 0, a (polynomial, rotation) pair named twice,
+ * a set of more than 32 points.  Two rotations with equal points, or u a point of T \ S_0, invert zero on the tape: the
+ * EVALUATION returns H2AGG_ERR_DIV_ZERO.  y, v, u and points equal to 0 are legal, and so is u in S_0 (t = 0). */
+int h2agg_schema_shplonk_multi_open(h2agg_schema* s, const char* key, size_t nq, const uint32_t* poly_ids,
+                                    const int32_t* rotations, const uint8_t* points, const uint32_t* query_nodes,
+                                    const uint8_t h1[64], const uint8_t h2[64], const uint8_t y[32], const uint8_t v[32],
+                                    const uint8_t u[32], uint32_t* left_out, uint32_t* right_out);
 /* eval(): out_jac = multi_exp(points with scalars) + sum(points without); *has_scalar / out_scalar = the
  * accumulated pure-scalar term (key ""), None -> *has_scalar = 0.  A Mul whose both sides hold
  * commitments, or an Add of non-singleton scalar sides, fails with H2AGG_ERR_INVALID (the reference's
@@ -377,6 +403,24 @@ void h2agg_vk_destroy(h2agg_vk* vk);
  * the reference never folds ShaRead proofs under an aggregation transcript (the outer proof is checked on its own,
  * verify_circuit.rs:1032-1055) — out of scope here. */
 int h2agg_vk_set_transcript(h2agg_vk* vk, int kind);
+/* The multiopen scheme the key's proofs end in: H2AGG_MULTIOPEN_GWC (the default: every existing caller is unchanged; the
+ * proof ends in v, one W per rotation group, u — multiopen.rs:23-102) or H2AGG_MULTIOPEN_SHPLONK (halo2_proofs' ProverSHPLONK /
+ * VerifierSHPLONK, which the reference does not read: recalled, not pinned — after the evaluations the proof reads y, v, H1, u,
+ * H2 and is verified by h2agg_schema_shplonk_multi_open's definition, a query's polynomial being its commitment's key; the
+ * vanishing query is a polynomial of its own).  Anything else -> H2AGG_ERR_INVALID.  The H2VK blob format is unchanged: the
+ * kind is a switch on the parsed key, like the transcript kind, and may be changed between calls (a recording kept for the
+ * other kind is not handed back).
+ * h2agg_verify_proofs honours it per circuit — one call may mix GWC and Shplonk circuits; a Shplonk proof is exactly the
+ * key's scalars and points plus H1 and H2, any other length -> H2AGG_ERR_INVALID for that proof (so a GWC proof under a
+ * Shplonk key, or the reverse, whenever their lengths differ.  They coincide for a circuit whose queries name exactly two
+ * rotations: its GWC proofs end in two W points.  Such a proof under a key of the other kind is read as that kind: status
+ * H2AGG_OK and a pairing verdict of 0, not an error).  h2agg_verify_aggregation and _ex accept Shplonk keys and
+ * mixed calls: the fold is linear in the pair whatever produced it; status, pairing_ok, advice_out and the plan cache work as
+ * for GWC.  h2agg_verify_aggregation_sharded returns H2AGG_ERR_INVALID for a Shplonk key before any exchange — out of
+ * scope for now. */
+#define H2AGG_MULTIOPEN_GWC 0
+#define H2AGG_MULTIOPEN_SHPLONK 1
+int h2agg_vk_set_multiopen(h2agg_vk* vk, int kind);
 typedef struct {
     const h2agg_vk* vk;
     const char* name;
