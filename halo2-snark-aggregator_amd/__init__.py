@@ -203,6 +203,20 @@ def load_library():
         "h2agg_commit_columns": (i32, [ctxp, u64, vp, sz, C.c_uint, vp]),
         "h2agg_witness_check_layout": (i32, [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "h2agg_witness_check": (i32, [ctxp, vp, C.c_uint, vp, vp, vp, u8p, u8p, vp, sz, vp, vp, vp, C.POINTER(u64)]),
+        "h2agg_columns_create": (i32, [ctxp, sz, C.c_uint, C.POINTER(u64)]),
+        "h2agg_columns_destroy": (i32, [ctxp, u64]),
+        "h2agg_columns_info": (i32, [ctxp, u64, C.POINTER(sz), C.POINTER(C.c_uint)]),
+        "h2agg_columns_write": (i32, [ctxp, u64, sz, sz, vp]),
+        "h2agg_columns_read": (i32, [ctxp, u64, sz, sz, vp]),
+        "h2agg_columns_ptr": (i32, [ctxp, u64, sz, C.POINTER(vp)]),
+        "h2agg_columns_move": (i32, [ctxp, u64, sz, u64, sz, sz, C.c_int32]),
+        "h2agg_columns_fft": (i32, [ctxp, u64, sz, u64, sz, sz, i32, u8p]),
+        "h2agg_columns_commit": (i32, [ctxp, u64, u64, sz, sz, vp]),
+        "h2agg_columns_sigmas": (i32, [ctxp, vp, sz, C.c_uint, sz, u8p, u64, sz, u64, sz]),
+        "h2agg_columns_witness_check": (i32, [ctxp, vp, C.c_uint, u64, sz, u64, sz, u64, sz, u8p, u8p, vp, sz, vp, vp, vp,
+                                              C.POINTER(u64)]),
+        "h2agg_columns_shplonk_begin": (i32, [ctxp, u64, u64, sz, sz, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, u8p, u8p, vp,
+                                              C.POINTER(vp)]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -927,6 +941,108 @@ class H2Agg:
                                                   max_rows, counts, first, rows, C.byref(total)))
         lines = None if rows is None else [list(rows[c * max_rows:(c + 1) * max_rows]) for c in range(ncons)]
         return list(counts[:ncons]), list(first[:ncons]), lines, total.value
+
+    # ------------------------------------------------------------------ Fr column stores
+    def columns_create(self, m: int, k: int) -> int:
+        """h2agg_columns_create: a zero-filled slab [m][2^k] of Fr in device memory that the context owns -> its handle"""
+        h = C.c_uint64()
+        self._check(self._lib.h2agg_columns_create(self._ctx, m, k, C.byref(h)))
+        return h.value
+
+    def columns_destroy(self, handle: int):
+        self._check(self._lib.h2agg_columns_destroy(self._ctx, handle))
+
+    def columns_info(self, handle: int):
+        """h2agg_columns_info: -> (m, k)"""
+        m, k = C.c_size_t(), C.c_uint()
+        self._check(self._lib.h2agg_columns_info(self._ctx, handle, C.byref(m), C.byref(k)))
+        return m.value, k.value
+
+    def columns_write(self, handle: int, first: int, data, count: Optional[int] = None):
+        """h2agg_columns_write: data = whole columns (32 * 2^k bytes each) to columns first, first + 1, ... of the store, or the
+        address of a host buffer (e.g. from host_alloc) together with count; synchronous; an element >= r raises
+        H2AggError(ERR_NONCANONICAL)"""
+        if isinstance(data, int):
+            self._check(self._lib.h2agg_columns_write(self._ctx, handle, first, count, C.c_void_p(data)))
+            return
+        _m, k = self.columns_info(handle)
+        count = len(data) // (32 << k)
+        _need(data, (32 << k) * count, "data")
+        self._check(self._lib.h2agg_columns_write(self._ctx, handle, first, count, self._hostptr(data)))
+
+    def columns_read(self, handle: int, first: int, count: int) -> bytes:
+        """h2agg_columns_read: columns first .. first + count - 1 of the store as bytes; synchronous"""
+        m, k = self.columns_info(handle)
+        ok = count >= 1 and 0 <= first and first + count <= m   # (the library refuses the others before it writes)
+        out = C.create_string_buffer((32 << k) * count if ok else 1)
+        self._check(self._lib.h2agg_columns_read(self._ctx, handle, first, count, out))
+        return out.raw[:(32 << k) * count]
+
+    def columns_ptr(self, handle: int, first: int = 0) -> int:
+        """h2agg_columns_ptr: the device address of column `first`, for the _device entry points; valid until the store goes"""
+        p = C.c_void_p()
+        self._check(self._lib.h2agg_columns_ptr(self._ctx, handle, first, C.byref(p)))
+        return p.value
+
+    def columns_move(self, src: int, sfirst: int, dst: int, dfirst: int, count: int, rotation: int = 0):
+        """h2agg_columns_move: dst[dfirst + j][i] = src[sfirst + j][(i + rotation) mod 2^k], j < count; queued"""
+        if not -(1 << 31) <= rotation < (1 << 31):
+            raise ValueError("rotation must be an int32")
+        self._check(self._lib.h2agg_columns_move(self._ctx, src, sfirst, dst, dfirst, count, rotation))
+
+    def columns_fft(self, src: int, sfirst: int, dst: int, dfirst: int, count: int, inverse: bool = False,
+                    shift: Optional[bytes] = None):
+        """h2agg_columns_fft: fr_fft_batch of `count` columns of a store into a store (the same range: in place); queued"""
+        if shift is not None:
+            _need(shift, 32, "shift")
+        self._check(self._lib.h2agg_columns_fft(self._ctx, src, sfirst, dst, dfirst, count, int(bool(inverse)), shift))
+
+    def columns_commit(self, bases_handle: int, src: int, first: int, count: int) -> List[bytes]:
+        """h2agg_columns_commit: commit_columns of `count` columns of a store -> canonical affine points, 64 bytes each"""
+        out = C.create_string_buffer(64 * count if 0 < count < (1 << 32) else 1)
+        self._check(self._lib.h2agg_columns_commit(self._ctx, bases_handle, src, first, count, out))
+        return [out.raw[64 * j:64 * j + 64] for j in range(count)]
+
+    def columns_sigmas(self, mapping, m: int, k: int, usable: int, delta: bytes, dst_lagrange: int = 0, lfirst: int = 0,
+                       dst_coeff: int = 0, cfirst: int = 0):
+        """h2agg_columns_sigmas: permutation_sigmas with the outputs in stores (a handle of 0: that output is not wanted)"""
+        _need(delta, 32, "delta")
+        words = _words(mapping, 2 * m << k, "mapping") if _perm_shape_ok(m, k, usable) else (C.c_uint32 * 1)()
+        self._check(self._lib.h2agg_columns_sigmas(self._ctx, words, m, k, usable, delta, dst_lagrange, lfirst, dst_coeff, cfirst))
+
+    def columns_witness_check(self, vk, what: int, advice, fixed, instance, challenges, theta: Optional[bytes], mapping,
+                              max_rows: int = 16, want_rows: bool = True):
+        """h2agg_columns_witness_check: witness_check with the slabs in stores: advice, fixed, instance are (handle, first
+        column) pairs, or None where the key has no column of the kind -> (counts, first_rows, rows, total) as witness_check"""
+        sh = vk.shape
+        k = sh["k"]
+        ncons = sh["gate_polys"] + sh["num_permutation_columns"] + len(sh["lookups"])
+        if theta is not None:
+            _need(theta, 32, "theta")
+        if max_rows < 0:
+            raise ValueError("max_rows must be >= 0")
+        places = [x for pair in (advice, fixed, instance) for x in ((0, 0) if pair is None else (int(pair[0]), int(pair[1])))]
+        words = None if mapping is None else _words(mapping, 2 * sh["num_permutation_columns"] << k, "mapping")
+        counts, first = (C.c_uint32 * max(ncons, 1))(), (C.c_uint32 * max(ncons, 1))()
+        rows = (C.c_uint32 * max(ncons * max_rows, 1))() if want_rows else None
+        total = C.c_uint64()
+        self._check(self._lib.h2agg_columns_witness_check(self._ctx, vk._vk, what, *places, self._vk_challenges(vk, challenges), theta,
+                                                          words, max_rows, counts, first, rows, C.byref(total)))
+        lines = None if rows is None else [list(rows[c * max_rows:(c + 1) * max_rows]) for c in range(ncons)]
+        return list(counts[:ncons]), list(first[:ncons]), lines, total.value
+
+    def columns_shplonk_begin(self, g_handle: int, src: int, first: int, npoly: int, queries, points: bytes, evals: bytes,
+                              y: bytes, v: bytes):
+        """h2agg_columns_shplonk_begin: kzg_shplonk_begin over npoly columns of a store -> (H1, the object for
+        kzg_shplonk_finish / kzg_shplonk_destroy); the store is free again when the call returns"""
+        qs, nq, npoints = self._queries(queries, points)
+        _need(evals, 32 * nq, "evals")
+        _need(y, 32, "y")
+        _need(v, 32, "v")
+        h1, obj = C.create_string_buffer(64), C.c_void_p()
+        self._check(self._lib.h2agg_columns_shplonk_begin(self._ctx, g_handle, src, first, npoly, qs, nq, points, npoints, evals, y, v,
+                                                          h1, C.byref(obj)))
+        return h1.raw, obj
 
     def params_setup(self, k: int, s: bytes):
         """ParamsKZG::setup with the trapdoor `s` (32-byte LE, canonical) -> (g_handle, g_lagrange_handle), 2^k points each"""

@@ -43,6 +43,7 @@
 #include "quotient_kernels.hpp"
 #include "keygen_kernels.hpp"
 #include "witness_kernels.hpp"
+#include "columns_kernels.hpp"
 #include "pairing.hpp"
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
 // the same pairing once more, compiled for BMI2 + ADX (csrc/pairing.hpp's header): taken when the CPU has both
@@ -113,6 +114,12 @@ struct Table {   // owns its device buffers: they go with it, behind a synchroni
         comb_n = 0;
         comb_retired.clear();
     }
+};
+struct ColumnStore {   // a slab [m][2^k] of canonical Fr behind a handle (csrc/columns.inc): owns it, as a Table owns its columns
+    DevMem d;
+    size_t m = 0;
+    unsigned k = 0;
+    size_t col() const { return (size_t)32 << k; }   // bytes of a column
 };
 struct PreTable {   // what msm_run needs of it
     const uint8_t* d;
@@ -283,6 +290,7 @@ struct h2agg_ctx {
     hipStream_t aux_stream = nullptr;
 
     std::map<uint64_t, Table> tables;
+    std::map<uint64_t, ColumnStore> stores;   // Fr column stores (csrc/columns.inc); handles come from the tables' counter
     uint64_t next_handle = 1;
 
     // multi-GPU: this context's rank in an RCCL communicator (csrc/comm.inc); ncclComm_t kept opaque here
@@ -753,3 +761,4 @@ int h2agg_synchronize(h2agg_ctx* c) try {
 #include "quotient.inc"
 #include "keygen.inc"
 #include "witness.inc"
+#include "columns.inc"

@@ -85,6 +85,11 @@ int stage_in(h2agg_ctx* c, DevBuf& b, const uint8_t* src, size_t bytes, size_t a
     if (bytes) HIP_TRY(c, hipMemcpyAsync((uint8_t*)b.p + at, src, bytes, hipMemcpyHostToDevice, c->stream));
     return H2AGG_OK;
 }
+//   in, to device memory that is no grow-only buffer (a column store's slab)
+int stage_in(h2agg_ctx* c, uint8_t* d_dst, const uint8_t* src, size_t bytes) {
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return H2AGG_OK;
+}
 //   out, the tail of the call: `bytes` at d_src back to the host, then finish() synchronises and reports the flags
 int stage_out(h2agg_ctx* c, uint8_t* dst, const void* d_src, size_t bytes) {
     HIP_TRY(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));

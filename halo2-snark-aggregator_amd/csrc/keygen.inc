@@ -5,8 +5,8 @@
 // unvendored git dependency of the reference, recalled from upstream (DESIGN.md section 2 and 5.15); the yardstick is the
 // definition in include/h2agg.h.
 //
-// There is no _device twin yet: perm_sigma_queue takes device pointers and synchronises nothing, so a resident twin is a
-// wrapper that can arrive later, with its caller-stream case (DESIGN.md 5.15, as 5.8 says of h2agg_fr_fft_batch).
+// There is no _device twin: the resident forms run over column stores (h2agg_columns_sigmas, h2agg_columns_commit in
+// csrc/columns.inc, DESIGN.md 5.20), on top of perm_sigma_queue and commit_columns_run below.
 
 namespace {
 
@@ -51,6 +51,21 @@ int perm_sigma_queue(h2agg_ctx* c, const void* d_mapping, size_t m, unsigned k, 
     hipLaunchKernelGGL(k_perm_sigma, dim3(grid_for(c, cells)), dim3(BLOCK), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return H2AGG_OK;
+}
+
+// The commitments of the slab d_cols[m][2^k] in device memory against a table that holds 2^k points or more, as canonical
+// affine points to the host: what h2agg_commit_columns runs behind its staging and h2agg_columns_commit over a store.
+int commit_columns_run(h2agg_ctx* c, uint64_t bases_handle, const uint8_t* d_cols, size_t m, unsigned k, uint8_t* out_aff) {
+    const size_t n = (size_t)1 << k;
+    TRY(ensure(c, c->kg_jac, 96 * m));
+    TRY(clear_flags(c));
+    // B columns per set of MSM launches: as many as hold 2^KG_COMMIT_WORK_LOG scalars (the sort's and the buckets' work memory
+    // grows with the scalars in flight), at least one, or the debug key commit_chunk; the batched MSM cuts further by its own limits
+    size_t B = std::max<size_t>(1, ((size_t)1 << KG_COMMIT_WORK_LOG) >> k);
+    if (c->dbg_commit_chunk) B = (size_t)c->dbg_commit_chunk;
+    for (size_t q = 0; q < m; q += B)
+        TRY(h2agg_g1_msm_device_batch_async(c, bases_handle, d_cols + 32 * n * q, n, std::min(B, m - q), (uint8_t*)c->kg_jac.p + 96 * q));
+    return h2agg_g1_batch_to_affine_device(c, (const uint8_t*)c->kg_jac.p, m, out_aff);   // joins, synchronises, reports the flags
 }
 
 }  // namespace
@@ -152,15 +167,7 @@ int h2agg_commit_columns(h2agg_ctx* c, uint64_t bases_handle, const uint8_t* col
     TRY(ensure(c, c->in_b, 32 * n * m));
     TRY(ensure(c, c->kg_jac, 96 * m));
     TRY(stage_in(c, c->in_b, columns, 32 * n * m));   // one staging of the slab
-    TRY(clear_flags(c));
-    // B columns per set of MSM launches: as many as hold 2^KG_COMMIT_WORK_LOG scalars (the sort's and the buckets' work memory
-    // grows with the scalars in flight), at least one, or the debug key commit_chunk; the batched MSM cuts further by its own limits
-    size_t B = std::max<size_t>(1, ((size_t)1 << KG_COMMIT_WORK_LOG) >> k);
-    if (c->dbg_commit_chunk) B = (size_t)c->dbg_commit_chunk;
-    for (size_t q = 0; q < m; q += B)
-        TRY(h2agg_g1_msm_device_batch_async(c, bases_handle, (const uint8_t*)c->in_b.p + 32 * n * q, n, std::min(B, m - q),
-                                            (uint8_t*)c->kg_jac.p + 96 * q));
-    return h2agg_g1_batch_to_affine_device(c, (const uint8_t*)c->kg_jac.p, m, out_aff);   // joins, synchronises, reports the flags
+    return commit_columns_run(c, bases_handle, (const uint8_t*)c->in_b.p, m, k, out_aff);
 } API_CATCH
 
 }  // extern "C"

@@ -190,8 +190,10 @@ int shplonk_name_mismatch(h2agg_ctx* c, h2agg_shplonk* o, const uint32_t* querie
     return fail(c, H2AGG_ERR_INVALID, "shplonk: a numerator does not vanish on its point set");
 }
 
-int shplonk_begin_run(h2agg_ctx* c, h2agg_shplonk* o, const uint8_t* polys, const uint32_t* queries, size_t nq, const uint8_t* evals,
-                      uint8_t* h1_aff) {
+// polys: the slab [npoly][2^k] on the host, or with `resident` in device memory (a column store's columns): the object's own
+// slab is filled by stage_in or by a device copy, so the source is free once the call has returned
+int shplonk_begin_run(h2agg_ctx* c, h2agg_shplonk* o, const uint8_t* polys, bool resident, const uint32_t* queries, size_t nq,
+                      const uint8_t* evals, uint8_t* h1_aff) {
     const size_t n = (size_t)1 << o->k, bytes = 32 * n;
     shplonk_interpolate(o);
     // the call's block: per set the list and weights of N_i, -corr, the queries (N_i, z) of the sweeps; the top values
@@ -224,7 +226,10 @@ int shplonk_begin_run(h2agg_ctx* c, h2agg_shplonk* o, const uint8_t* polys, cons
     enum { STAGE, NUMERATORS, DIVIDE, COMMIT };
     PhaseClock phases(c);
     phases.mark(STAGE);
-    TRY(stage_in(c, o->slab, polys, bytes * o->npoly));
+    if (resident)
+        HIP_TRY(c, hipMemcpyAsync(o->slab.p, polys, bytes * o->npoly, hipMemcpyDeviceToDevice, c->stream));
+    else
+        TRY(stage_in(c, o->slab, polys, bytes * o->npoly));
     TRY(stage_in(c, o->lists, (const uint8_t*)blob.w.data(), 4 * blob.w.size()));
     TRY(clear_flags(c));
     const uint32_t* d_lists = (const uint32_t*)o->lists.p;
@@ -337,14 +342,10 @@ int shplonk_finish_run(h2agg_ctx* c, h2agg_shplonk* o, const ph::HFr& u, uint8_t
     return H2AGG_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int h2agg_kzg_shplonk_begin(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries,
-                            size_t nq, const uint8_t* points, size_t npoints, const uint8_t* evals, const uint8_t y[32],
-                            const uint8_t v[32], uint8_t h1_aff[64], h2agg_shplonk** out) try {
-    TRY(bind(c));
+// h2agg_kzg_shplonk_begin behind bind(), over a host slab or (resident) a slab in device memory: h2agg_columns_shplonk_begin
+int shplonk_begin(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, bool resident, size_t npoly, unsigned k, const uint32_t* queries,
+                  size_t nq, const uint8_t* points, size_t npoints, const uint8_t* evals, const uint8_t* y, const uint8_t* v,
+                  uint8_t* h1_aff, h2agg_shplonk** out) {
     if (out) *out = nullptr;
     if (!polys || !evals || !y || !out) return fail(c, H2AGG_ERR_INVALID, "null buffer");
     std::unique_ptr<h2agg_shplonk> o(new h2agg_shplonk());
@@ -361,9 +362,20 @@ int h2agg_kzg_shplonk_begin(h2agg_ctx* c, uint64_t g_handle, const uint8_t* poly
     o->npoly = npoly;
     TRY(shplonk_sets(c, o.get(), npoly, queries, nq, ev));
     if (c->dbg_phases) c->last_phases.clear();
-    TRY(shplonk_begin_run(c, o.get(), polys, queries, nq, evals, h1_aff));
+    TRY(shplonk_begin_run(c, o.get(), polys, resident, queries, nq, evals, h1_aff));
     *out = o.release();
     return H2AGG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int h2agg_kzg_shplonk_begin(h2agg_ctx* c, uint64_t g_handle, const uint8_t* polys, size_t npoly, unsigned k, const uint32_t* queries,
+                            size_t nq, const uint8_t* points, size_t npoints, const uint8_t* evals, const uint8_t y[32],
+                            const uint8_t v[32], uint8_t h1_aff[64], h2agg_shplonk** out) try {
+    TRY(bind(c));
+    return shplonk_begin(c, g_handle, polys, false, npoly, k, queries, nq, points, npoints, evals, y, v, h1_aff, out);
 } API_CATCH
 
 int h2agg_kzg_shplonk_finish(h2agg_shplonk* o, const uint8_t u[32], uint8_t h2_aff[64]) try {

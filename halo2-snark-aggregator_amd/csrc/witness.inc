@@ -5,8 +5,8 @@
 // upstream (DESIGN.md section 2 and 5.17); the yardstick is the definition in include/h2agg.h.  The order of the constraints
 // is pinned by halo2-snark-aggregator-api/src/systems/halo2/params.rs:74-224.
 //
-// There is no _device twin yet: wc_queue takes device pointers and synchronises nothing, so a resident twin is a wrapper
-// that can arrive later, with its caller-stream case (as keygen.inc says of its own).
+// There is no _device twin: the resident form runs over column stores (h2agg_columns_witness_check in csrc/columns.inc,
+// DESIGN.md 5.20), on top of wc_check, wc_queue and wc_report_out below.
 
 namespace {
 
@@ -269,6 +269,22 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
     return H2AGG_OK;
 }
 
+// The report of the check wc_queue queued, from wc_work to the caller's host arrays; synchronises and reports the flags.
+int wc_report_out(h2agg_ctx* c, const WcLayout& l, size_t max_rows, uint32_t* counts, uint32_t* first_rows, uint32_t* rows, uint64_t* total) {
+    const uint8_t* w = (const uint8_t*)c->wc_work.p;
+    HIP_TRY(c, hipMemcpyAsync(counts, w + l.counts, 4 * l.C, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(first_rows, w + l.first_rows, 4 * l.C, hipMemcpyDeviceToHost, c->stream));
+    if (max_rows) {
+        if (l.max_rows == max_rows) {
+            HIP_TRY(c, hipMemcpyAsync(rows, w + l.rows, 4 * l.C * max_rows, hipMemcpyDeviceToHost, c->stream));
+        } else {   // max_rows > n: the device lines are n wide, the tail of every line of the caller's is "no row"
+            memset(rows, 0xFF, 4 * l.C * max_rows);
+            HIP_TRY(c, hipMemcpy2DAsync(rows, 4 * max_rows, w + l.rows, 4 * l.max_rows, 4 * l.max_rows, l.C, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    return stage_out(c, (uint8_t*)total, w + l.total_at, 8);
+}
+
 }  // namespace
 
 extern "C" {
@@ -312,18 +328,7 @@ int h2agg_witness_check(h2agg_ctx* c, const h2agg_vk* vk, unsigned what, const u
     TRY(clear_flags(c));
     const uint8_t* d = (const uint8_t*)c->in_a.p;
     TRY(wc_queue(c, *vk, call, d, d + A * col, d + (A + F) * col, c->in_b.p));
-    const uint8_t* w = (const uint8_t*)c->wc_work.p;
-    HIP_TRY(c, hipMemcpyAsync(counts, w + l.counts, 4 * l.C, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(first_rows, w + l.first_rows, 4 * l.C, hipMemcpyDeviceToHost, c->stream));
-    if (max_rows) {
-        if (l.max_rows == max_rows) {
-            HIP_TRY(c, hipMemcpyAsync(rows, w + l.rows, 4 * l.C * max_rows, hipMemcpyDeviceToHost, c->stream));
-        } else {   // max_rows > n: the device lines are n wide, the tail of every line of the caller's is "no row"
-            memset(rows, 0xFF, 4 * l.C * max_rows);
-            HIP_TRY(c, hipMemcpy2DAsync(rows, 4 * max_rows, w + l.rows, 4 * l.max_rows, 4 * l.max_rows, l.C, hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    return stage_out(c, (uint8_t*)total, w + l.total_at, 8);
+    return wc_report_out(c, l, max_rows, counts, first_rows, rows, total);
 } API_CATCH
 
 }  // extern "C"

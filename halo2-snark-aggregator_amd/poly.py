@@ -6,7 +6,8 @@ h2agg_lookup_product); and the lookup argument in front of its product (h2agg_fr
 and the quotient polynomial h(X) from a verifying key (h2agg_vk_expressions_eval, h2agg_quotient); and the keys those stages
 take: the permutation's mapping, sigma columns and commitments, the fixed columns' (h2agg_permutation_assembly,
 h2agg_permutation_sigmas, h2agg_commit_columns); and, in front of all that work, the check whether a witness satisfies the key
-at all, and where it does not (h2agg_witness_check).
+at all, and where it does not (h2agg_witness_check); and, for a caller that keeps its columns on the device between those
+stages, ColumnStore and the resident_* spellings of the slab helpers (h2agg_columns_*).
 
 halo2_proofs is an unvendored git dependency of the reference: the names below are recalled from upstream
 (poly/domain.rs), not pinned.  What each function computes is the definition in include/h2agg.h:
@@ -452,3 +453,174 @@ def fixed_key(eng, gl_handle: int, fixed_cols, k: int):
     """the fixed columns' share of keygen: Lagrange columns -> (coeff, commitments): columns_lagrange_to_coeff of them and
     their commitments against g_lagrange as affine points (the fixed commitments of a verifying key)"""
     return columns_lagrange_to_coeff(eng, fixed_cols, k), commit_columns_lagrange(eng, gl_handle, fixed_cols, k)
+
+
+# ---------------------------------------------------------------------------------------------- columns that stay on the device
+class ColumnView:
+    """columns first .. first + count - 1 of a ColumnStore: what the resident helpers below take and answer.  The range is
+    checked here, in the store's own column numbers; view() of a view counts from the view's first column."""
+
+    def __init__(self, store, first: int, count: int):
+        first, count = int(first), int(count)
+        if count < 1 or first < 0 or first + count > store.m:
+            raise ValueError("columns %d .. %d are outside a store of %d columns (or count < 1)" % (first, first + count - 1, store.m))
+        self.store, self.first, self.count = store, first, count
+
+    k = property(lambda self: self.store.k)
+    handle = property(lambda self: self.store.handle)
+
+    def view(self, first: int, count: int) -> "ColumnView":
+        if count < 1 or first < 0 or first + count > self.count:
+            raise ValueError("columns %d .. %d are outside a view of %d columns (or count < 1)" % (first, first + count - 1, self.count))
+        return ColumnView(self.store, self.first + first, count)
+
+    def overlaps(self, other: "ColumnView") -> bool:
+        """one store and at least one column in common"""
+        return (self.store.handle == other.store.handle and self.first < other.first + other.count
+                and other.first < self.first + self.count)
+
+    def same(self, other: "ColumnView") -> bool:
+        return self.store.handle == other.store.handle and (self.first, self.count) == (other.first, other.count)
+
+    def write(self, cols):
+        self.store.write(self.first, cols, self.count)
+
+    def read(self):
+        return self.store.read(self.first, self.count)
+
+    def ptr(self, column: int = 0) -> int:
+        if not 0 <= column < self.count:
+            raise ValueError("column %d is outside a view of %d columns" % (column, self.count))
+        return self.store.ptr(self.first + column)
+
+
+class ColumnStore:
+    """A slab [m][2^k] of Fr in device memory that the engine's context owns (h2agg_columns_create): a context manager, freed
+    on exit or by close().  handle=...: wraps a store that somebody else made and frees (nothing is called)."""
+
+    def __init__(self, eng, m: int, k: int, handle=None):
+        self.eng, self.m, self.k = eng, int(m), int(k)
+        self.owned = handle is None
+        self.handle = eng.columns_create(m, k) if handle is None else int(handle)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.owned and self.handle:
+            self.eng.columns_destroy(self.handle)
+        self.handle = 0
+
+    def view(self, first: int = 0, count=None) -> ColumnView:
+        return ColumnView(self, first, self.m - first if count is None else count)
+
+    def write(self, first: int, cols, count=None):
+        """cols: a slab of whole columns, or a list of columns"""
+        data = cols if isinstance(cols, (bytes, bytearray, memoryview)) else b"".join(_poly(c, self.k, "column") for c in cols)
+        if len(data) % (32 << self.k) or not data or (count is not None and len(data) != (32 << self.k) * count):
+            raise ValueError("cols must be %s whole columns of 2^%d elements" % ("some" if count is None else count, self.k))
+        ColumnView(self, first, len(data) // (32 << self.k))
+        self.eng.columns_write(self.handle, first, data)
+
+    def read(self, first: int = 0, count=None):
+        """-> a list of columns"""
+        v = self.view(first, count)
+        return _split(self.eng.columns_read(self.handle, v.first, v.count), self.k)
+
+    def ptr(self, first: int = 0) -> int:
+        ColumnView(self, first, 1)
+        return self.eng.columns_ptr(self.handle, first)
+
+
+def _resident_fft(eng, src: ColumnView, dst, inverse: bool, shift):
+    dst = src if dst is None else dst
+    if dst.count != src.count or dst.k != src.k:
+        raise ValueError("source and destination must be as many columns of one k")
+    if src.overlaps(dst) and not src.same(dst):
+        raise ValueError("source and destination overlap (in place is the same range)")
+    eng.columns_fft(src.handle, src.first, dst.handle, dst.first, src.count, inverse, shift)
+    return dst
+
+
+def resident_lagrange_to_coeff(eng, src: ColumnView, dst: ColumnView = None) -> ColumnView:
+    """columns_lagrange_to_coeff over a store's columns (h2agg_columns_fft, queued): into dst, or in place -> the view that
+    holds the result"""
+    return _resident_fft(eng, src, dst, True, None)
+
+
+def resident_coeff_to_lagrange(eng, src: ColumnView, dst: ColumnView = None) -> ColumnView:
+    """columns_coeff_to_lagrange over a store's columns"""
+    return _resident_fft(eng, src, dst, False, None)
+
+
+def resident_extended_to_coeff(eng, src: ColumnView, dst: ColumnView = None, shift: bytes = ZETA) -> ColumnView:
+    """columns_extended_to_coeff over the columns of a store of 2^extended_k rows"""
+    return _resident_fft(eng, src, dst, True, shift)
+
+
+def resident_extended_from_padded(eng, src: ColumnView, dst: ColumnView = None, shift: bytes = ZETA) -> ColumnView:
+    """the transform of columns_coeff_to_extended over columns of a store of 2^extended_k rows that already hold the
+    coefficients zero-padded (a new store is zero-filled: write the 2^k coefficients of a column in front)"""
+    return _resident_fft(eng, src, dst, False, shift)
+
+
+def resident_commit_columns_lagrange(eng, gl_handle: int, cols: ColumnView):
+    """commit_columns_lagrange of a store's columns (h2agg_columns_commit) -> affine points, 64 bytes each"""
+    return eng.columns_commit(gl_handle, cols.handle, cols.first, cols.count)
+
+
+def resident_commit_columns_coeff(eng, g_handle: int, cols: ColumnView):
+    """commit_columns_coeff of a store's columns"""
+    return eng.columns_commit(g_handle, cols.handle, cols.first, cols.count)
+
+
+def resident_permutation_key(eng, gl_handle: int, mapping, m: int, k: int, usable: int, delta: bytes):
+    """permutation_key with the sigma columns left on the device: -> (lagrange, coeff, commitments), two new ColumnStores of
+    m columns (the caller closes them) and the commitments against g_lagrange"""
+    lag, coeff = ColumnStore(eng, m, k), None
+    try:
+        coeff = ColumnStore(eng, m, k)
+        eng.columns_sigmas(mapping, m, k, usable, delta, lag.handle, 0, coeff.handle, 0)
+        return lag, coeff, eng.columns_commit(gl_handle, lag.handle, 0, m)
+    except Exception:
+        lag.close()
+        if coeff is not None:
+            coeff.close()
+        raise
+
+
+def _key_place(view, count: int, k: int, what: str):
+    if count == 0:
+        return None
+    if view is None or view.count != count or view.k != k:
+        raise ValueError("%s must be a view of %d columns of 2^%d rows" % (what, count, k))
+    return (view.handle, view.first)
+
+
+def resident_witness_check(eng, vk, advice, fixed, instance, challenges, theta=None, mapping=None, what=None, max_rows=16):
+    """witness_check over views of stores (None where the key has no column of the kind) -> a WitnessReport"""
+    from . import WC_GATES, WC_LOOKUPS, WC_PERMUTATION
+    sh = vk.shape
+    k = sh["k"]
+    if what is None:
+        what = WC_GATES | (WC_PERMUTATION if mapping is not None else 0) | (WC_LOOKUPS if theta is not None else 0)
+    counts, first_rows, rows, total = eng.columns_witness_check(
+        vk, what, _key_place(advice, sh["num_advice"], k, "advice"), _key_place(fixed, sh["num_fixed"], k, "fixed"),
+        _key_place(instance, sh["num_instance"], k, "instance"), _challenges(vk, challenges), theta, mapping, max_rows, max_rows > 0)
+    return WitnessReport(eng.witness_check_layout(vk), counts, first_rows, rows, total)
+
+
+def resident_shplonk_prove(eng, g_handle: int, polys: ColumnView, queries, points: bytes, y: bytes, v: bytes, squeeze_u):
+    """shplonk_prove over a store's columns (coefficient form): the values through h2agg_fr_poly_eval_device over the store's
+    pointer, the two rounds through h2agg_columns_shplonk_begin and the existing finish -> (evals, h1, h2)"""
+    queries = [(int(p), int(z)) for p, z in queries]
+    evals = eng.fr_poly_eval_device(polys.ptr(), polys.count, polys.k, queries, points)
+    h1, obj = eng.columns_shplonk_begin(g_handle, polys.handle, polys.first, polys.count, queries, points, evals, y, v)
+    try:
+        h2 = eng.kzg_shplonk_finish(obj, squeeze_u(h1))
+    finally:
+        eng.kzg_shplonk_destroy(obj)
+    return [evals[32 * q:32 * q + 32] for q in range(len(queries))], h1, h2

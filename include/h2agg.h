@@ -625,7 +625,7 @@ int h2agg_fr_fft_device(h2agg_ctx* ctx, const void* d_in, unsigned k, int invers
  * to all its Lagrange columns at once (lagrange_to_coeff of every advice column) and what h2agg_quotient does inside.
  * Refusals: those of h2agg_fr_fft, and m == 0: H2AGG_ERR_INVALID.  The slab is staged whole (as h2agg_fr_poly_eval stages its
  * slab): one the device cannot hold is H2AGG_ERR_NOMEM.  An element >= r in any column: H2AGG_ERR_NONCANONICAL from the call;
- * `out` is then unspecified.  The context stays usable after any of them.  There is no _device twin yet. */
+ * `out` is then unspecified.  The context stays usable after any of them.  The resident form is h2agg_columns_fft. */
 int h2agg_fr_fft_batch(h2agg_ctx* ctx, const uint8_t* in, size_t m, unsigned k, int inverse, const uint8_t shift[32],
                        uint8_t* out);
 
@@ -942,7 +942,7 @@ int h2agg_quotient_device(h2agg_ctx* ctx, const h2agg_vk* vk, const void* d_advi
  *   H2AGG_ERR_NONCANONICAL through the context's device status, as h2agg_g1_msm_preloaded reports it; out_aff is then
  *   unspecified.  Out of memory: H2AGG_ERR_NOMEM.  The context stays usable after each.
  *
- * These entry points have no device-memory twins yet; the functions behind them take device pointers. */
+ * The resident forms are h2agg_columns_sigmas and h2agg_columns_commit, over column stores. */
 #define H2AGG_PERM_MAX_COLUMNS 4096
 int h2agg_permutation_assembly(size_t m, unsigned k, size_t usable, const uint32_t* copies, size_t ncopies, uint32_t* mapping);
 int h2agg_permutation_sigmas(h2agg_ctx* ctx, const uint32_t* mapping, size_t m, unsigned k, size_t usable, const uint8_t delta[32],
@@ -994,7 +994,7 @@ int h2agg_commit_columns(h2agg_ctx* ctx, uint64_t bases_handle, const uint8_t* c
  *   >= r: H2AGG_ERR_NONCANONICAL from the call.  A column element >= r: H2AGG_ERR_NONCANONICAL through the context's device
  *   status, from the call; the outputs are then unspecified.  Out of memory: H2AGG_ERR_NOMEM.
  *
- * These entry points have no device-memory twins yet; the function behind the check takes device pointers. */
+ * The resident form is h2agg_columns_witness_check, over column stores. */
 #define H2AGG_WC_GATES 1
 #define H2AGG_WC_PERMUTATION 2
 #define H2AGG_WC_LOOKUPS 4
@@ -1002,6 +1002,82 @@ int h2agg_witness_check_layout(const h2agg_vk* vk, size_t* n_gate_polys, size_t*
 int h2agg_witness_check(h2agg_ctx* ctx, const h2agg_vk* vk, unsigned what, const uint8_t* advice, const uint8_t* fixed,
                         const uint8_t* instance, const uint8_t* challenges, const uint8_t theta[32], const uint32_t* mapping,
                         size_t max_rows, uint32_t* counts, uint32_t* first_rows, uint32_t* rows, uint64_t* total);
+
+/* ---- Fr column stores: prover columns that stay on the device between stages -------------------------------------------------
+ * What h2agg_bases_upload / h2agg_g1_msm_preloaded are to G1 bases, for scalars: a store is a slab [m][n] of canonical 32-byte
+ * little-endian Fr elements, n = 2^k, column j at byte 32 * n * j, in DEVICE memory that the context owns behind a handle
+ * (handles are never 0 and never reused; a store's handle is no base table's).  A caller without HIP of its own writes its
+ * witness once, runs the stages over stores and reads back only commitments, evaluations and reports.  The families that take
+ * whole slabs have resident forms below; every other family runs over a store through its _device entry point and
+ * h2agg_columns_ptr.  Each resident form answers byte for byte what its host-buffer family answers, keeps that family's
+ * definitions and refusals, and changes only where the columns live.
+ *
+ * Buffer rules.  A store's memory is the library's, ordered on the context's stream: everything below is queued there, and a
+ * call synchronises only where results go to host memory (said per call).  h2agg_set_stream: the stores follow the rule the
+ * base tables and the context's work memory follow — the switch joins and waits for everything queued on the old stream, so a
+ * store is complete when h2agg_set_stream returns and is ordered on the new stream from then on; nothing is copied or moved.
+ *
+ * h2agg_columns_create   allocates exactly 32 * m * n bytes, zero-filled; *handle_out names the store.
+ * h2agg_columns_destroy  waits for the work queued on the context and frees the slab.  h2agg_destroy frees every store that
+ *   is left, as it frees the base tables.
+ * h2agg_columns_info     m and k of a store (either output may be NULL).
+ * h2agg_columns_write    columns first .. first + count - 1 from host memory (pageable or from h2agg_host_alloc; count * n
+ *   elements); synchronous.  Every element written is checked: one >= r gives H2AGG_ERR_NONCANONICAL from the call, the written
+ *   columns are then unspecified (write them again), the other columns and the context are as before.  With the debug key
+ *   "phases" h2agg_last_phases gives " stage=ms check=ms": the copy and the check of the elements.
+ * h2agg_columns_read     the same range back to host memory; synchronous.
+ * h2agg_columns_ptr      the device address of column `first`, valid until the store is destroyed: what the _device entry
+ *   points take (columns first, first + 1, ... follow at 32 * n bytes each).  The memory is ordered on the context's stream,
+ *   which is exactly what the buffer rules of the _device entry points ask of a caller's buffers: handing the pointer to
+ *   them needs no synchronisation.  A caller that touches the memory with HIP of its own orders that work against the
+ *   context's stream itself.
+ * h2agg_columns_move     dst[dfirst + j][i] = src[sfirst + j][(i + rotation) mod n] for j < count, with the mathematical
+ *   modulus: any int32 rotation is legal, -1 reads the row before.  Queued.  The two stores must have one k.  One store on both
+ *   sides is allowed when the two column ranges are disjoint, or when they are the same range and rotation mod n == 0 (nothing
+ *   is done); any other overlap: H2AGG_ERR_INVALID.
+ *
+ * Resident forms.
+ * h2agg_columns_fft      h2agg_fr_fft_batch over `count` columns, k the stores'; queued, no synchronisation (a workspace that
+ *   has to grow drains the device first, as for h2agg_fr_fft_device).  In place is allowed: dst == src with dfirst == sfirst.
+ *   Any other overlap of the two ranges and stores of different k: H2AGG_ERR_INVALID.  An element >= r raises the context's
+ *   device status, as for h2agg_fr_fft_device.
+ * h2agg_columns_commit   h2agg_commit_columns over `count` columns with no staging; synchronous (the points go to the host).
+ * h2agg_columns_sigmas   h2agg_permutation_sigmas with the two outputs in stores: the Lagrange columns to columns lfirst ..
+ *   lfirst + m - 1 of dst_lagrange, the coefficient columns to cfirst .. of dst_coeff.  Either handle may be 0 (that output
+ *   is not wanted), not both; the two ranges must not overlap.  The mapping comes from host memory.  Synchronous up to the
+ *   device's verdict on the mapping: an invalid mapping is H2AGG_ERR_INVALID from the call and leaves both stores unchanged
+ *   (the columns are made in work memory and reach the stores by a device copy queued behind the verdict).
+ * h2agg_columns_witness_check  h2agg_witness_check with the three slabs in stores: the key's num_advice columns from afirst
+ *   of `advice`, its fixed columns from ffirst of `fixed`, its instance columns from ifirst of `instance`; a handle is not
+ *   looked at where the key has no column of the kind.  mapping, challenges, theta and the report are host memory, as there;
+ *   the report's layout is unchanged.  Synchronous.
+ * h2agg_columns_shplonk_begin  h2agg_kzg_shplonk_begin over columns first .. first + npoly - 1 of a store, k the store's.
+ *   Returns the same object: h2agg_kzg_shplonk_finish and _destroy are the existing ones.  The object's own slab is filled by
+ *   a device copy of the store's columns inside the call, so the store may be overwritten or destroyed before _finish.
+ *
+ * Refusals common to all, H2AGG_ERR_INVALID with the context usable and no output written: an unknown or destroyed handle;
+ * first + count (npoly, m, the key's column count) beyond the store's m, or count == 0; a store whose k is not the call's, the
+ * other store's or the key's; m == 0 or k > 24 at create; a null host buffer.  A slab whose byte size does not fit size_t:
+ * H2AGG_ERR_NOMEM without an allocation; a failed allocation: H2AGG_ERR_NOMEM.  The context stays usable after each. */
+int h2agg_columns_create(h2agg_ctx* ctx, size_t m, unsigned k, uint64_t* handle_out);
+int h2agg_columns_destroy(h2agg_ctx* ctx, uint64_t handle);
+int h2agg_columns_info(h2agg_ctx* ctx, uint64_t handle, size_t* m_out, unsigned* k_out);
+int h2agg_columns_write(h2agg_ctx* ctx, uint64_t handle, size_t first, size_t count, const uint8_t* host);
+int h2agg_columns_read(h2agg_ctx* ctx, uint64_t handle, size_t first, size_t count, uint8_t* host);
+int h2agg_columns_ptr(h2agg_ctx* ctx, uint64_t handle, size_t first, void** d_ptr_out);
+int h2agg_columns_move(h2agg_ctx* ctx, uint64_t src, size_t sfirst, uint64_t dst, size_t dfirst, size_t count, int32_t rotation);
+int h2agg_columns_fft(h2agg_ctx* ctx, uint64_t src, size_t sfirst, uint64_t dst, size_t dfirst, size_t count, int inverse,
+                      const uint8_t shift[32]);
+int h2agg_columns_commit(h2agg_ctx* ctx, uint64_t bases_handle, uint64_t src, size_t first, size_t count, uint8_t* out_aff);
+int h2agg_columns_sigmas(h2agg_ctx* ctx, const uint32_t* mapping, size_t m, unsigned k, size_t usable, const uint8_t delta[32],
+                         uint64_t dst_lagrange, size_t lfirst, uint64_t dst_coeff, size_t cfirst);
+int h2agg_columns_witness_check(h2agg_ctx* ctx, const h2agg_vk* vk, unsigned what, uint64_t advice, size_t afirst, uint64_t fixed,
+                                size_t ffirst, uint64_t instance, size_t ifirst, const uint8_t* challenges, const uint8_t theta[32],
+                                const uint32_t* mapping, size_t max_rows, uint32_t* counts, uint32_t* first_rows, uint32_t* rows,
+                                uint64_t* total);
+int h2agg_columns_shplonk_begin(h2agg_ctx* ctx, uint64_t g_handle, uint64_t src, size_t first, size_t npoly, const uint32_t* queries,
+                                size_t nq, const uint8_t* points, size_t npoints, const uint8_t* evals, const uint8_t y[32],
+                                const uint8_t v[32], uint8_t h1_aff[64], h2agg_shplonk** out);
 
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:

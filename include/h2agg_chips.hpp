@@ -294,4 +294,68 @@ inline EvaluationQuerySchema::Evaluated EvaluationQuerySchema::eval() const {
     return e;
 }
 
+// An Fr column store (include/h2agg.h "Fr column stores"): a slab [m][2^k] of canonical scalars in device memory that the
+// context owns.  RAII over h2agg_columns_create / _destroy; move-only; must not outlive its Gpu.  Columns go in and out as
+// 32 * 2^k bytes each; the resident forms take handle() and column numbers, the _device entry points take ptr().
+class Columns {
+  public:
+    Columns(const Gpu& g, size_t m, unsigned k) : g_(&g), m_(m), k_(k) { g.check(h2agg_columns_create(g.ctx(), m, k, &h_)); }
+    ~Columns() { reset(); }
+    Columns(Columns&& o) noexcept : g_(o.g_), h_(o.h_), m_(o.m_), k_(o.k_) { o.h_ = 0; }
+    Columns& operator=(Columns&& o) noexcept {
+        if (this != &o) {
+            reset();
+            g_ = o.g_, h_ = o.h_, m_ = o.m_, k_ = o.k_;
+            o.h_ = 0;
+        }
+        return *this;
+    }
+    Columns(const Columns&) = delete;
+    Columns& operator=(const Columns&) = delete;
+    uint64_t handle() const { return h_; }
+    size_t m() const { return m_; }
+    unsigned k() const { return k_; }
+    size_t column_bytes() const { return (size_t)32 << k_; }
+    // whole columns from / to host memory; synchronous; an element >= r throws ChipError(H2AGG_ERR_NONCANONICAL)
+    void write(size_t first, const std::vector<uint8_t>& cols) {
+        if (cols.empty() || cols.size() % column_bytes()) throw ChipError(H2AGG_ERR_INVALID, "Columns::write: whole columns only");
+        g_->check(h2agg_columns_write(g_->ctx(), h_, first, cols.size() / column_bytes(), cols.data()));
+    }
+    std::vector<uint8_t> read(size_t first, size_t count) const {
+        std::vector<uint8_t> out(first <= m_ && count >= 1 && count <= m_ - first ? count * column_bytes() : 1);
+        g_->check(h2agg_columns_read(g_->ctx(), h_, first, count, out.data()));
+        return out;
+    }
+    void* ptr(size_t first = 0) const {
+        void* p = nullptr;
+        g_->check(h2agg_columns_ptr(g_->ctx(), h_, first, &p));
+        return p;
+    }
+    // dst[dfirst + j][i] = (*this)[first + j][(i + rotation) mod 2^k]; queued
+    void move_to(size_t first, Columns& dst, size_t dfirst, size_t count, int32_t rotation = 0) const {
+        g_->check(h2agg_columns_move(g_->ctx(), h_, first, dst.h_, dfirst, count, rotation));
+    }
+    // h2agg_fr_fft_batch of `count` columns into dst (dst may be *this with dfirst == first: in place); queued
+    void fft_to(size_t first, Columns& dst, size_t dfirst, size_t count, bool inverse, const Scalar* shift = nullptr) const {
+        g_->check(h2agg_columns_fft(g_->ctx(), h_, first, dst.h_, dfirst, count, inverse ? 1 : 0, shift ? shift->data() : nullptr));
+    }
+    // h2agg_commit_columns of `count` columns against a base table
+    std::vector<Affine> commit(uint64_t bases_handle, size_t first, size_t count) const {
+        std::vector<Affine> out(count >= 1 && count <= m_ ? count : 1);   // (the library refuses the others before it writes)
+        g_->check(h2agg_columns_commit(g_->ctx(), bases_handle, h_, first, count, out[0].data()));
+        out.resize(count);
+        return out;
+    }
+
+  private:
+    void reset() {
+        if (h_) (void)h2agg_columns_destroy(g_->ctx(), h_);
+        h_ = 0;
+    }
+    const Gpu* g_;
+    uint64_t h_ = 0;
+    size_t m_;
+    unsigned k_;
+};
+
 }  // namespace h2agg_chips
