@@ -21,6 +21,13 @@ OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, 
 OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
 FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
 FR_FFT_MAX_K = 24
+# The grid-stride launches whose workgroup cap goes by the CU count, as (workgroups per CU, elements per workgroup): a lane's
+# loop runs a second time above cus * per_cu * per_workgroup elements (cus: the device's count, or the debug key launch_cus)
+LAUNCH_ELEMENTWISE = (8, 256)   # grid_for (csrc/host.inc): the element-wise kernels, BLOCK elements per workgroup
+LAUNCH_SCALAR_MUL = (16, 32)    # h2agg_g1_batch_scalar_mul (csrc/chips_api.inc) and the comb's table (csrc/bases_api.inc): SM_GROUPS
+LAUNCH_SIZE_ORDER = (4, 256)    # k_size_count / k_size_scatter over the buckets of an MSM (csrc/msm_run.inc msm_order)
+LAUNCH_MSM_FIX = (12, 64)       # k_msm_accumulate_fix over the lean accumulation's fix-up list (csrc/msm_run.inc msm_big_kernels)
+LAUNCH_MSM_BIG = (8, 64)        # k_msm_accumulate_big / k_msm_big_combine: one-wave workgroups, one list entry per workgroup
 FR_POLY_CHUNK = 11   # log2 of the coefficients per workgroup of the KZG opening kernels by default (csrc/fr_chunk.hpp)
 FR_SCAN_CHUNK = 11   # log2 of the elements per workgroup of the grand-product kernels by default (csrc/fr_chunk.hpp)
 FR_PROD_MAX_COLUMNS = 16
@@ -511,7 +518,8 @@ class H2Agg:
         out = C.create_string_buffer(96 * max(nseg, 1))
         self._check(self._lib.h2agg_g1_msm_segmented(self._ctx, C.cast(bases_aff, C.c_void_p), C.cast(scalars, C.c_void_p), n,
                                                      seg, nseg, out))
-        return [out.raw[96 * s: 96 * (s + 1)] for s in range(nseg)]
+        raw = out.raw   # (one copy of the buffer, not one per segment)
+        return [raw[96 * s: 96 * (s + 1)] for s in range(nseg)]
 
     def host_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()

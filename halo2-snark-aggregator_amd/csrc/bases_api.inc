@@ -73,7 +73,7 @@ int comb_msm_run(h2agg_ctx* c, Table& t, const uint8_t* d_scalars, size_t n, siz
         if (t.comb) t.comb_retired.push_back(std::move(t.comb));
         t.comb = std::move(fresh);
         size_t grid = (entries + SM_GROUPS - 1) / SM_GROUPS;
-        const size_t cap = (size_t)c->cu_count * 16;
+        const size_t cap = launch_cap(c, 16);
         if (grid > cap) grid = cap;
         hipLaunchKernelGGL(k_comb_table_build, dim3((unsigned)grid), dim3(SM_THREADS), 0, c->stream, t.comb, c->d_flags,
                            (const uint8_t*)t.d, (uint32_t)nb);

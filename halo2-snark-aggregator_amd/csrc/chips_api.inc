@@ -104,7 +104,7 @@ int h2agg_g1_batch_scalar_mul(h2agg_ctx* c, const uint8_t* bases, const uint8_t*
                            (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, n, (uint8_t*)c->out.p, c->d_flags);
     } else {
         size_t groups = (n + SM_GROUPS - 1) / SM_GROUPS;
-        const size_t cap = (size_t)c->cu_count * 16;
+        const size_t cap = launch_cap(c, 16);
         if (groups > cap) groups = cap;
         hipLaunchKernelGGL(k_g1_batch_scalar_mul_w4, dim3((unsigned)groups), dim3(SM_THREADS), 0, c->stream,
                            (const uint8_t*)c->in_a.p, (const uint8_t*)c->in_b.p, n, (uint8_t*)c->out.p, c->d_flags);

@@ -35,6 +35,7 @@ const DebugKey DEBUG_KEYS[] = {
     {"fr_scan_chunk", &h2agg_ctx::dbg_fr_scan_chunk, (int)FR_CHUNK_PER_LOG, (int)FR_CHUNK_LOG, true},
     {"fr_sort_tile", &h2agg_ctx::dbg_fr_sort_tile, (int)LK_TILE_LOG_MIN, (int)LK_TILE_LOG, true},
     {"commit_chunk", &h2agg_ctx::dbg_commit_chunk, 0, INT_MAX},
+    {"launch_cus", &h2agg_ctx::dbg_launch_cus, 1, 1024, true},
 };
 
 bool debug_key_takes(const DebugKey& k, int value) {

@@ -321,6 +321,7 @@ struct h2agg_ctx {
     int dbg_fr_scan_chunk = 0;        // grand products: log2 of the elements per workgroup (0 = FR_CHUNK_LOG)
     int dbg_fr_sort_tile = 0;         // lookup permutation: log2 of the keys per workgroup (0 = LK_TILE_LOG)
     int dbg_commit_chunk = 0;         // h2agg_commit_columns: columns per set of MSM launches (0 = by the work-memory budget)
+    int dbg_launch_cus = 0;           // grid-stride launches capped by the CU count: compute units the cap counts (0 = cu_count)
     int dbg_shard_calls = 0;          // (no key: the all-gathers of the sharded call in progress, counted for shard_fail 3 / 4)
     uint32_t table_word = 0;                // flags[1] as the last finish() read it: the creating call stored an identity base
     int last_lean_variant = -1;             // VAR of the last lean accumulation launched (h2agg_debug_table_identity)

@@ -54,9 +54,17 @@ int dev_alloc(h2agg_ctx* c, DevMem& m, size_t bytes, const char* what) {
     return H2AGG_OK;
 }
 
+// The most workgroups of a grid-stride launch whose cap goes by the device: per_cu for each compute unit (debug key launch_cus:
+// that many units instead, so that a test's few thousand elements walk the stride loop several times).  The key sizes grids
+// and nothing else: routes, plans and stream placement never see it (tests/test_launch_geometry_host.py: cu_count is read
+// here and by h2agg_describe only).
+size_t launch_cap(const h2agg_ctx* c, unsigned per_cu) {
+    return (size_t)(c->dbg_launch_cus ? c->dbg_launch_cus : c->cu_count) * per_cu;
+}
+
 int grid_for(const h2agg_ctx* c, size_t n) {
     size_t blocks = (n + BLOCK - 1) / BLOCK;
-    size_t cap = (size_t)c->cu_count * 8;
+    size_t cap = launch_cap(c, 8);
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     return (int)blocks;

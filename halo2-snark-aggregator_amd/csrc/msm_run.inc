@@ -596,7 +596,7 @@ void msm_order(h2agg_ctx* c, const MsmRoute& r, const MsmWorkspace& w, hipStream
     if (!r.ordered) return;
     StageTimer t(c, ST_ORDER);
     unsigned g = (r.p.NBT + BLOCK * 8 - 1) / (BLOCK * 8);
-    if (g > (unsigned)c->cu_count * 4) g = (unsigned)c->cu_count * 4;
+    if (g > (unsigned)launch_cap(c, 4)) g = (unsigned)launch_cap(c, 4);
     hipLaunchKernelGGL(k_size_count, dim3(g), dim3(BLOCK), 0, st, w.hist, r.p.NBT, w.bin_count);
     hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(BLOCK), 0, st, w.bin_count, (uint32_t)SIZE_BINS, w.bin_start,
                        w.bin_cursor);
@@ -670,11 +670,11 @@ void msm_big_kernels(h2agg_ctx* c, const MsmRoute& r, const MsmWorkspace& w, hip
     const bool chain_open = r.chain == CHAIN_FIRST || r.chain == CHAIN_MID;   // no tail yet
     StageTimer t(c, ST_ACCUM_BIG, bs);
     if (r.lean)   // (grid-stride over a list that is empty but for the one-limb filter's false positives and adversarial inputs)
-        hipLaunchKernelGGL(k_msm_accumulate_fix, dim3((unsigned)std::min<size_t>((size_t)c->cu_count * 12, ((size_t)p.NBT * lpb + 63) / 64)), dim3(64), 0, bs, w.d_bases, w.d_endo_x, w.entries, w.offs,
+        hipLaunchKernelGGL(k_msm_accumulate_fix, dim3((unsigned)std::min<size_t>(launch_cap(c, 12), ((size_t)p.NBT * lpb + 63) / 64)), dim3(64), 0, bs, w.d_bases, w.d_endo_x, w.entries, w.offs,
                            w.hist, lpb, w.acc_out, (const uint32_t*)w.big_count, (const uint32_t*)w.fix_list);
     if (!r.big_possible && lpb == 1) return;
     size_t grid = r.max_slots;
-    const size_t cap = (size_t)c->cu_count * 8;   // one-wave workgroups, grid-stride over the (usually empty) lists
+    const size_t cap = launch_cap(c, 8);   // one-wave workgroups, grid-stride over the (usually empty) lists
     if (grid > cap) grid = cap;
     hipLaunchKernelGGL(k_msm_accumulate_big, dim3((unsigned)grid), dim3(64), 0, bs, w.d_bases, w.d_endo_x, w.entries, w.offs, w.hist,
                        w.acc_out, lpb, w.big_part, w.big_list, w.big_count, resume);

@@ -1160,6 +1160,12 @@ int h2agg_msm_configure_sort(h2agg_ctx* ctx, int sub_bits, int tile);
  *                         then run every multi-tile path, the step loops of both scans and the histogram's stride loop included
  *       "commit_chunk" B  h2agg_commit_columns hands its columns to the batched MSM B at a time (0 = the default: as many as hold
  *                         2^22 scalars): a slab of a few short columns then crosses the chunk boundary
+ *       "launch_cus" u    the grid-stride launches whose workgroup cap goes by the device (u x 8 workgroups of 256 elements for
+ *                         the element-wise kernels, u x 16 of 32 points for h2agg_g1_batch_scalar_mul and the comb's table, u x 4,
+ *                         u x 12 and u x 8 for the MSM's size order, fix-up and over-long-bucket lists) count u compute units,
+ *                         1 .. 1024 (0 = the default: the device's own count).  Sizes grids only: routes, plans, lanes per bucket
+ *                         and stream placement keep the real count.  At u = 1 an input of a few thousand elements walks every
+ *                         such loop several times
  *       "lean_full" 0|1   the bucket accumulation keeps its per-entry identity test and endomorphism select for every table
  *                         and plan (1: A/B and tests of the instantiation for any table)
  *       "pre_big" 0|1     h2agg_bases_precompute takes any explicit width (1: levels through the two-array sort, A/B only)

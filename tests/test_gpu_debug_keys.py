@@ -19,16 +19,16 @@ KEYS = {
     "pcie_slices": 0, "pcie_glv": 0, "pcie_chain": 1, "comb_msm": 1, "plan_cache": 1, "small_sort": 1, "eval_split": 1,
     "lean_acc": 1, "tape_lds": 1, "prewake": 1, "phases": 0, "fr_fft_local": 0, "fr_fft_batch_chunk": 0, "fr_poly_chunk": 0,
     "fr_scan_chunk": 0, "fr_sort_tile": 0, "commit_chunk": 0, "lean_full": 0, "pre_big": 0, "seg_chunk": 0, "seg_c": 0,
-    "shard_fail": 0,
+    "shard_fail": 0, "launch_cus": 0,
 }
 # key -> (lowest, highest) accepted value besides 0
 RANGES = {
     "seg_c": (4, 8), "fr_fft_local": (1, 11), "fr_poly_chunk": (3, 11), "fr_scan_chunk": (3, 11), "fr_sort_tile": (4, 11),
-    "fr_fft_batch_chunk": (0, INT_MAX), "commit_chunk": (0, INT_MAX),
+    "fr_fft_batch_chunk": (0, INT_MAX), "commit_chunk": (0, INT_MAX), "launch_cus": (1, 1024),
 }
 REFUSED = [("seg_c", 3), ("seg_c", 9), ("fr_fft_local", -1), ("fr_fft_local", 12), ("fr_poly_chunk", 2), ("fr_poly_chunk", 12),
            ("fr_scan_chunk", 2), ("fr_scan_chunk", 12), ("fr_sort_tile", 3), ("fr_sort_tile", 12), ("fr_fft_batch_chunk", -1),
-           ("commit_chunk", -1)]
+           ("commit_chunk", -1), ("launch_cus", -1), ("launch_cus", 1025)]
 
 
 def header_keys():
@@ -84,6 +84,8 @@ def test_ranged_keys_are_refused_outside_their_range(pkg, own):
         own.debug_configure("fr_poly_chunk", 12)
     with pytest.raises(pkg.H2AggError, match="commit_chunk must be >= 0"):
         own.debug_configure("commit_chunk", -1)
+    with pytest.raises(pkg.H2AggError, match="launch_cus must be 0 or 1 .. 1024"):
+        own.debug_configure("launch_cus", 1025)
 
 
 def test_ranged_keys_are_accepted_at_both_ends_and_at_zero(own):
