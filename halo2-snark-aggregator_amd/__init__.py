@@ -21,6 +21,7 @@ OK, ERR_INVALID, ERR_DIV_ZERO, ERR_EMPTY, ERR_HIP, ERR_NONCANONICAL, ERR_NOMEM, 
 OP_ADD, OP_SUB, OP_MUL, OP_SQR, OP_INV, OP_DIV = range(6)
 FR_FFT_LOCAL = 10    # radix-2 stages h2agg_fr_fft fuses per pass by default (csrc/fr_fft_kernels.hpp)
 FR_FFT_MAX_K = 24
+FR_QUOTIENT_MAX_K = 28  # h2agg_quotient_device: k + e, the extended domain (the two-adicity of Fr); above 2^24 the coset-split ending
 # The grid-stride launches whose workgroup cap goes by the CU count, as (workgroups per CU, elements per workgroup): a lane's
 # loop runs a second time above cus * per_cu * per_workgroup elements (cus: the device's count, or the debug key launch_cus)
 LAUNCH_ELEMENTWISE = (8, 256)   # grid_for (csrc/host.inc): the element-wise kernels, BLOCK elements per workgroup
@@ -205,6 +206,8 @@ def load_library():
         "h2agg_vk_expressions_eval_device": (i32, [ctxp, vp, i32, sz, C.c_uint, vp, vp, vp, u8p, u8p, vp]),
         "h2agg_quotient": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
         "h2agg_quotient_device": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
+        "h2agg_quotient_configure": (i32, [ctxp, i32]),
+        "h2agg_quotient_work_bytes": (i32, [vp, C.POINTER(sz)]),
         "h2agg_permutation_assembly": (i32, [sz, C.c_uint, sz, vp, sz, vp]),
         "h2agg_permutation_sigmas": (i32, [ctxp, vp, sz, C.c_uint, sz, u8p, vp, vp]),
         "h2agg_commit_columns": (i32, [ctxp, u64, vp, sz, C.c_uint, vp]),
@@ -878,7 +881,8 @@ class H2Agg:
                                        (perm_z, nsets, "perm_z"), (lookup_z, nl, "lookup_z"), (lookup_ap, nl, "lookup_ap"),
                                        (lookup_sp, nl, "lookup_sp")))
         if (pieces << k) > (1 << FR_FFT_MAX_K):   # (the library refuses it as well: the extended domain is 2^(k+e) >= pieces * 2^k)
-            raise H2AggError(ERR_INVALID, "quotient: the extended domain must be <= 2^%d" % FR_FFT_MAX_K)
+            raise H2AggError(ERR_INVALID, "quotient: the host-buffer form takes extended domains <= 2^%d (quotient_device: <= 2^%d)"
+                             % (FR_FFT_MAX_K, FR_QUOTIENT_MAX_K))
         out = C.create_string_buffer((32 << k) * pieces)
         self._check(self._lib.h2agg_quotient(self._ctx, vk._vk, *slabs, self._vk_challenges(vk, challenges), theta, beta, gamma, y,
                                              delta, out))
@@ -893,6 +897,19 @@ class H2Agg:
         self._check(self._lib.h2agg_quotient_device(self._ctx, vk._vk, d_advice_ptr, d_fixed_ptr, d_instance_ptr, d_sigma_ptr,
                                                     d_perm_z_ptr, d_lookup_z_ptr, d_lookup_ap_ptr, d_lookup_sp_ptr, challenges,
                                                     theta, beta, gamma, y, delta, d_h_ptr))
+
+    def quotient_configure(self, split: int):
+        """h2agg_quotient_configure: 1 = every quotient of this context takes the coset-split ending (per-coset inverse
+        transforms of size 2^k and k_qe_cross_cosets), 0 = only where the extended domain is above 2^24 (the default)"""
+        self._check(self._lib.h2agg_quotient_configure(self._ctx, int(split)))
+
+    def quotient_work_bytes(self, vk) -> int:
+        """h2agg_quotient_work_bytes: the device work memory a quotient call of this key holds in the context (the coset's value
+        slab, the Lagrange rows, the fold columns, the extended evaluations or the cosets' inverse transforms, the transforms'
+        work array), on the route the key takes by its size; a key the quotient refuses: ERR_INVALID"""
+        out = C.c_size_t()
+        self._check(self._lib.h2agg_quotient_work_bytes(vk._vk, C.byref(out)))
+        return out.value
 
     # ------------------------------------------------------------------ keys
     def permutation_sigmas(self, mapping, m: int, k: int, usable: int, delta: bytes, lagrange: bool = True, coeff: bool = True):

@@ -1,6 +1,7 @@
 // The quotient polynomial h(X), host side (included into h2agg.hip behind lookup.inc: shares the context internals and reads
 // h2agg_vk, which is verifier.inc's; kernels, number forms and bounds in quotient_kernels.hpp, checks in
-// fr_host.inc, staging in host.inc, transforms and power tables in fr_fft.inc): h2agg_vk_expressions_eval[_device], h2agg_quotient[_device].
+// fr_host.inc, staging in host.inc, transforms and power tables in fr_fft.inc): h2agg_vk_expressions_eval[_device],
+// h2agg_quotient[_device], h2agg_quotient_configure, h2agg_quotient_work_bytes.
 // They stand for the evaluation of h(X) in halo2_proofs' create_proof — an unvendored git dependency of the reference, recalled
 // from upstream (DESIGN.md section 2); the yardstick is the definition in include/h2agg.h.  Which expressions h has to satisfy,
 // and in which order, is pinned by halo2-snark-aggregator-api/src/systems/halo2/params.rs:74-224 and vanish.rs:18-72.
@@ -188,15 +189,24 @@ const ph::HFr& qt_zeta() {
 }
 
 // Where every polynomial sits in a coset's value slab [polys][n], and the work memory of a call in elements of 32 bytes:
-// the slab, the coefficients of l_0 / l_last / l_blind, the fold column, a lookup's two theta-folds, the extended evaluations.
+// the slab, the coefficients of l_0 / l_last / l_blind, the fold column, a lookup's two theta-folds, and `ext`: the extended
+// evaluations [n][2^e], or on the split route the per-coset inverse transforms u[2^e][n] (the same size).  fft_work: the bytes
+// of the transforms' work array.  Only the existing route has a transform of size 2^(k + e), so only there the work array (and
+// the twiddle and shift tables, qt_queue) go by k + e.
+constexpr unsigned QT_MAX_K = FR_S;   // k + e: the two-adicity of Fr, 28 (w_ext = fft_omega(k + e) is a host scalar)
 struct QtLayout {
     uint32_t A, F, I, P, sets, L;
     uint32_t fixed0, instance0, sigma0, z0, lz0, lap0, lsp0, l0, polys;
-    size_t lcoef, acc, lin, ltab, ext, total;
+    size_t lcoef, acc, lin, ltab, ext, total, fft_work;
     unsigned e;
+    bool split;
 };
 
-QtLayout qt_layout(const h2agg_vk& vk) {
+// k + e <= 24: one inverse transform of size 2^(k + e) ends the call; above that, or after h2agg_quotient_configure(ctx, 1), the
+// coset-split ending, which transforms nothing larger than 2^k
+bool qt_split_route(unsigned k, unsigned e, int forced) { return forced != 0 || k + e > FFT_MAX_K; }
+
+QtLayout qt_layout(const h2agg_vk& vk, int forced_split) {
     QtLayout l;
     l.A = vk.num_advice;
     l.F = (uint32_t)qe_nfixed(vk);
@@ -222,7 +232,17 @@ QtLayout qt_layout(const h2agg_vk& vk) {
     l.ltab = l.lin + n;
     l.ext = l.ltab + n;
     l.total = l.ext + (n << l.e);
+    l.split = qt_split_route(vk.k, l.e, forced_split);
+    l.fft_work = fr_fft_batch_work_bytes(l.polys, vk.k);
+    if (!l.split) l.fft_work = std::max(l.fft_work, (size_t)32 << (vk.k + l.e));
     return l;
+}
+
+// what both h2agg_quotient* and h2agg_quotient_work_bytes refuse by the key's shape alone; null: the key is taken
+const char* qt_shape_refusal(const h2agg_vk& vk, const QtLayout& l) {
+    if (vk.k > FFT_MAX_K || vk.k + l.e > QT_MAX_K) return "the extended domain 2^(k + e) must be <= 2^28, and k <= 24";
+    if (l.P && vk.degree < 3) return "permutation columns need degree >= 3";
+    return nullptr;
 }
 
 struct QtScalars {
@@ -237,9 +257,8 @@ struct QtSlabs {
 int qt_check(h2agg_ctx* c, const h2agg_vk* vk, const QtSlabs& s, const uint8_t* challenges, const uint8_t* theta, const uint8_t* beta,
              const uint8_t* gamma, const uint8_t* y, const uint8_t* delta, const void* h, QtLayout* l, QtScalars* sc) {
     if (!vk) return fail(c, H2AGG_ERR_INVALID, "null verifying key");
-    *l = qt_layout(*vk);
-    if (vk->k + l->e > FFT_MAX_K) return fail(c, H2AGG_ERR_INVALID, "the extended domain 2^(k + e) must be <= 2^24");
-    if (l->P && vk->degree < 3) return fail(c, H2AGG_ERR_INVALID, "permutation columns need degree >= 3");
+    *l = qt_layout(*vk, c->cfg_quotient_split);
+    if (const char* why = qt_shape_refusal(*vk, *l)) return fail(c, H2AGG_ERR_INVALID, why);
     if ((l->A && !s.advice) || (l->F && !s.fixed) || (l->I && !s.instance) || (l->P && (!s.sigma || !s.perm_z)) ||
         (l->L && (!s.lookup_z || !s.lookup_ap || !s.lookup_sp)) || !theta || !beta || !gamma || !y || !delta || !h)
         return fail(c, H2AGG_ERR_INVALID, "null buffer");
@@ -278,6 +297,9 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     }
     const size_t cols_at = prog_words;
     prog_words += l.P;
+    const uint32_t pieces = vk.degree - 1;
+    const size_t cross_at = prog_words;   // the split ending's constants, behind the permutation columns' places
+    if (l.split) prog_words += 8 * (size_t)pieces * cosets;
     const size_t m = progs[0].m + (l.sets ? 2 * (size_t)l.sets + 1 : 0) + 5 * (size_t)l.L;
     if (m == 0) {   // no expression at all: N = 0
         HIP_TRY(c, hipMemsetAsync(d_h, 0, col * (vk.degree - 1), c->stream));
@@ -287,11 +309,12 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     TRY(ensure(c, c->qt_work, 32 * l.total));
     TRY(ensure(c, c->qt_prog, 4 * prog_words + 4));
     TRY(ensure(c, c->qt_tab, fr_table_bytes(k)));
-    TRY(ensure(c, c->frfft_work, std::max((size_t)32 << K, fr_fft_batch_work_bytes(l.polys, k))));
-    TRY(ensure(c, c->frfft_shift, fr_table_bytes(K)));
-    if (K) {
-        TRY(fr_fft_ensure_twiddles(c, K, 0));
-        TRY(fr_fft_ensure_twiddles(c, K, 1));
+    const unsigned Kt = l.split ? k : K;   // the largest transform of the call: its work array, shift table and twiddles
+    TRY(ensure(c, c->frfft_work, l.fft_work));
+    TRY(ensure(c, c->frfft_shift, fr_table_bytes(Kt)));
+    if (Kt) {
+        TRY(fr_fft_ensure_twiddles(c, Kt, 0));
+        TRY(fr_fft_ensure_twiddles(c, Kt, 1));
     }
     uint8_t* w = (uint8_t*)c->qt_work.p;
     uint8_t* cos = w;
@@ -315,6 +338,26 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         qe_put_queue(c, cols.data(), cols.size(), d_prog + cols_at);
         fr_table_launch(c, fft_omega(k), k, (uint8_t*)c->qt_tab.p);
     }
+    const ph::HFr w_ext = fft_omega(K), zeta = qt_zeta();
+    if (l.split) {
+        // T[i][c'] R, T[i][c'] = zeta^(-n i) w_E^(-c' i) / (2^e (s_c'^n - 1)): s_c'^n = zeta^n w_E^c', w_E = w_ext^n a primitive
+        // 2^e-th root of unity.  They depend on k, e and degree alone.
+        const ph::HFr zn = hfr_pow(zeta, n), w_E = hfr_pow(w_ext, n), zn_inv = ph::inv(zn), scale = ph::inv(hfr_u64(cosets));
+        std::vector<ph::HFr> w_pow(cosets), per_coset(cosets);   // w_E^-j; 1 / (2^e (s_c'^n - 1))
+        ph::HFr wp = ph::one(), sn = zn;
+        const ph::HFr w_E_inv = ph::inv(w_E);
+        for (uint32_t cs = 0; cs < cosets; ++cs, wp = ph::mul(wp, w_E_inv), sn = ph::mul(sn, w_E)) {
+            w_pow[cs] = wp;
+            per_coset[cs] = ph::mul(scale, ph::inv(ph::sub(sn, ph::one())));   // s^n - 1 != 0: see below
+        }
+        std::vector<uint32_t> tab(8 * (size_t)pieces * cosets);
+        ph::HFr zi = fr_radix();   // zeta^(-n i) R
+        for (uint32_t i = 0; i < pieces; ++i, zi = ph::mul(zi, zn_inv))
+            for (uint32_t cs = 0; cs < cosets; ++cs)
+                hfr_words(ph::mul(ph::mul(zi, w_pow[(uint32_t)(((uint64_t)cs * i) & (cosets - 1u))]), per_coset[cs]),
+                          tab.data() + 8 * ((size_t)i * cosets + cs));
+        qe_put_queue(c, tab.data(), tab.size(), d_prog + cross_at);
+    }
     phases.mark(FORWARD);
     const uint32_t u = (uint32_t)n - vk.blinding_factors - 1u;
     hipLaunchKernelGGL(k_qe_lagrange_rows, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, lcoef, (uint32_t)n, u);
@@ -325,7 +368,6 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     // ---- the sources of the slab's columns, in QtLayout's order: one transform launch per pass takes them all
     const FrFftSeg src[FR_FFT_SEGS] = {{in.advice, l.A},    {in.fixed, l.F},     {in.instance, l.I},  {in.sigma, l.P}, {in.perm_z, l.sets},
                                        {in.lookup_z, l.L},  {in.lookup_ap, l.L}, {in.lookup_sp, l.L}, {lcoef, 3}};
-    const ph::HFr w_ext = fft_omega(K), zeta = qt_zeta();
     const dim3 rows((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
     ph::HFr s = zeta;
     for (uint32_t cs = 0; cs < cosets; ++cs, s = ph::mul(s, w_ext)) {
@@ -385,13 +427,38 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
             acc_in = acc;
         }
         // s^n - 1 != 0: s = zeta w_ext^c' is outside the domain of n-th roots (zeta^n is a primitive cube root of unity)
+        if (l.split) {
+            // row c' of u = the size-n inverse transform of the fold column at shift s; the division by s^n - 1 is a scalar
+            // per coset and waits in the constants of k_qe_cross_cosets
+            phases.mark(INVERSE);
+            TRY(fr_fft_queue(c, acc, k, 1, &s, ext + cs * col));
+            continue;
+        }
         QeScalar inv;
         hfr_words(ph::mul(ph::inv(ph::sub(hfr_pow(s, n), ph::one())), fr_radix()), inv.w);
         hipLaunchKernelGGL(k_qe_store_extended, rows, block, 0, c->stream, (const uint8_t*)acc, inv, (uint32_t)n, (uint32_t)l.e, cs, ext);
     }
     phases.mark(INVERSE);
-    TRY(fr_fft_queue(c, ext, K, 1, &zeta, ext));
-    HIP_TRY(c, hipMemcpyAsync(d_h, ext, col * (vk.degree - 1), hipMemcpyDeviceToDevice, c->stream));
+    if (l.split) {
+        QeCrossArgs a;
+        a.u = ext;
+        a.tab = d_prog + cross_at;
+        a.h = d_h;
+        a.n = (uint32_t)n;
+        a.cosets = cosets;
+        a.pieces = pieces;
+        a.first = 0;
+        const uint32_t full = pieces / QX_PIECES, rest = pieces % QX_PIECES;   // groups of QX_PIECES, then one smaller group
+        if (full) hipLaunchKernelGGL(k_qe_cross_cosets<QX_PIECES>, dim3(rows.x, full), block, 0, c->stream, a);
+        a.first = full * QX_PIECES;
+        static_assert(QX_PIECES == 4, "one case per smaller group");
+        if (rest == 1) hipLaunchKernelGGL(k_qe_cross_cosets<1>, dim3(rows.x, 1), block, 0, c->stream, a);
+        if (rest == 2) hipLaunchKernelGGL(k_qe_cross_cosets<2>, dim3(rows.x, 1), block, 0, c->stream, a);
+        if (rest == 3) hipLaunchKernelGGL(k_qe_cross_cosets<3>, dim3(rows.x, 1), block, 0, c->stream, a);
+    } else {
+        TRY(fr_fft_queue(c, ext, K, 1, &zeta, ext));
+        HIP_TRY(c, hipMemcpyAsync(d_h, ext, col * pieces, hipMemcpyDeviceToDevice, c->stream));
+    }
     phases.mark(PhaseClock::END);
     HIP_TRY(c, hipGetLastError());
     static const char* const names[PHASES] = {"forward", "gates", "permutation", "lookups", "inverse"};
@@ -460,6 +527,9 @@ int h2agg_quotient(h2agg_ctx* c, const h2agg_vk* vk, const uint8_t* advice, cons
     QtLayout l;
     QtScalars sc;
     TRY(qt_check(c, vk, s, challenges, theta, beta, gamma, y, delta, h, &l, &sc));
+    // the host form stages every slab whole: it keeps the bound it had (the resident form takes the larger keys)
+    if (vk->k + l.e > FFT_MAX_K)
+        return fail(c, H2AGG_ERR_INVALID, "the host-buffer form takes extended domains 2^(k + e) <= 2^24 (h2agg_quotient_device: <= 2^28)");
     const size_t col = (size_t)32 << vk->k;
     const uint8_t* host[8] = {advice, fixed, instance, sigma, perm_z, lookup_z, lookup_ap, lookup_sp};
     const size_t count[8] = {l.A, l.F, l.I, l.P, l.sets, l.L, l.L, l.L};
@@ -474,6 +544,22 @@ int h2agg_quotient(h2agg_ctx* c, const h2agg_vk* vk, const uint8_t* advice, cons
     const QtSlabs ds = {d + at[0], d + at[1], d + at[2], d + at[3], d + at[4], d + at[5], d + at[6], d + at[7]};
     TRY(qt_queue(c, *vk, l, sc, ds, (uint8_t*)c->out.p));
     return stage_out(c, h, c->out.p, out_bytes);
+} API_CATCH
+
+int h2agg_quotient_configure(h2agg_ctx* c, int split) try {
+    if (!c) return H2AGG_ERR_INVALID;
+    if (split != 0 && split != 1) return fail(c, H2AGG_ERR_INVALID, "h2agg_quotient_configure: split must be 0 (by size) or 1 (always)");
+    c->cfg_quotient_split = split;
+    return H2AGG_OK;
+} API_CATCH
+
+// no context: the route is the rule's (h2agg_quotient_configure belongs to a context)
+int h2agg_quotient_work_bytes(const h2agg_vk* vk, size_t* bytes_out) try {
+    if (!vk || !bytes_out) return H2AGG_ERR_INVALID;
+    const QtLayout l = qt_layout(*vk, 0);
+    if (qt_shape_refusal(*vk, l)) return H2AGG_ERR_INVALID;
+    *bytes_out = 32 * l.total + l.fft_work;
+    return H2AGG_OK;
 } API_CATCH
 
 }  // extern "C"

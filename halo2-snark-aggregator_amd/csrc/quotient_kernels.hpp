@@ -1,6 +1,7 @@
 // The quotient polynomial h(X) over Fr for gfx950: the device side of
 //   h2agg_vk_expressions_eval   the expressions of a verifying key (gates, a lookup's input / table lists) on every row
-//   h2agg_quotient              gates, permutation and lookup identities folded with y on the cosets of the extended domain
+//   h2agg_quotient              gates, permutation and lookup identities folded with y on the cosets of the extended domain;
+//                               above 2^24 the pieces come from k_qe_cross_cosets (the coset-split ending, at the end of this file)
 //   (halo2_proofs' evaluation of h(X) in create_proof: an unvendored git dependency of the reference, recalled — DESIGN.md
 //    section 2; the yardstick is the definition in include/h2agg.h.  WHICH expressions, in which order, is pinned:
 //    halo2-snark-aggregator-api/src/systems/halo2/params.rs:74-224, permutation.rs:54-136, lookup.rs:34-119, vanish.rs:18-72.)
@@ -275,6 +276,48 @@ __global__ void __launch_bounds__(BLOCK) k_qe_store_extended(const uint8_t* __re
     if (i >= n || coset >= (1u << e)) return;
     const Fr v = fp_mul<FrParams>(fp_load<FrParams>(acc + 32 * (size_t)i), fp_unpack<FrParams>(invM.w));   // plain, < 1.01
     fp_store<FrParams>(ext + 32 * ((((size_t)i) << e) | coset), fp_cond_sub<FrParams>(v));
+}
+
+// The coset-split ending (quotient.inc, qt_queue): u[cosets][n] holds, per coset c', the size-n inverse transform at shift
+// s = zeta w_ext^c' of that coset's fold column (plain canonical: the transform's output), NOT yet divided by s^n - 1.  The
+// pieces are a small transform across the coset index, row by row:
+//   h[i][l] = sum_c' u[c'][l] * T[i][c'],   T[i][c'] = zeta^(-n i) w_E^(-c' i) / (2^e (s_c'^n - 1)),   i < pieces <= cosets
+// (the per-coset division is linear, so it rides in the constants).  tab[i][c'] is T[i][c'] R, canonical, eight words, written
+// by k_qe_put.  One thread per row l and per group of LIVE pieces (blockIdx.y): a coset row is read along l by consecutive
+// threads, the constant's address is the same for a whole workgroup, and the LIVE accumulators are a register file walked by
+// fully unrolled loops (LIVE is a template parameter: a run-time count would turn them into an indexed array in scratch).
+// The host launches k_qe_cross_cosets<QX_PIECES> over the full groups and one more instantiation over the rest.
+// Bounds, in units of r: u < 1 times a constant < 1 is < 1.01 and plain; an accumulator < 2 plus that is < 4 and goes through
+// fr_fft_reduce2 (< 2); fp_cond_sub makes the stored value canonical.
+// Indices: l < n; c' < cosets; i0 + g < first + groups * LIVE <= pieces (the host's two launches), so the tab index is
+// < pieces * cosets and the h row < pieces.
+constexpr int QX_PIECES = 4;   // (eight accumulators: the compiler keeps the array in scratch; four stay in registers)
+struct QeCrossArgs {
+    const uint8_t* u;      // [cosets][n]
+    const uint32_t* tab;   // [pieces][cosets][8]
+    uint8_t* h;            // [pieces][n]
+    uint32_t n, cosets, pieces;
+    uint32_t first;        // the launch's first piece: workgroup row y holds pieces first + y LIVE .. first + y LIVE + LIVE - 1
+};
+template <int LIVE>
+__global__ void __launch_bounds__(BLOCK) k_qe_cross_cosets(const QeCrossArgs a) {
+    static_assert(LIVE >= 1 && LIVE <= QX_PIECES, "one instantiation per size of a group");
+    const uint32_t l = blockIdx.x * BLOCK + threadIdx.x, i0 = a.first + blockIdx.y * LIVE;
+    if (l >= a.n || i0 + LIVE > a.pieces) return;
+    Fr acc[LIVE];
+#pragma unroll
+    for (int g = 0; g < LIVE; ++g) acc[g] = Fr::zero();
+#pragma unroll 1
+    for (uint32_t cs = 0; cs < a.cosets; ++cs) {
+        const Fr x = fp_load<FrParams>(a.u + 32 * ((size_t)cs * a.n + l));
+#pragma unroll
+        for (int g = 0; g < LIVE; ++g) {
+            const Fr t = fp_load<FrParams>(a.tab + 8 * ((size_t)(i0 + g) * a.cosets + cs));
+            acc[g] = fr_fft_reduce2(fp_add<FrParams>(acc[g], fp_mul<FrParams>(x, t)));
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < LIVE; ++g) fp_store<FrParams>(a.h + 32 * ((size_t)(i0 + g) * a.n + l), fp_cond_sub<FrParams>(acc[g]));
 }
 
 }  // namespace h2agg

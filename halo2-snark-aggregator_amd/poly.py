@@ -371,6 +371,11 @@ def quotient_pieces(eng, vk, advice, fixed, instance, sigma, perm_z, lookup_z, l
     return [out[at:at + (32 << k)] for at in range(0, len(out), 32 << k)]
 
 
+def quotient_work_bytes(eng, vk) -> int:
+    """the device work memory a quotient_pieces call of this key holds in the context, in bytes (include/h2agg.h)"""
+    return eng.quotient_work_bytes(vk)
+
+
 def commit_quotient(eng, g_handle: int, pieces):
     """the commitments of h's pieces against the monomial table (ParamsKZG.g), in order: commit_coeff of each, as 96-byte
     Jacobian points (the h commitments a proof carries, vanish.rs:18-72).  (Not the slab call: that one answers canonical

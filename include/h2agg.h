@@ -865,10 +865,27 @@ int h2agg_fr_columns_compress_device(h2agg_ctx* ctx, const void* d_cols, size_t 
  *   H = the unique polynomial of degree < 2^(k+e) with H(s) = N(s) / (s^n - 1) at every s = zeta w_ext^j, j < 2^(k+e);
  *   h_i = the coefficients [i n, (i+1) n) of H, i < degree - 1 (higher ones are dropped, as extended_to_coeff truncates).
  *   For a satisfied circuit H = N / (X^n - 1) exactly; for any other input it is still this one answer.
+ *   Two routes give this one H, byte for byte.  k + e <= 24: the cosets' values are interleaved and one
+ *   inverse transform of size 2^(k+e) ends the call.  24 < k + e <= 28 (28 is the two-adicity of Fr), k <= 24: the coset-split
+ *   ending — every coset's fold goes through an inverse transform of size n at its own shift, and one kernel across the
+ *   cosets turns the 2^e results of a row into its degree - 1 piece values; nothing larger than 2^k is transformed.
+ *   The larger keys are h2agg_quotient_device's: the host-buffer form stages every slab whole and keeps k + e <= 24.
+ *
+ * h2agg_quotient_configure — split = 1: every h2agg_quotient* call of the context takes the coset-split ending, at every size
+ *   (tests and A/B measurements below 2^24; the pieces are the same bytes on either route); split = 0, the default: by the
+ *   rule above.  Any other value: H2AGG_ERR_INVALID, and the setting stays.
  *   Work memory, kept in the context: one coset's values of every polynomial, nine more columns and the
- *   extended evaluations — (the number of input polynomials + 9) n + 2^(k+e) elements, not columns x 2^(k+e) — and the
- *   transform's work array: max(2^(k+e), min((the number of input polynomials + 3) n, 2^23)) elements, so that a coset's
- *   transforms are one launch per pass (h2agg_fr_fft_batch's rule) wherever that fits 256 MiB.
+ *   extended evaluations (split route: the cosets' inverse transforms) — (the number of input polynomials + 9) n + 2^(k+e)
+ *   elements, not columns x 2^(k+e) — and the transform's work array: max(W, min((the number of input polynomials + 3) n,
+ *   2^23)) elements, W = 2^(k+e), on the split route n, so that a coset's transforms are one launch per pass
+ *   (h2agg_fr_fft_batch's rule) wherever that fits 256 MiB.
+ *
+ * h2agg_quotient_work_bytes — that work memory in bytes for this key, 32 x (the two sums above) on the route the key takes by
+ *   the rule above (h2agg_quotient_configure is a context's and is not seen here): what an h2agg_quotient* call will hold in the context beside the caller's columns (at k = 24 with 34
+ *   input polynomials and e = 3: 51 + 1 columns of 512 MiB, 26 GiB).  Not counted: the compiled programs and the power tables
+ *   (under 1 MiB together), the staging buffers of the host form, and the slack of the context's grow-only buffers, which
+ *   allocate one eighth more than they are asked for.  Needs no context and no device.  A null argument, or a key that
+ *   h2agg_quotient refuses by its shape (k > 24, k + e > 28): H2AGG_ERR_INVALID.
  *
  * The plain entry points are synchronous over host buffers (pageable or h2agg_host_alloc); the _device twins take DEVICE
  * memory and are queued on the context's stream with no synchronisation and no read-back (buffer rules: h2agg_fr_fft_device;
@@ -877,7 +894,7 @@ int h2agg_fr_columns_compress_device(h2agg_ctx* ctx, const void* d_cols, size_t 
  * inverse=ms".
  * Refusals, the context stays usable after each: an unknown `which` or j, k different from the key's (or > 24), a list
  * without expressions, a null required buffer, an expression deeper than H2AGG_EXPR_MAX_DEPTH; for the quotient also
- * k + e > 24 and degree < 3 with permutation columns: H2AGG_ERR_INVALID.  A scalar (challenge, fold, theta, beta, gamma, y,
+ * k + e > 28 (h2agg_quotient: > 24), k > 24 and degree < 3 with permutation columns: H2AGG_ERR_INVALID.  A scalar (challenge, fold, theta, beta, gamma, y,
  * delta, a CONST of the key) >= r: H2AGG_ERR_NONCANONICAL from the call.  A column element >= r: H2AGG_ERR_NONCANONICAL through
  * the context's device status — from the call for the synchronous entry points, at h2agg_synchronize (or the next
  * synchronous entry point), once, for the _device twins; outputs are then unspecified.  Out of memory: H2AGG_ERR_NOMEM. */
@@ -896,6 +913,8 @@ int h2agg_quotient_device(h2agg_ctx* ctx, const h2agg_vk* vk, const void* d_advi
                           const void* d_sigma, const void* d_perm_z, const void* d_lookup_z, const void* d_lookup_ap,
                           const void* d_lookup_sp, const uint8_t* challenges, const uint8_t theta[32], const uint8_t beta[32],
                           const uint8_t gamma[32], const uint8_t y[32], const uint8_t delta[32], void* d_h);
+int h2agg_quotient_configure(h2agg_ctx* ctx, int split);
+int h2agg_quotient_work_bytes(const h2agg_vk* vk, size_t* bytes_out);
 
 /* ---- Keys: sigma columns from copy constraints, and the commitments of a slab of columns ------------------------------------
  * Stand for: permutation::keygen::Assembly (new, copy, build_vk, build_pk) and the commit_lagrange loops of keygen_vk /

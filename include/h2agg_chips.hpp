@@ -358,4 +358,14 @@ class Columns {
     unsigned k_;
 };
 
+// The device work memory an h2agg_quotient* call of this key holds in its context, in bytes (h2agg_quotient_work_bytes): what
+// a prover at k = 23 or 24 plans beside its Columns.  Needs no Gpu.  A key the quotient refuses: ChipError(H2AGG_ERR_INVALID).
+// (The classes above carry no quotient method: the call itself is the C ABI's, over Columns::ptr().)
+inline size_t quotient_work_bytes(const h2agg_vk* vk) {
+    size_t bytes = 0;
+    const int rc = h2agg_quotient_work_bytes(vk, &bytes);
+    if (rc != H2AGG_OK) throw ChipError(rc, "h2agg_quotient_work_bytes: null key, or a key the quotient refuses (k > 24, k + e > 28)");
+    return bytes;
+}
+
 }  // namespace h2agg_chips

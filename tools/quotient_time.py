@@ -2,6 +2,7 @@
 """Timing of h2agg_quotient_device: the call, its split by events, and the same transforms issued alone.
 
     python tools/quotient_time.py [--ks 16,18,20] > profiles/quotient.txt
+    python tools/quotient_time.py --routes [--ks 16,18,20] >> profiles/quotient.txt     the two endings of the call, see below
 
 One shape: 8 advice, 4 fixed and 1 instance column, 6 gate polynomials of degree <= 4 over rotations 0, +1 and -1, 8
 permutation columns (four sets of chunk_len = 2), 2 lookups (2 + 2 and 1 + 1 expressions), degree 4: e = 2, four cosets, 34
@@ -21,6 +22,12 @@ brackets.
               2^(k+2), queued through h2agg_fr_fft_device alone (that entry point exists in the parent commit): what of the
               call is not new.  Each of these calls builds its own shift table and is its own set of launches; inside the
               quotient a coset is one batched transform (fr_fft_queue_batch): one table, one launch per pass for all 34.
+
+--routes: the two endings of the call where both are legal (k + 2 <= 24), in one process on one context, alternating: the
+h2agg_quotient_configure at 0 (the values of the four cosets interleaved, one inverse transform of size 2^(k+2)) and at 1
+(per coset one inverse transform of size 2^k at the coset's shift, then k_qe_cross_cosets over the four results: twelve
+products and 224 B per row).  Three rounds; per round and route the call (median of five brackets, key "phases" off) and the
+`inverse` phase of one more call with the key on.  The pieces of the two routes are compared byte for byte first.
 """
 import argparse
 import os
@@ -57,6 +64,7 @@ def shape(k):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="16,18,20")
+    ap.add_argument("--routes", action="store_true", help="the split ending against the default one, alternating")
     args = ap.parse_args()
     import importlib
     import torch
@@ -92,6 +100,9 @@ def main():
 
     sc = [(0x1234567 + 0x1111 * i).to_bytes(32, "little") for i in range(5)]
     print("# %s" % eng.describe())
+    if args.routes:
+        routes(args, eng, verifier, torch, dev, slab, sc, measure)
+        return
     print("# 8 advice, 4 fixed, 1 instance, 6 gate polynomials, 8 permutation columns, 2 lookups, degree 4: 4 cosets, 34 polynomials")
     print("# one call per bracket, median of 5 brackets; times in ms")
     print("#  k    call ms | split: forward    gates  permutation  lookups  inverse | the transforms alone   share of the call")
@@ -130,6 +141,42 @@ def main():
         sys.stdout.flush()
         vk.close()
         del slabs, d_h, d_x
+        torch.cuda.empty_cache()
+
+
+def routes(args, eng, verifier, torch, dev, slab, sc, measure):
+    print("# the two endings of h2agg_quotient_device, alternating in one process (h2agg_quotient_configure 0 / 1); times in ms")
+    print("#  k  round |  default: call   inverse |    split: call   inverse")
+    for k in [int(x) for x in args.ks.split(",") if x]:
+        n = 1 << k
+        vk = verifier.VerifyingKey(eng, verifier.encode_vk(shape(k), lambda p: p))
+        counts = (8, 4, 1, 8, 4, 2, 2, 2)
+        slabs = [slab(c, n, 97 * k + i) for i, c in enumerate(counts)]
+        d_h = [torch.zeros((3 * n, 32), dtype=torch.uint8, device=dev) for _ in range(2)]
+        torch.cuda.synchronize()
+        ptrs = [s.data_ptr() for s in slabs]
+        for route in (0, 1):
+            eng.quotient_configure(route)
+            eng.quotient_device(vk, *ptrs, None, *sc, d_h[route].data_ptr())
+        eng.synchronize()
+        if not torch.equal(d_h[0], d_h[1]):
+            sys.exit("k = %d: the two routes differ" % k)
+        for rnd in range(3):
+            row = []
+            for route in (0, 1):
+                eng.quotient_configure(route)
+                call = lambda: eng.quotient_device(vk, *ptrs, None, *sc, d_h[route].data_ptr())
+                t_call = measure(call)
+                eng.debug_configure("phases", 1)
+                call()
+                split = dict(kv.split("=") for kv in eng.last_phases().split())
+                eng.debug_configure("phases", 0)
+                row += [t_call, float(split.get("inverse", "nan"))]
+            print("%4d  %5d | %14.3f %9.3f | %14.3f %9.3f" % (k, rnd, *row))
+            sys.stdout.flush()
+        eng.quotient_configure(0)
+        vk.close()
+        del slabs, d_h
         torch.cuda.empty_cache()
 
 
