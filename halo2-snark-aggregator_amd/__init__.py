@@ -34,6 +34,7 @@ FR_SCAN_CHUNK = 11   # log2 of the elements per workgroup of the grand-product k
 FR_PROD_MAX_COLUMNS = 16
 FR_SORT_TILE = 11    # log2 of the keys per workgroup of the lookup permutation by default (csrc/lookup_kernels.hpp)
 FR_SORT_TILE_MIN = 4
+LOOKUP_STATUS_NONCANONICAL, LOOKUP_STATUS_NOT_IN_TABLE = 1, 8   # the bits of a lookup batch's status words (include/h2agg.h)
 FR_COMPRESS_MAX_COLUMNS = 1 << 16   # most columns of one fr_columns_compress (the library's limit: csrc/lookup.inc)
 PERM_MAX_COLUMNS = 4096   # H2AGG_PERM_MAX_COLUMNS: most columns of one permutation (csrc/keygen_kernels.hpp)
 EXPR_MAX_DEPTH = 16  # H2AGG_EXPR_MAX_DEPTH: the operand stack of h2agg_vk_expressions_eval / h2agg_quotient (csrc/quotient_kernels.hpp)
@@ -200,6 +201,12 @@ def load_library():
         "h2agg_lookup_product_device": (i32, [ctxp, vp, vp, vp, vp, C.c_uint, sz, u8p, u8p, vp, vp]),
         "h2agg_lookup_permute": (i32, [ctxp, vp, vp, C.c_uint, sz, vp, vp]),
         "h2agg_lookup_permute_device": (i32, [ctxp, vp, vp, C.c_uint, sz, vp, vp]),
+        "h2agg_lookup_batch_permute": (i32, [ctxp, vp, vp, sz, C.c_uint, sz, vp, vp, vp]),
+        "h2agg_lookup_batch_product": (i32, [ctxp, vp, vp, vp, vp, sz, C.c_uint, sz, u8p, u8p, vp, vp]),
+        "h2agg_lookup_store_permute": (i32, [ctxp, u64, sz, u64, sz, sz, sz, u64, sz, u64, sz, vp]),
+        "h2agg_lookup_store_product": (i32, [ctxp, u64, sz, u64, sz, u64, sz, u64, sz, sz, sz, u8p, u8p, u64, sz, vp]),
+        "h2agg_lookup_configure": (i32, [ctxp, sz]),
+        "h2agg_lookup_chunk_rule": (sz, [sz, sz]),
         "h2agg_fr_columns_compress": (i32, [ctxp, vp, sz, C.c_uint, u8p, vp]),
         "h2agg_fr_columns_compress_device": (i32, [ctxp, vp, sz, C.c_uint, u8p, vp]),
         "h2agg_vk_expressions_eval": (i32, [ctxp, vp, i32, sz, C.c_uint, vp, vp, vp, u8p, u8p, vp]),
@@ -804,6 +811,84 @@ class H2Agg:
         """h2agg_lookup_permute_device: columns in device memory, queued on the context's stream (no synchronisation); rows
         from u up of d_ap / d_sp are left alone; d_ap / d_sp must not overlap d_a, d_s or each other"""
         self._check(self._lib.h2agg_lookup_permute_device(self._ctx, d_a_ptr, d_s_ptr, k, u, d_ap_ptr, d_sp_ptr))
+
+    # ------------------------------------------------------------------ lookup argument, batched
+    def lookup_configure(self, batch_chunk: int):
+        """h2agg_lookup_configure: at most batch_chunk lookups per set of launches of a batch (0 = the default rule)"""
+        self._check(self._lib.h2agg_lookup_configure(self._ctx, int(batch_chunk)))
+
+    @staticmethod
+    def lookup_chunk_rule(u: int, batch_chunk: int = 0) -> int:
+        """h2agg_lookup_chunk_rule: the lookups per chunk at u rows under lookup_configure(batch_chunk); host arithmetic"""
+        return int(load_library().h2agg_lookup_chunk_rule(int(u), int(batch_chunk)))
+
+    @staticmethod
+    def _batch_slab(x, count: int, k: int, what: str):
+        if 0 <= k <= FR_FFT_MAX_K and 1 <= count <= 65535:
+            _need(x, (32 << k) * count, what)
+
+    def lookup_batch_permute(self, a: bytes, s: bytes, count: int, k: int, u: int, ap=None, sp=None):
+        """h2agg_lookup_batch_permute: slabs [count][2^k] -> (ap, sp, status): slabs whose rows from u up are what ap / sp (the
+        caller's pre-filled slabs, or zero) held, and the per-lookup status words.  Raises the error of the lowest-numbered
+        failing lookup, with the slabs and the words in the exception's .partial"""
+        for x, what in ((a, "a"), (s, "s")):
+            self._batch_slab(x, count, k, what)
+        size = (32 << k) * count if 0 <= k <= FR_FFT_MAX_K and 1 <= count <= 65535 else 32
+        outs = []
+        for x, what in ((ap, "ap"), (sp, "sp")):
+            if x is not None:
+                _need(x, size, what)
+            outs.append(C.create_string_buffer(bytes(x), size) if x is not None else C.create_string_buffer(size))
+        status = (C.c_uint32 * max(count, 1))()
+        rc = self._lib.h2agg_lookup_batch_permute(self._ctx, self._hostptr(a), self._hostptr(s), count, k, u, outs[0], outs[1],
+                                                  status)
+        result = (outs[0].raw, outs[1].raw, list(status)[:max(count, 0)])
+        try:
+            self._check(rc)
+        except H2AggError as e:
+            e.partial = result
+            raise
+        return result
+
+    def lookup_batch_product(self, a: bytes, s: bytes, ap: bytes, sp: bytes, count: int, k: int, u: int, beta: bytes,
+                             gamma: bytes, z=None):
+        """h2agg_lookup_batch_product: slabs [count][2^k] -> (z, last): the slab whose rows from u + 1 up are what z (the
+        caller's pre-filled slab, or zero) held, and the list of z[j][u]"""
+        self._need32(beta=beta, gamma=gamma)
+        for x, what in ((a, "a"), (s, "s"), (ap, "ap"), (sp, "sp")):
+            self._batch_slab(x, count, k, what)
+        size = (32 << k) * count if 0 <= k <= FR_FFT_MAX_K and 1 <= count <= 65535 else 32
+        if z is not None:
+            _need(z, size, "z")
+        out = C.create_string_buffer(bytes(z), size) if z is not None else C.create_string_buffer(size)
+        last = C.create_string_buffer(32 * max(count, 1))
+        self._check(self._lib.h2agg_lookup_batch_product(self._ctx, self._hostptr(a), self._hostptr(s), self._hostptr(ap),
+                                                         self._hostptr(sp), count, k, u, beta, gamma, out, last))
+        return out.raw, [last.raw[32 * j:32 * j + 32] for j in range(count)]
+
+    def lookup_store_permute(self, a: int, afirst: int, s: int, sfirst: int, count: int, u: int, ap: int, apfirst: int, sp: int,
+                             spfirst: int, want_status: bool = True):
+        """h2agg_lookup_store_permute over column-store handles.  want_status: synchronous, -> the status words (an error is
+        raised with them in .partial); else queued with no synchronisation -> None"""
+        status = (C.c_uint32 * max(count, 1))() if want_status else None
+        rc = self._lib.h2agg_lookup_store_permute(self._ctx, a, afirst, s, sfirst, count, u, ap, apfirst, sp, spfirst, status)
+        result = list(status)[:max(count, 0)] if want_status else None
+        try:
+            self._check(rc)
+        except H2AggError as e:
+            e.partial = result
+            raise
+        return result
+
+    def lookup_store_product(self, a: int, afirst: int, s: int, sfirst: int, ap: int, apfirst: int, sp: int, spfirst: int,
+                             count: int, u: int, beta: bytes, gamma: bytes, z: int, zfirst: int, want_last: bool = True):
+        """h2agg_lookup_store_product over column-store handles.  want_last: synchronous, -> the list of z[j][u]; else queued
+        with no synchronisation -> None"""
+        self._need32(beta=beta, gamma=gamma)
+        last = C.create_string_buffer(32 * max(count, 1)) if want_last else None
+        self._check(self._lib.h2agg_lookup_store_product(self._ctx, a, afirst, s, sfirst, ap, apfirst, sp, spfirst, count, u, beta,
+                                                         gamma, z, zfirst, last))
+        return [last.raw[32 * j:32 * j + 32] for j in range(count)] if want_last else None
 
     def fr_columns_compress(self, cols: bytes, m: int, k: int, theta: bytes) -> bytes:
         """h2agg_fr_columns_compress: a slab [m][2^k] -> out[i] = sum_j theta^(m - 1 - j) cols[j][i], 2^k elements"""

@@ -1,12 +1,14 @@
 // Fr column stores, host side (included into h2agg.hip behind witness.inc: shares the context internals and every family's
 // queue functions; the two kernels in columns_kernels.hpp, checks in fr_host.inc, staging and allocation in host.inc):
 // h2agg_columns_create / _destroy / _info / _write / _read / _ptr / _move, and the resident forms of the families that take
-// whole slabs — h2agg_columns_fft, _commit, _sigmas, _witness_check, _shplonk_begin.  A store is a slab [m][2^k] of canonical
+// whole slabs — h2agg_columns_fft, _commit, _sigmas, _witness_check, _shplonk_begin, and of the lookup batches (lookup.inc) —
+// h2agg_lookup_store_permute, h2agg_lookup_store_product.  A store is a slab [m][2^k] of canonical
 // Fr in device memory that the context owns behind a handle, as it owns a base table (DESIGN.md 5.20); the yardstick is the
 // definition in include/h2agg.h: a resident form answers byte for byte what its host-buffer family answers.
 //
 // Every resident form is a front over the function its family already runs behind its staging: fr_fft_queue_batch,
-// commit_columns_run, perm_sigma_queue, wc_check / wc_queue / wc_report_out, shplonk_begin.  Nothing here computes.
+// commit_columns_run, perm_sigma_queue, wc_check / wc_queue / wc_report_out, shplonk_begin, lk_batch_permute_queue /
+// lk_batch_product_queue.  Nothing here computes.
 
 namespace {
 
@@ -270,6 +272,81 @@ int h2agg_columns_witness_check(h2agg_ctx* c, const h2agg_vk* vk, unsigned what,
     TRY(clear_flags(c));
     TRY(wc_queue(c, *vk, call, d_advice, d_fixed, d_instance, c->in_b.p));
     return wc_report_out(c, l, max_rows, counts, first_rows, rows, total);
+} API_CATCH
+
+// The lookup batches over stores (lookup.inc has the host-slab forms and the chunk loop).  With a host block to fill (status /
+// last) the call is synchronous; without, it is queued and reports through the context's device status.
+int h2agg_lookup_store_permute(h2agg_ctx* c, uint64_t a, size_t afirst, uint64_t s, size_t sfirst, size_t count, size_t u,
+                               uint64_t ap, size_t apfirst, uint64_t sp, size_t spfirst, uint32_t* status) try {
+    TRY(bind(c));
+    if (c->dbg_phases) c->last_phases.clear();
+    if (count == 0 || count > LK_MAX_LOOKUPS) return fail(c, H2AGG_ERR_INVALID, "count must be 1 .. 65535");
+    const uint64_t h[4] = {a, s, ap, sp};
+    const size_t first[4] = {afirst, sfirst, apfirst, spfirst};
+    ColumnStore* st[4] = {};
+    uint8_t* d[4] = {};
+    for (int i = 0; i < 4; ++i) {
+        TRY(store_range(c, h[i], first[i], count, &st[i], &d[i]));
+        if (st[i]->k != st[0]->k) return fail(c, H2AGG_ERR_INVALID, "lookup_store_permute: the stores differ in k");
+    }
+    TRY(prod_check_ku(c, st[0]->k, u));
+    for (int o = 2; o < 4; ++o)
+        for (int i = 0; i < o; ++i)
+            if (st[o] == st[i] && ranges_meet(first[o], first[i], count))
+                return fail(c, H2AGG_ERR_INVALID, "lookup_store_permute: ap / sp must not overlap a, s or each other");
+    if (u == 0) {
+        if (status) memset(status, 0, 4 * count);
+        return H2AGG_OK;
+    }
+    enum { SORT, RANK, PHASES };   // of h2agg_last_phases (debug key phases)
+    static const char* const names[PHASES] = {"sort", "rank"};
+    PhaseClock phases(c);
+    uint32_t* d_status = nullptr;
+    if (status) {
+        TRY(ensure(c, c->lk_status, 4 * count));
+        d_status = (uint32_t*)c->lk_status.p;
+        TRY(clear_flags(c));
+    }
+    TRY(lk_batch_permute_queue(c, d[0], d[1], st[0]->col(), count, u, d[2], d[3], d_status, &phases, SORT));
+    phases.mark(PhaseClock::END);
+    const int rc = status ? lk_batch_finish(c, d_status, count, status) : H2AGG_OK;
+    phases.report(names, PHASES);   // (with the debug key only: waits for the last event)
+    return rc;
+} API_CATCH
+
+int h2agg_lookup_store_product(h2agg_ctx* c, uint64_t a, size_t afirst, uint64_t s, size_t sfirst, uint64_t ap, size_t apfirst,
+                               uint64_t sp, size_t spfirst, size_t count, size_t u, const uint8_t beta[32], const uint8_t gamma[32],
+                               uint64_t z, size_t zfirst, uint8_t* last) try {
+    TRY(bind(c));
+    if (c->dbg_phases) c->last_phases.clear();
+    if (count == 0 || count > LK_MAX_LOOKUPS) return fail(c, H2AGG_ERR_INVALID, "count must be 1 .. 65535");
+    const uint64_t h[5] = {a, s, ap, sp, z};
+    const size_t first[5] = {afirst, sfirst, apfirst, spfirst, zfirst};
+    ColumnStore* st[5] = {};
+    uint8_t* d[5] = {};
+    for (int i = 0; i < 5; ++i) {
+        TRY(store_range(c, h[i], first[i], count, &st[i], &d[i]));
+        if (st[i]->k != st[0]->k) return fail(c, H2AGG_ERR_INVALID, "lookup_store_product: the stores differ in k");
+    }
+    ph::HFr bf, gf;
+    TRY(lookup_check(c, st[0]->k, u, beta, gamma, &bf, &gf));
+    for (int i = 0; i < 4; ++i)
+        if (st[4] == st[i] && ranges_meet(first[4], first[i], count))
+            return fail(c, H2AGG_ERR_INVALID, "lookup_store_product: z must not overlap a, s, ap or sp");
+    enum { TERMS, INVERT, SCAN, PHASES };   // of h2agg_last_phases (debug key phases)
+    static const char* const names[PHASES] = {"terms", "invert", "scan"};
+    PhaseClock phases(c);
+    const size_t col = st[0]->col();
+    if (last) TRY(clear_flags(c));
+    TRY(lk_batch_product_queue(c, d[0], d[1], d[2], d[3], col, count, u, bf, gf, d[4], col, &phases, TERMS));
+    phases.mark(PhaseClock::END);
+    int rc = H2AGG_OK;
+    if (last) {
+        HIP_TRY(c, hipMemcpy2DAsync(last, 32, d[4] + 32 * u, col, 32, count, hipMemcpyDeviceToHost, c->stream));
+        rc = finish(c);
+    }
+    phases.report(names, PHASES);   // (with the debug key only: waits for the last event)
+    return rc;
 } API_CATCH
 
 int h2agg_columns_shplonk_begin(h2agg_ctx* c, uint64_t g_handle, uint64_t src, size_t first, size_t npoly, const uint32_t* queries,

@@ -342,8 +342,8 @@ struct h2agg_ctx {
     // h2agg_fr_grand_product), the chunk products of every level above the elements, the two-level table of w^i
     DevBuf prod_num, prod_den, prod_lvl, prod_tab;
     // lookup permutation (csrc/lookup.inc): the key buffers, rank columns, count matrix, histograms and plans of a call
-    // (lk_layout), the descriptor of a compression
-    DevBuf lk_work, lk_desc;
+    // (lk_layout), the descriptor of a compression, the status words of a batch (one per lookup)
+    DevBuf lk_work, lk_desc, lk_status;
     // quotient polynomial (csrc/quotient.inc): a coset's value slab with the columns behind it and the extended evaluations
     // (qt_layout), the compiled programs and the permutation columns' places, the two-level table of w^i
     DevBuf qt_work, qt_prog, qt_tab;
@@ -359,6 +359,7 @@ struct h2agg_ctx {
     int cfg_glv = 0;   // 0 = auto, 1 = on, -1 = off
     int cfg_lpb = 0;   // lanes per bucket in the accumulate kernel: 0 = auto, 1 / 2 / 4 / 8 / 16
     int cfg_quotient_split = 0;   // h2agg_quotient_configure: 1 = every quotient takes the coset-split ending (0: only where k + e > 24)
+    size_t cfg_lookup_chunk = 0;   // h2agg_lookup_configure: most lookups per set of launches of a batch (0: by the rows, csrc/lookup.inc)
     bool cfg_no_stage = false, cfg_stage_l1 = false, staged_attr_set = false, cfg_no_dm = false, dm_attr_set = false, r2d_attr_set = false;
 
     // optional overlap of the serial tail (k_msm_final) of MSM k with the bulk of MSM k+1

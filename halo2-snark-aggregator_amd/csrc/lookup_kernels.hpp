@@ -39,6 +39,15 @@
 // wave-columns (u > 2^19) or tiles (u > 2^21) and a second stride u > 2^18.  Under the debug key fr_sort_tile (t < 11) all three
 // shrink with the tile — step = hist_lanes = T / 4, at most 2 workgroups — so that inputs of 65 .. 1024 rows walk the step loop
 // of both scans and the stride loop several times (t = 4, u = 65: 5 steps over the count matrix, 2 over the tile sums, 9 strides).
+//
+// Batch.  A launch carries a second grid dimension.  The sort kernels take blockIdx.y as the SORT COLUMN c of a chunk of nb
+// lookups: c < nb is the input column of lookup c, nb + c' the table column of lookup c'; every column has its own histograms,
+// plan, count matrix and pair of work buffers, slabs addressed base + c * stride in size_t (lk_sort_column).  Indices inside a
+// column stay the 32-bit values of one column (< u < 2^24).  Every kernel reads its own column's plan word, so in one launch a
+// column that skips a pass returns beside a column that moves, and each column ends in its own buffer state plan[32].  The
+// rank kernels take blockIdx.y as the LOOKUP b: marks and prefixes are dense [nb][u] / [nb][u + 1], tile sums [nb][tiles].
+// A kernel that raises a status bit also ORs it into status[lookup] where the chunk has such words (null: a single call).
+// A single call is the chunk of one lookup (gridDim.y = 2 for its two sorts, 1 for the rank step).
 #pragma once
 #include "poly_kernels.hpp"
 
@@ -58,13 +67,18 @@ constexpr uint32_t LK_HIST_GRID = 1024;              // most workgroups of k_lk_
 static_assert(LK_THREADS == 64 * LK_WAVES && LK_THREADS == (int)LK_BINS, "one thread per bin, four waves of 64");
 
 struct FrSortArgs {
-    const uint8_t* in;       // [u] the caller's column: state 0, read only
-    uint8_t* w0;             // [u] work buffers: states 1 and 2
+    const uint8_t* in;       // [u] the callers' columns: state 0, read only.  Sort column c < nb: in + c in_stride;
+    const uint8_t* in2;      //     c >= nb: in2 + (c - nb) in_stride
+    uint8_t* w0;             // [u] work buffers: states 1 and 2; column c at + c key_stride
     uint8_t* w1;
-    uint32_t* hist;          // [32][256] byte histograms of the keys (zeroed in front of k_lk_digit_hist)
-    uint32_t* plan;          // [33] (file header)
-    uint32_t* counts;        // [256][ncols]
+    uint32_t* hist;          // [32][256] byte histograms of the keys (zeroed in front of k_lk_digit_hist); column c at + c 8192
+    uint32_t* plan;          // [33] (file header); column c at + c 33
+    uint32_t* counts;        // [256][ncols]; column c at + c 256 ncols
     uint32_t* flags;
+    uint32_t* status;        // [nb] one word per lookup, or null
+    size_t in_stride;        // bytes between the callers' columns
+    size_t key_stride;       // bytes between the work buffers of two sort columns (>= 32 u)
+    uint32_t nb;             // lookups of the chunk: gridDim.y <= 2 nb sort columns
     uint32_t u;              // keys, 1 .. 2^24 - 1
     uint32_t t;              // log2 T, LK_TILE_LOG_MIN .. LK_TILE_LOG
     uint32_t ncols;          // 4 * ceil(u / T)
@@ -78,6 +92,23 @@ FP_INLINE const uint8_t* lk_state_buf(const uint8_t* in, const uint8_t* w0, cons
 // byte p of key i: one 4-byte load (no dynamically indexed register array).  i < u.
 FP_INLINE uint32_t lk_digit(const uint8_t* keys, uint32_t i, uint32_t p) {
     return (reinterpret_cast<const uint32_t*>(keys)[8 * (size_t)i + (p >> 2)] >> (8 * (p & 3))) & 0xffu;
+}
+// The arguments of sort column blockIdx.y: every pointer moved to the column's own slab (file header, "Batch"); status moved to
+// the word of the column's lookup.  c < 2 nb <= 2048, strides in size_t.
+FP_INLINE FrSortArgs lk_sort_column(FrSortArgs a) {
+    const uint32_t c = blockIdx.y, b = c < a.nb ? c : c - a.nb;
+    a.in = (c < a.nb ? a.in : a.in2) + (size_t)b * a.in_stride;
+    a.w0 += (size_t)c * a.key_stride;
+    a.w1 += (size_t)c * a.key_stride;
+    a.hist += (size_t)c * (LK_PASSES * LK_BINS);
+    a.plan += (size_t)c * LK_PLAN_WORDS;
+    a.counts += (size_t)c * LK_BINS * a.ncols;
+    if (a.status) a.status += b;
+    return a;
+}
+FP_INLINE void lk_raise(uint32_t* flags, uint32_t* status, uint32_t bit) {
+    atomicOr(flags, bit);
+    if (status) atomicOr(status, bit);
 }
 FP_INLINE void u256_store(void* p, const U256& v) {
     uint4* q = reinterpret_cast<uint4*>(p);
@@ -130,7 +161,8 @@ FP_INLINE uint32_t lk_block_excl_scan(uint32_t v, uint32_t* lds, uint32_t& total
 // b hist_lanes + x + j gridDim.x hist_lanes, j = 0, 1, .. (every key below u exactly once; i < u < 2^24 and the stride is at
 // most 2^18: no overflow); the other threads only help with the LDS.  LDS and hist indices 256 p + d < 8192.  Reads in, adds to
 // hist (zeroed by the host's memset on the same stream).
-__global__ void __launch_bounds__(LK_THREADS) k_lk_digit_hist(const FrSortArgs a) {
+__global__ void __launch_bounds__(LK_THREADS) k_lk_digit_hist(const FrSortArgs a0) {
+    const FrSortArgs a = lk_sort_column(a0);
     __shared__ uint32_t h[LK_PASSES * LK_BINS];
     for (uint32_t j = threadIdx.x; j < LK_PASSES * LK_BINS; j += LK_THREADS) h[j] = 0;
     __syncthreads();
@@ -145,7 +177,7 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_digit_hist(const FrSortArgs a
             for (int b = 0; b < 4; ++b) atomicAdd(&h[(4 * j + b) * LK_BINS + ((x.w[j] >> (8 * b)) & 0xffu)], 1u);
         }
     }
-    if (bad) atomicOr(a.flags, FLAG_NONCANONICAL);
+    if (bad) lk_raise(a.flags, a.status, FLAG_NONCANONICAL);
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < LK_PASSES * LK_BINS; j += LK_THREADS) {
         const uint32_t v = h[j];
@@ -153,8 +185,9 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_digit_hist(const FrSortArgs a
     }
 }
 
-// One workgroup.  Reads hist[32][256], writes plan[0 .. 32] (file header).
-__global__ void __launch_bounds__(LK_THREADS) k_lk_plan(const FrSortArgs a) {
+// One workgroup per sort column (grid 1 x columns).  Reads hist[32][256], writes plan[0 .. 32] (file header).
+__global__ void __launch_bounds__(LK_THREADS) k_lk_plan(const FrSortArgs a0) {
+    const FrSortArgs a = lk_sort_column(a0);
     uint32_t state = 0;
 #pragma unroll 1
     for (uint32_t p = 0; p < LK_PASSES; ++p) {
@@ -184,7 +217,8 @@ FP_INLINE LkLane lk_lane(uint32_t t) {
 
 // counts[d][col] for the four columns of this tile, all 256 d (zeros included: the matrix needs no clearing).
 // Indices: keys < u; counts index d ncols + col < 256 ncols as col < 4 gridDim.x = ncols.  Reads the pass's source buffer.
-__global__ void __launch_bounds__(LK_THREADS) k_lk_tile_hist(const FrSortArgs a) {
+__global__ void __launch_bounds__(LK_THREADS) k_lk_tile_hist(const FrSortArgs a0) {
+    const FrSortArgs a = lk_sort_column(a0);
     const uint32_t pw = a.plan[a.pass];
     if (pw & 1u) return;
     const uint8_t* src = lk_state_buf(a.in, a.w0, a.w1, pw >> 1);
@@ -206,9 +240,15 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_tile_hist(const FrSortArgs a)
 // hist == null: base 0 (the tile sums of a u32 prefix sum: one row).  A step covers the entries [start, start + step), step a
 // multiple of 4 in 4 .. 1024: thread x < step / 4 holds the 4 consecutive entries from start + 4 x (the other threads hold
 // zeros and store nothing), all loaded before the first store of the step; the sum of a step is carried into the next.
-// Indices: entry e < ncols only, and inside the step.
+// Indices: entry e < ncols only, and inside the step.  With hist, blockIdx.y is the sort column: its matrix, histograms and plan
+// are the column's slabs (FrSortArgs); without, the rows of the launch are the lookups' tile sums [gridDim.x][ncols].
 __global__ void __launch_bounds__(LK_THREADS) k_lk_scan_rows(uint32_t* data, uint32_t ncols, const uint32_t* hist,
                                                               const uint32_t* plan, uint32_t pass, uint32_t step) {
+    if (hist) {
+        data += (size_t)blockIdx.y * LK_BINS * ncols;
+        hist += (size_t)blockIdx.y * (LK_PASSES * LK_BINS);
+        plan += (size_t)blockIdx.y * LK_PLAN_WORDS;
+    }
     if (plan && (plan[pass] & 1u)) return;
     __shared__ uint32_t lds[LK_WAVES];
     uint32_t carry = 0, total;
@@ -237,7 +277,8 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_scan_rows(uint32_t* data, uin
 // Moves the keys of the pass.  Reads the source buffer and the scanned counts; writes the other work buffer: positions
 // < u (file header), checked.  off[wave][d]: where the wave's next key with byte d goes.  A round: every lane reads its
 // offset; barrier; the lowest lane of every group of peers advances the group's offset; barrier.
-__global__ void __launch_bounds__(LK_THREADS) k_lk_scatter(const FrSortArgs a) {
+__global__ void __launch_bounds__(LK_THREADS) k_lk_scatter(const FrSortArgs a0) {
+    const FrSortArgs a = lk_sort_column(a0);
     const uint32_t pw = a.plan[a.pass];
     if (pw & 1u) return;
     const uint32_t state = pw >> 1;
@@ -275,9 +316,11 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_scatter(const FrSortArgs a) {
 }
 
 // sums[b] = the sum of src[bT .. bT + T) below n.  A thread adds 8 consecutive entries (threads >= T / 8 idle).
-// Indices: src index < n; sums index blockIdx.x < gridDim.x = ceil(n / T).
+// Indices: src index < n; sums index blockIdx.x < gridDim.x = ceil(n / T).  blockIdx.y = lookup: src [.][n], sums [.][gridDim.x].
 __global__ void __launch_bounds__(LK_THREADS) k_lk_block_reduce(const uint32_t* src, uint32_t* sums, uint32_t n, uint32_t t) {
     __shared__ uint32_t lds[LK_WAVES];
+    src += (size_t)blockIdx.y * n;
+    sums += (size_t)blockIdx.y * gridDim.x;
     const uint32_t i0 = (blockIdx.x << t) + 8u * threadIdx.x;
     uint32_t s = 0;
     if (8u * threadIdx.x < (1u << t)) {
@@ -290,10 +333,14 @@ __global__ void __launch_bounds__(LK_THREADS) k_lk_block_reduce(const uint32_t* 
 }
 
 // dst[i] = sum of src[0 .. i), i <= n: the tile's exclusive prefix on top of sums[b] (the scanned tile sums); the thread that
-// holds entry n - 1 also stores dst[n], the total.  dst has n + 1 entries and is not src.
+// holds entry n - 1 also stores dst[n], the total.  dst has n + 1 entries and is not src.  blockIdx.y = lookup: src [.][n],
+// sums [.][gridDim.x], dst [.][n + 1].
 __global__ void __launch_bounds__(LK_THREADS) k_lk_block_scan(const uint32_t* src, const uint32_t* sums, uint32_t* dst, uint32_t n,
                                                                uint32_t t) {
     __shared__ uint32_t lds[LK_WAVES];
+    src += (size_t)blockIdx.y * n;
+    sums += (size_t)blockIdx.y * gridDim.x;
+    dst += (size_t)blockIdx.y * ((size_t)n + 1);
     const uint32_t i0 = (blockIdx.x << t) + 8u * threadIdx.x;
     const bool mine = 8u * threadIdx.x < (1u << t);
     uint32_t v[8], s = 0;
@@ -330,13 +377,40 @@ struct FrLookupPermuteArgs {
     uint8_t* ap;             // [u]
     uint8_t* sp;             // [u]
     uint32_t* flags;
+    uint32_t* status;        // [lookups] or null
+    size_t col_stride;       // bytes between the lookups' columns of a_in, s_in, ap, sp
+    size_t key_stride;       // ... of a_w0, a_w1, s_w0, s_w1
     uint32_t u;
 };
+
+// The arguments of lookup blockIdx.y (file header, "Batch"): the callers' columns by col_stride, the work buffers by key_stride,
+// the plans by 33 words, the marks by u words, the prefixes by u + 1.
+FP_INLINE FrLookupPermuteArgs lk_permute_lookup(FrLookupPermuteArgs p) {
+    const size_t b = blockIdx.y;
+    p.a_in += b * p.col_stride;
+    p.s_in += b * p.col_stride;
+    p.ap += b * p.col_stride;
+    p.sp += b * p.col_stride;
+    p.a_w0 += b * p.key_stride;
+    p.a_w1 += b * p.key_stride;
+    p.s_w0 += b * p.key_stride;
+    p.s_w1 += b * p.key_stride;
+    p.a_plan += b * LK_PLAN_WORDS;
+    p.s_plan += b * LK_PLAN_WORDS;
+    p.non_head += b * p.u;
+    p.left += b * p.u;
+    p.left_idx += b * p.u;
+    p.non_head_pre += b * ((size_t)p.u + 1);
+    p.left_pre += b * ((size_t)p.u + 1);
+    if (p.status) p.status += b;
+    return p;
+}
 
 // Row i < u of sorted a: head or not; a head finds the first row of sorted s that is >= its value (binary search: lo, mid < u)
 // and clears left[] there if the values are equal — different heads have different values, so different rows — or raises
 // FLAG_NOT_IN_TABLE.  Reads both sorted columns; writes non_head[i], left[lo].
-__global__ void __launch_bounds__(BLOCK) k_lk_heads(const FrLookupPermuteArgs p) {
+__global__ void __launch_bounds__(BLOCK) k_lk_heads(const FrLookupPermuteArgs p0) {
+    const FrLookupPermuteArgs p = lk_permute_lookup(p0);
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= p.u) return;
     const uint8_t* A = lk_state_buf(p.a_in, p.a_w0, p.a_w1, p.a_plan[LK_PASSES]);
@@ -353,11 +427,12 @@ __global__ void __launch_bounds__(BLOCK) k_lk_heads(const FrLookupPermuteArgs p)
         else hi = mid;
     }
     if (lo < p.u && lk_equal(u256_load(S + 32 * (size_t)lo), x)) p.left[lo] = 0u;
-    else atomicOr(p.flags, FLAG_NOT_IN_TABLE);
+    else lk_raise(p.flags, p.status, FLAG_NOT_IN_TABLE);
 }
 
 // left_idx[left_pre[q]] = q for every unconsumed row q < u of sorted s.  left_pre[q] < left_pre[u] <= u.
-__global__ void __launch_bounds__(BLOCK) k_lk_leftovers(const FrLookupPermuteArgs p) {
+__global__ void __launch_bounds__(BLOCK) k_lk_leftovers(const FrLookupPermuteArgs p0) {
+    const FrLookupPermuteArgs p = lk_permute_lookup(p0);
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
     if (q >= p.u) return;
     const uint32_t j = p.left_pre[q];
@@ -367,7 +442,8 @@ __global__ void __launch_bounds__(BLOCK) k_lk_leftovers(const FrLookupPermuteArg
 // ap[i] = A[i]; sp[i] = A[i] on a head, else the leftover of rank j = non-heads - 1 - (non-heads below i).  j < leftovers
 // whenever every head was found (then leftovers = non-heads); checked, as is the row read from left_idx, so a call that
 // raised FLAG_NOT_IN_TABLE stays inside its buffers (its outputs are unspecified).  Writes only ap[i] and sp[i], i < u.
-__global__ void __launch_bounds__(BLOCK) k_lk_fill(const FrLookupPermuteArgs p) {
+__global__ void __launch_bounds__(BLOCK) k_lk_fill(const FrLookupPermuteArgs p0) {
+    const FrLookupPermuteArgs p = lk_permute_lookup(p0);
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= p.u) return;
     const uint8_t* A = lk_state_buf(p.a_in, p.a_w0, p.a_w1, p.a_plan[LK_PASSES]);

@@ -10,47 +10,57 @@ namespace {
 constexpr size_t PROD_MAX_N = (size_t)1 << FFT_MAX_K;
 
 // the levels of one sweep pair over n elements, in the context's level buffer.  (The last level, one element, is never stored:
-// the top chunk keeps its root.)
-FrLevelPlan prod_plan(const h2agg_ctx* c, size_t n) {
-    return fr_level_plan(c->dbg_fr_scan_chunk ? (unsigned)c->dbg_fr_scan_chunk : FR_CHUNK_LOG, n, 1);
+// the top chunk keeps its root.)  nq > 1: a batch of nq running products of n positions each, level l >= 1 is [nq][cnt[l]] at off[l]
+FrLevelPlan prod_plan(const h2agg_ctx* c, size_t n, size_t nq = 1) {
+    return fr_level_plan(c->dbg_fr_scan_chunk ? (unsigned)c->dbg_fr_scan_chunk : FR_CHUNK_LOG, n, nq);
 }
 
 // Queues both sweeps of `op` over n >= 1 elements (scan: n = u + 1 positions): up-sweeps of the levels below the top one, then
-// the down-sweeps from the top.  The level buffer must hold prod_plan(c, n).total elements.
+// the down-sweeps from the top.  The level buffer must hold prod_plan(c, n, nq).total elements.  nq > 1 (scan only): nq columns
+// in the second grid dimension — column y of src and aux at + y src_stride bytes, of dst at + y dst_stride — with the launch
+// count of one column.
 void prod_sweeps_queue(h2agg_ctx* c, uint32_t op, const uint8_t* d_src, const uint8_t* d_aux, size_t n, const ph::HFr& top,
-                       bool check, uint8_t* d_dst) {
-    const FrLevelPlan plan = prod_plan(c, n);
+                       bool check, uint8_t* d_dst, size_t nq = 1, size_t src_stride = 0, size_t dst_stride = 0) {
+    const FrLevelPlan plan = prod_plan(c, n, nq);
     uint8_t* lvl = (uint8_t*)c->prod_lvl.p;
     const size_t L = plan.launches();
+    const unsigned ny = (unsigned)nq;
     FrProdArgs a;
     hfr_words(top, a.top);
     a.aux = d_aux;
+    a.aux_stride = src_stride;
     a.flags = c->d_flags;
     a.t = plan.t;
     a.op = op;
     a.check = check;
     for (size_t l = 0; l + 1 < L; ++l) {
         a.src = l == 0 ? d_src : lvl + 32 * plan.off[l];
+        a.src_stride = l == 0 ? src_stride : 32 * (size_t)plan.cnt[l];
         a.dst = lvl + 32 * plan.off[l + 1];
+        a.dst_stride = 32 * (size_t)plan.cnt[l + 1];
         a.carry = nullptr;
+        a.carry_stride = 0;
         a.n = plan.cnt[l];
         a.level0 = l == 0;
-        hipLaunchKernelGGL(k_fr_prod_chunk, dim3(plan.cnt[l + 1]), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
+        hipLaunchKernelGGL(k_fr_prod_chunk, dim3(plan.cnt[l + 1], ny), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
     }
     for (size_t l = L; l-- > 0;) {
         a.src = l == 0 ? d_src : lvl + 32 * plan.off[l];
+        a.src_stride = l == 0 ? src_stride : 32 * (size_t)plan.cnt[l];
         a.dst = l == 0 ? d_dst : lvl + 32 * plan.off[l];
+        a.dst_stride = l == 0 ? dst_stride : 32 * (size_t)plan.cnt[l];
         a.carry = l + 1 == L ? nullptr : lvl + 32 * plan.off[l + 1];
+        a.carry_stride = 32 * (size_t)plan.cnt[l + 1];
         a.n = plan.cnt[l];
         a.level0 = l == 0;
         if (op == FR_PROD_INVERT)
             hipLaunchKernelGGL(k_fr_prod_invert, dim3(plan.cnt[l + 1]), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
         else
-            hipLaunchKernelGGL(k_fr_prod_scan, dim3(plan.cnt[l + 1]), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
+            hipLaunchKernelGGL(k_fr_prod_scan, dim3(plan.cnt[l + 1], ny), dim3(FR_CHUNK_THREADS), 0, c->stream, a);
     }
 }
 
-int prod_ensure_levels(h2agg_ctx* c, size_t n) { return ensure(c, c->prod_lvl, 32 * prod_plan(c, n).total); }
+int prod_ensure_levels(h2agg_ctx* c, size_t n, size_t nq = 1) { return ensure(c, c->prod_lvl, 32 * prod_plan(c, n, nq).total); }
 
 // out[i] = 1 / in[i] (montgomery2 = false) or R^2 / in[i] (true: what the scan multiplies num with), 0 for 0; n >= 1
 int prod_invert_queue(h2agg_ctx* c, const uint8_t* d_in, size_t n, bool montgomery2, bool check, uint8_t* d_out) {
@@ -145,11 +155,21 @@ int lookup_check(h2agg_ctx* c, unsigned k, size_t u, const uint8_t* beta, const 
     return fr_parse(c, gamma, gf);
 }
 
-int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uint8_t* d_ap, const uint8_t* d_sp, size_t u,
-                 const ph::HFr& beta, const ph::HFr& gamma, uint8_t* d_out, uint8_t* d_last) {
+// The Z columns of a chunk of nb lookups over u rows each, nb u <= 2^24: lookup y reads column y of the four slabs (col_stride
+// bytes apart) and writes z[0 .. u] of column y of d_out (out_stride apart).  One term launch into num / den [nb][u], ONE
+// inversion of the nb u denominators, one pair of sweeps with the lookups in the second grid dimension: the launch count of
+// one lookup.  phases (or null) is marked with first, first + 1, first + 2 in front of the terms, the inversion and the scan.
+int lookup_chunk_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uint8_t* d_ap, const uint8_t* d_sp,
+                       size_t col_stride, size_t nb, size_t u, const ph::HFr& beta, const ph::HFr& gamma, uint8_t* d_out,
+                       size_t out_stride, PhaseClock* phases = nullptr, int first = 0) {
     if (u) {
-        TRY(ensure(c, c->prod_num, 32 * u));
-        TRY(ensure(c, c->prod_den, 32 * u));
+        TRY(ensure(c, c->prod_num, 32 * nb * u));
+        TRY(ensure(c, c->prod_den, 32 * nb * u));
+    }
+    uint8_t* num = (uint8_t*)c->prod_num.p;
+    uint8_t* den = (uint8_t*)c->prod_den.p;
+    if (phases) phases->mark(first);
+    if (u) {
         FrLookupArgs a;
         hfr_words(beta, a.beta);
         hfr_words(gamma, a.gamma);
@@ -157,13 +177,27 @@ int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uin
         a.s = d_s;
         a.ap = d_ap;
         a.sp = d_sp;
-        a.num = (uint8_t*)c->prod_num.p;
-        a.den = (uint8_t*)c->prod_den.p;
+        a.num = num;
+        a.den = den;
         a.flags = c->d_flags;
+        a.col_stride = col_stride;
         a.u = (uint32_t)u;
-        hipLaunchKernelGGL(k_fr_lookup_terms, dim3((unsigned)((u + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a);
+        hipLaunchKernelGGL(k_fr_lookup_terms, dim3((unsigned)((u + BLOCK - 1) / BLOCK), (unsigned)nb), dim3(BLOCK), 0, c->stream, a);
+        if (phases) phases->mark(first + 1);
+        TRY(prod_invert_queue(c, den, nb * u, true, false, den));   // in place: R^2 / den
     }
-    return prod_grand_queue(c, (const uint8_t*)c->prod_num.p, (const uint8_t*)c->prod_den.p, u, ph::one(), false, d_out, d_last);
+    TRY(prod_ensure_levels(c, u + 1, nb));
+    if (phases) phases->mark(first + 2);
+    prod_sweeps_queue(c, FR_PROD_SCAN, num, u ? den : nullptr, u + 1, ph::one(), false, d_out, nb, 32 * u, out_stride);
+    HIP_TRY(c, hipGetLastError());
+    return H2AGG_OK;
+}
+
+int lookup_queue(h2agg_ctx* c, const uint8_t* d_a, const uint8_t* d_s, const uint8_t* d_ap, const uint8_t* d_sp, size_t u,
+                 const ph::HFr& beta, const ph::HFr& gamma, uint8_t* d_out, uint8_t* d_last) {
+    TRY(lookup_chunk_queue(c, d_a, d_s, d_ap, d_sp, 0, 1, u, beta, gamma, d_out, 0));
+    if (d_last) HIP_TRY(c, hipMemcpyAsync(d_last, d_out + 32 * u, 32, hipMemcpyDeviceToDevice, c->stream));
+    return H2AGG_OK;
 }
 
 // the tail of every synchronous product call: out[0 .. u] and `last` back to the host

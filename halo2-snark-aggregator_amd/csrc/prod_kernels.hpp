@@ -38,6 +38,11 @@
 // Term kernels: a term v + b + gamma (v an input, b a product < 1.04, gamma < 1) is < 3.04 (< 7.4 non-canonical); the
 // accumulator starts at R^m (R^2) < 1 and stays < 7.4 * 1.05 / 169 + 1 < 1.05; stored through fp_cond_sub.
 //
+// Batch.  k_fr_prod_chunk and k_fr_prod_scan take blockIdx.y as the column of a batch of running products (the lookups of a
+// chunk): every array of the launch is a slab, column y at + y * its stride in bytes (fr_prod_column; the strides are 0 in a
+// single call, whose grid has one row).  A level above the elements is [columns][chunks].  k_fr_lookup_terms takes blockIdx.y
+// as the lookup in the same way.  Indices inside a column stay 32-bit.
+//
 // Per-call constants (top, init, beta, gamma, the delta powers) come BY VALUE in the kernel arguments: a device block that
 // a host copy fills could be rewritten by a second queued call before the first one's launch has read it
 // (fr_fft_kernels.hpp, poly_kernels.hpp).  The table of w^i is built by k_fr_powers on the same stream.
@@ -61,7 +66,17 @@ struct FrProdArgs {
     uint32_t op;            // FR_PROD_INVERT / FR_PROD_SCAN
     uint32_t level0;
     uint32_t check;         // level 0: src is the caller's, elements are checked for < r
+    size_t src_stride, aux_stride, dst_stride, carry_stride;   // bytes from column y to y + 1 of each array (file header, "Batch")
 };
+
+FP_INLINE FrProdArgs fr_prod_column(FrProdArgs a) {
+    const size_t y = blockIdx.y;
+    a.src += y * a.src_stride;
+    if (a.aux) a.aux += y * a.aux_stride;
+    a.dst += y * a.dst_stride;
+    if (a.carry) a.carry += y * a.carry_stride;
+    return a;
+}
 
 // Element i of this level in the form the sweep multiplies (file header); zero: an inversion's input that is 0.
 // Reads src[i] (and aux[i]) for i < n only — scan, level 0: i < n - 1 = u.
@@ -145,7 +160,8 @@ FP_INLINE void fr_prod_tree_up(uint32_t* lds, uint32_t tid, uint32_t nthr, const
 
 // Up-sweep.  Indices: a thread reads element i for i in [cT + 8 tid, cT + 8 tid + 8) with i < n only, thread 0 stores dst[c],
 // c < chunks = gridDim.x.
-__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_chunk(const FrProdArgs a) {
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_chunk(const FrProdArgs a0) {
+    const FrProdArgs a = fr_prod_column(a0);
     __shared__ uint32_t lds[NL * 2 * FR_CHUNK_THREADS];
     const auto [nthr, tid, c, i0] = fr_chunk(a.t, blockIdx.x);
     Fr x[FR_CHUNK_PER];
@@ -202,7 +218,8 @@ __global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_invert(const FrPro
 // Down-sweep of the scan.  In place (dst == src, which h2agg_fr_grand_product_device allows for out and num) is safe for the
 // reason given at k_fr_prod_invert; dst[n - 1] (level 0: out[u]) is stored by the thread that owns position n - 1, which
 // loads nothing there.
-__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_scan(const FrProdArgs a) {
+__global__ void __launch_bounds__(FR_CHUNK_THREADS) k_fr_prod_scan(const FrProdArgs a0) {
+    const FrProdArgs a = fr_prod_column(a0);
     __shared__ uint32_t lds[NL * 2 * FR_CHUNK_THREADS];
     const auto [nthr, tid, c, i0] = fr_chunk(a.t, blockIdx.x);
     Fr x[FR_CHUNK_PER];
@@ -275,13 +292,24 @@ struct FrLookupArgs {
     uint8_t* num;                 // [u]
     uint8_t* den;                 // [u]
     uint32_t* flags;
+    size_t col_stride;            // bytes between the lookups' columns of a, s, ap, sp; num and den are dense [lookups][u]
     uint32_t u;
 };
 
-// num[i] = (a[i] + beta)(s[i] + gamma), den[i] = (ap[i] + beta)(sp[i] + gamma), i < u
-__global__ void __launch_bounds__(BLOCK) k_fr_lookup_terms(const FrLookupArgs a) {
+// num[i] = (a[i] + beta)(s[i] + gamma), den[i] = (ap[i] + beta)(sp[i] + gamma), i < u; blockIdx.y = lookup
+__global__ void __launch_bounds__(BLOCK) k_fr_lookup_terms(const FrLookupArgs a0) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= a.u) return;
+    if (i >= a0.u) return;
+    FrLookupArgs a = a0;
+    {
+        const size_t y = blockIdx.y, at = y * a.col_stride, dense = y * 32 * (size_t)a.u;
+        a.a += at;
+        a.s += at;
+        a.ap += at;
+        a.sp += at;
+        a.num += dense;
+        a.den += dense;
+    }
     const Fr beta = fp_unpack<FrParams>(a.beta), gamma = fp_unpack<FrParams>(a.gamma);
     const Fr x = fp_load<FrParams>(a.a + 32 * (size_t)i), s = fp_load<FrParams>(a.s + 32 * (size_t)i);
     const Fr xp = fp_load<FrParams>(a.ap + 32 * (size_t)i), sp = fp_load<FrParams>(a.sp + 32 * (size_t)i);

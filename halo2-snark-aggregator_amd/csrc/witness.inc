@@ -243,14 +243,14 @@ int wc_queue(h2agg_ctx* c, const h2agg_vk& vk, const WcCall& call, const uint8_t
             for (int t = 0; t < 2; ++t)
                 qe_eval_queue(c, call.lookup_progs[2 * j + t], d_prog + lookup_at[2 * j + t], false, k, d_advice, d_fixed, d_instance,
                               &call.theta, nullptr, true, fold[t]);
-            TRY(lk_sort_queue(c, fold[1], sort, 0, l.u, geom));
+            TRY(lk_sort_queue(c, fold[1], sort, l.u, geom));
             const uint8_t* lw = (const uint8_t*)c->lk_work.p;
             WcLookupArgs a;
             a.a = fold[0];
             a.s_in = fold[1];
-            a.s_w0 = lw + sort.keys[0];
-            a.s_w1 = lw + sort.keys[1];
-            a.s_plan = (const uint32_t*)(lw + sort.plan[0]);
+            a.s_w0 = lw + sort.w0;
+            a.s_w1 = lw + sort.w1;
+            a.s_plan = (const uint32_t*)(lw + sort.plan);
             a.zflags = zflags;
             a.n = n;
             a.u = l.u;

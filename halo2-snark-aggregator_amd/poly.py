@@ -286,6 +286,64 @@ def lookup_argument(eng, inputs, tables, k: int, usable: int, theta: bytes, beta
     return ap, sp, z
 
 
+# ---------------------------------------------------------------------------------------------- lookup argument, batched
+def _blocks(blinding, count: int, rows: int, what: str):
+    """None, or one block of `rows` elements per lookup -> a list of `count` blocks (zero for None)"""
+    if blinding is None:
+        return [bytes(32 * rows)] * count
+    blinding = list(blinding)
+    if len(blinding) != count or any(len(b) != 32 * rows for b in blinding):
+        raise ValueError("%s must be %d blocks of %d elements of 32 bytes" % (what, count, rows))
+    return [bytes(b) for b in blinding]
+
+
+def _filled(blocks, below: int) -> bytes:
+    """a slab whose columns hold zero in the rows below `below` and their block above"""
+    return b"".join(bytes(32 * below) + b for b in blocks)
+
+
+def permute_expression_pairs(eng, a_cols, s_cols, k: int, usable: int, blinding=None):
+    """permute_expression_pair of every lookup of a list in ONE call (h2agg_lookup_batch_permute): a_cols / s_cols are the
+    compressed inputs and tables, one column of 2^k rows per lookup.  blinding: None, or (blocks for ap, blocks for sp), one
+    block of 2^k - usable elements per lookup.  -> (list of ap, list of sp).  Raises the H2AggError of the lowest-numbered
+    failing lookup; its .partial holds (ap slab, sp slab, status words)."""
+    a_cols = list(a_cols)
+    count = len(a_cols)
+    a, s = _columns(a_cols, k, "a"), _slab(s_cols, count, k, "s")
+    top = (1 << k) - usable
+    if blinding is not None and len(blinding) != 2:
+        raise ValueError("blinding must be two lists of blocks: ap, sp")
+    pre = [_filled(_blocks(None if blinding is None else blinding[i], count, top, "blinding"), usable) for i in range(2)]
+    ap, sp, _status = eng.lookup_batch_permute(a, s, count, k, usable, pre[0], pre[1])
+    return _split(ap, k), _split(sp, k)
+
+
+def lookup_products(eng, a_cols, s_cols, ap_cols, sp_cols, k: int, usable: int, beta: bytes, gamma: bytes, blinding=None):
+    """lookup::prover::commit_product of every lookup of a list in ONE call (h2agg_lookup_batch_product).  blinding: None, or
+    one block of 2^k - usable - 1 elements per lookup.  -> a list of Z columns of 2^k rows."""
+    a_cols = list(a_cols)
+    count = len(a_cols)
+    slabs = [_columns(a_cols, k, "a")] + [_slab(c, count, k, w) for c, w in ((s_cols, "s"), (ap_cols, "ap"), (sp_cols, "sp"))]
+    pre = _filled(_blocks(blinding, count, (1 << k) - usable - 1, "blinding"), usable + 1)
+    z, _last = eng.lookup_batch_product(*slabs, count, k, usable, beta, gamma, pre)
+    return _split(z, k)
+
+
+def lookup_arguments(eng, inputs, tables, k: int, usable: int, theta: bytes, beta: bytes, gamma: bytes, blinding=None):
+    """every lookup of a circuit from its expressions to its Z: inputs[j] / tables[j] are the expression columns of lookup j.
+    One compression per expression list, then ONE permutation call and ONE product call for all lookups.  blinding: None, or
+    (blocks for ap, blocks for sp, blocks for z), one block per lookup.  -> (list of ap, list of sp, list of z)."""
+    if len(inputs) != len(tables) or not inputs:
+        raise ValueError("inputs and tables must be the same non-zero number of lookups")
+    if blinding is not None and len(blinding) != 3:
+        raise ValueError("blinding must be three lists of blocks: ap, sp, z")
+    a = [compress_expressions(eng, cols, k, theta) for cols in inputs]
+    s = [compress_expressions(eng, cols, k, theta) for cols in tables]
+    ap, sp = permute_expression_pairs(eng, a, s, k, usable, None if blinding is None else blinding[:2])
+    z = lookup_products(eng, a, s, ap, sp, k, usable, beta, gamma, None if blinding is None else blinding[2])
+    return ap, sp, z
+
+
 # ---------------------------------------------------------------------------------------------- quotient polynomial
 def _slab(cols, count: int, k: int, what: str):
     """a list of `count` columns -> one slab, or None for no columns"""
@@ -629,3 +687,27 @@ def resident_shplonk_prove(eng, g_handle: int, polys: ColumnView, queries, point
     finally:
         eng.kzg_shplonk_destroy(obj)
     return [evals[32 * q:32 * q + 32] for q in range(len(queries))], h1, h2
+
+
+def _same_shape(views, what: str):
+    first = views[0]
+    if any(v.count != first.count or v.k != first.k for v in views):
+        raise ValueError("%s must be as many columns of one k" % what)
+
+
+def resident_lookup_permute(eng, a: ColumnView, s: ColumnView, usable: int, ap: ColumnView, sp: ColumnView, status: bool = True):
+    """permute_expression_pairs over views of stores (h2agg_lookup_store_permute): column j of a and s -> rows below `usable`
+    of column j of ap and sp; the rows above stay what the stores hold.  status=True: synchronous -> the per-lookup status
+    words (an error carries them in .partial); False: queued on the context's stream -> None"""
+    _same_shape((a, s, ap, sp), "a, s, ap, sp")
+    return eng.lookup_store_permute(a.handle, a.first, s.handle, s.first, a.count, usable, ap.handle, ap.first, sp.handle, sp.first,
+                                    status)
+
+
+def resident_lookup_product(eng, a: ColumnView, s: ColumnView, ap: ColumnView, sp: ColumnView, usable: int, beta: bytes,
+                            gamma: bytes, z: ColumnView, last: bool = True):
+    """lookup_products over views of stores (h2agg_lookup_store_product): rows 0 .. usable of column j of z.  last=True:
+    synchronous -> the list of z[j][usable]; False: queued on the context's stream -> None"""
+    _same_shape((a, s, ap, sp, z), "a, s, ap, sp, z")
+    return eng.lookup_store_product(a.handle, a.first, s.handle, s.first, ap.handle, ap.first, sp.handle, sp.first, a.count, usable,
+                                    beta, gamma, z.handle, z.first, last)

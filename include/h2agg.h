@@ -821,6 +821,51 @@ int h2agg_lookup_permute_device(h2agg_ctx* ctx, const void* d_a, const void* d_s
 int h2agg_fr_columns_compress(h2agg_ctx* ctx, const uint8_t* cols, size_t m, unsigned k, const uint8_t theta[32], uint8_t* out);
 int h2agg_fr_columns_compress_device(h2agg_ctx* ctx, const void* d_cols, size_t m, unsigned k, const uint8_t theta[32], void* d_out);
 
+/* ---- Lookup argument, batched: every lookup of a circuit in one call ---------------------------------------------------------
+ * Lookup j of a batch of `count` is EXACTLY h2agg_lookup_permute / h2agg_lookup_product (the two blocks above) on column j of
+ * each slab, byte for byte; what a batch changes is the number of launches: all lookups of a chunk share the launches of one
+ * (DESIGN.md 5.21).  Slabs are [count][2^k] (column j at 32 * 2^k * j bytes); u, beta, gamma are the batch's.
+ *   lookup_batch_permute(a, s, count, k, u) -> ap, sp, status[count]
+ *   lookup_batch_product(a, s, ap, sp, count, k, u, beta, gamma) -> z, last[count][32]
+ *   lookup_store_permute / lookup_store_product: the same over column stores (the block "Fr column stores" below): columns
+ *     first .. first + count - 1 of each named store, k the stores'.  The stores may be one store with disjoint ranges.
+ *     - Rows from u up of ap and sp, rows from u + 1 up of z are not written (the caller's blinding rows); columns of a store
+ *       outside the named ranges are not touched.  u == 0: z[j][0] = 1 and nothing else is written.
+ *     - status[j] (may be NULL) is 0, or the OR of the status bits of lookup j: H2AGG_LOOKUP_STATUS_NONCANONICAL (1) = an
+ *       element >= r, H2AGG_LOOKUP_STATUS_NOT_IN_TABLE (8) = a head value absent from its table.  last[j] (may be NULL) =
+ *       z[j][u].
+ *     - The host-slab forms are synchronous.  A store form that is given status (permute) or last (product) is synchronous
+ *       too.  A synchronous call returns the code the single call would return for the LOWEST-NUMBERED failing lookup
+ *       (H2AGG_ERR_NONCANONICAL, H2AGG_ERR_NOT_IN_TABLE); the outputs of every lookup that did not fail are complete and
+ *       correct, those of a failed one unspecified.
+ *     - A store form with status == NULL / last == NULL is queued on the context's stream with no synchronisation and no
+ *       read-back, and reports through the context's device status as the _device twins above do (a workspace that has to
+ *       grow drains the device first).
+ *   lookup_configure(batch_chunk): at most that many lookups per chunk (set of launches) in this context; 0 = the default,
+ *     clamp(2^24 / max(u, 1), 1, 1024).  lookup_chunk_rule(u, batch_chunk) -> the lookups per chunk a context configured
+ *     with batch_chunk takes at u rows (host arithmetic, no context; a batch_chunk above 1024 counts as 0).  Work memory per chunk of B lookups: B times a single call's (about 150 bytes per row),
+ *     kept in the context.
+ * Refusals, the context stays usable and nothing is written: those of the single calls (k > 24, u >= 2^k, a null buffer,
+ *   beta / gamma >= r: H2AGG_ERR_NONCANONICAL) and of the store family (an unknown handle, a range outside its store, stores
+ *   that differ in k); count == 0 or count > 65535; an output range that overlaps an input range or another output;
+ *   batch_chunk > 1024: H2AGG_ERR_INVALID.  Out of memory: H2AGG_ERR_NOMEM.
+ * Debug key phases: h2agg_last_phases gives " sort= rank=" (permute) and " terms= invert= scan=" (product), milliseconds on
+ *   the context's stream; the host-slab forms put " stage=" in front. */
+#define H2AGG_LOOKUP_STATUS_NONCANONICAL 1u
+#define H2AGG_LOOKUP_STATUS_NOT_IN_TABLE 8u
+int h2agg_lookup_batch_permute(h2agg_ctx* ctx, const uint8_t* a, const uint8_t* s, size_t count, unsigned k, size_t u,
+                               uint8_t* ap, uint8_t* sp, uint32_t* status);
+int h2agg_lookup_batch_product(h2agg_ctx* ctx, const uint8_t* a, const uint8_t* s, const uint8_t* ap, const uint8_t* sp,
+                               size_t count, unsigned k, size_t u, const uint8_t beta[32], const uint8_t gamma[32],
+                               uint8_t* z, uint8_t* last);
+int h2agg_lookup_store_permute(h2agg_ctx* ctx, uint64_t a, size_t afirst, uint64_t s, size_t sfirst, size_t count, size_t u,
+                               uint64_t ap, size_t apfirst, uint64_t sp, size_t spfirst, uint32_t* status);
+int h2agg_lookup_store_product(h2agg_ctx* ctx, uint64_t a, size_t afirst, uint64_t s, size_t sfirst, uint64_t ap, size_t apfirst,
+                               uint64_t sp, size_t spfirst, size_t count, size_t u, const uint8_t beta[32],
+                               const uint8_t gamma[32], uint64_t z, size_t zfirst, uint8_t* last);
+int h2agg_lookup_configure(h2agg_ctx* ctx, size_t batch_chunk);
+size_t h2agg_lookup_chunk_rule(size_t u, size_t batch_chunk);
+
 /* ---- Quotient polynomial h(X): a key's expressions on every row, and the quotient from the verifying key ---------------------
  * Stand for: the evaluation of h(X) in halo2_proofs' create_proof (evaluate_h, coeff_to_extended, extended_to_coeff) — recalled
  * from upstream, not pinned, like the blocks above; what the entry points compute is this definition.  Which expressions h

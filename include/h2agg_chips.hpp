@@ -346,6 +346,20 @@ class Columns {
         out.resize(count);
         return out;
     }
+    // h2agg_lookup_store_permute: the `count` lookups whose compressed inputs are the columns afirst .. of *this and whose
+    // tables are the columns sfirst .. of s -> rows below u of ap's and sp's columns.  status null: queued; else `count` words
+    // are filled, the call is synchronous and throws the lowest-numbered failing lookup's error
+    void lookup_permute(size_t afirst, const Columns& s, size_t sfirst, size_t count, size_t u, Columns& ap, size_t apfirst,
+                        Columns& sp, size_t spfirst, uint32_t* status = nullptr) const {
+        g_->check(h2agg_lookup_store_permute(g_->ctx(), h_, afirst, s.h_, sfirst, count, u, ap.h_, apfirst, sp.h_, spfirst, status));
+    }
+    // h2agg_lookup_store_product: rows 0 .. u of z's columns.  last null: queued; else count x 32 bytes, synchronous
+    void lookup_product(size_t afirst, const Columns& s, size_t sfirst, const Columns& ap, size_t apfirst, const Columns& sp,
+                        size_t spfirst, size_t count, size_t u, const Scalar& beta, const Scalar& gamma, Columns& z, size_t zfirst,
+                        uint8_t* last = nullptr) const {
+        g_->check(h2agg_lookup_store_product(g_->ctx(), h_, afirst, s.h_, sfirst, ap.h_, apfirst, sp.h_, spfirst, count, u, beta.data(),
+                                             gamma.data(), z.h_, zfirst, last));
+    }
 
   private:
     void reset() {

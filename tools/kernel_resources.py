@@ -20,6 +20,11 @@ BUDGETS = [  # (name pattern, max VGPRs, max scratch bytes)
     ("k_fb_partition", 128, 0),
     ("k_fb_bucket_sort", 128, 128),   # (a 1024-thread workgroup caps it at 128; a few loop invariants are parked in scratch around the staged passes)
     ("k_qe_cross_cosets", 128, 0),    # (its accumulators are a register file: a group of pieces too large for it shows up as scratch)
+    # the lookup batch: the kernels that took a second grid dimension keep their occupancy — eight waves
+    # per SIMD for the sort and rank kernels, four for the field kernels — and gain no scratch
+    ("k_lk_digit_hist", 64, 0), ("k_lk_plan", 64, 0), ("k_lk_tile_hist", 64, 0), ("k_lk_scan_rows", 64, 0), ("k_lk_scatter", 64, 0),
+    ("k_lk_block_reduce", 64, 0), ("k_lk_block_scan", 64, 0), ("k_lk_heads", 64, 0), ("k_lk_leftovers", 64, 0), ("k_lk_fill", 64, 0),
+    ("k_fr_lookup_terms", 128, 0), ("k_fr_prod_chunk", 128, 0), ("k_fr_prod_scan", 128, 0),
 ]
 
 # EVERY kernel of the code object is checked: a kernel with a scratch segment or spilled VGPRs that is not
