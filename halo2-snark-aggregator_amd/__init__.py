@@ -40,6 +40,9 @@ PERM_MAX_COLUMNS = 4096   # H2AGG_PERM_MAX_COLUMNS: most columns of one permutat
 EXPR_MAX_DEPTH = 16  # H2AGG_EXPR_MAX_DEPTH: the operand stack of h2agg_vk_expressions_eval / h2agg_quotient (csrc/quotient_kernels.hpp)
 WC_GATES, WC_PERMUTATION, WC_LOOKUPS = 1, 2, 4   # H2AGG_WC_*: the kinds of constraint h2agg_witness_check checks
 WC_NONE = 0xFFFFFFFF   # "no row" in its report
+PK_COSETS = 1   # H2AGG_PK_COSETS: the proving key also holds its columns' values on every coset of the extended domain
+# H2AGG_PK_*: the forms h2agg_pk_ptr answers
+PK_FIXED_LAGRANGE, PK_SIGMA_LAGRANGE, PK_FIXED_COEFF, PK_SIGMA_COEFF, PK_LAGRANGE_COEFF, PK_COSET = range(6)
 
 IDENTITY_JAC =(0).to_bytes(32, "little") + (1).to_bytes(32, "little") + (0).to_bytes(32, "little")
 
@@ -234,6 +237,15 @@ def load_library():
                                               C.POINTER(u64)]),
         "h2agg_columns_shplonk_begin": (i32, [ctxp, u64, u64, sz, sz, C.POINTER(C.c_uint32), sz, u8p, sz, u8p, u8p, u8p, vp,
                                               C.POINTER(vp)]),
+        "h2agg_pk_create": (i32, [ctxp, vp, vp, vp, C.c_uint, C.POINTER(vp)]),
+        "h2agg_pk_create_resident": (i32, [ctxp, vp, vp, vp, C.c_uint, C.POINTER(vp)]),
+        "h2agg_pk_bytes": (i32, [vp, C.c_uint, C.POINTER(sz)]),
+        "h2agg_pk_info": (i32, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_uint),
+                                C.POINTER(sz)]),
+        "h2agg_pk_ptr": (i32, [vp, i32, sz, C.POINTER(vp), C.POINTER(sz)]),
+        "h2agg_pk_quotient": (i32, [ctxp, vp, vp, vp, vp, vp, vp, vp, u8p, u8p, u8p, u8p, u8p, u8p, vp]),
+        "h2agg_pk_quotient_work_bytes": (i32, [vp, C.POINTER(sz)]),
+        "h2agg_pk_destroy": (None, [vp]),
         "h2agg_g2_scalar_mul": (i32, [u8p, u8p, vp]),
         "h2agg_g2_batch_compress": (i32, [u8p, sz, vp]),
         "h2agg_pairing_product": (i32, [ctxp, u8p, u8p, sz, vp]),
@@ -1051,6 +1063,66 @@ class H2Agg:
                                                   max_rows, counts, first, rows, C.byref(total)))
         lines = None if rows is None else [list(rows[c * max_rows:(c + 1) * max_rows]) for c in range(ncons)]
         return list(counts[:ncons]), list(first[:ncons]), lines, total.value
+
+    # ------------------------------------------------------------------ proving key on the device
+    def _pk_create(self, fn, vk, fixed, sigma, forms: int):
+        pk = C.c_void_p()
+        self._check(fn(self._ctx, vk._vk, fixed, sigma, forms, C.byref(pk)))
+        return pk
+
+    def pk_create(self, vk, fixed, sigma, forms: int = PK_COSETS):
+        """h2agg_pk_create: the host slabs fixed[num_fixed][2^k] and sigma[num_permutation_columns][2^k] in Lagrange form (None
+        for a slab without columns) -> the object (pass it to pk_quotient; free it with pk_destroy before the key and the
+        engine go).  Synchronous.  forms: 0 or PK_COSETS.  The sizes come from vk.shape."""
+        sh = vk.shape
+        slabs = self._vk_slabs(vk, sh["k"], ((fixed, sh["num_fixed"], "fixed"), (sigma, sh["num_permutation_columns"], "sigma")))
+        return self._pk_create(self._lib.h2agg_pk_create, vk, *slabs, forms)
+
+    def pk_create_resident(self, vk, d_fixed_ptr, d_sigma_ptr, forms: int = PK_COSETS):
+        """h2agg_pk_create_resident: the same from slabs in device memory (not written); synchronous"""
+        return self._pk_create(self._lib.h2agg_pk_create_resident, vk, d_fixed_ptr, d_sigma_ptr, forms)
+
+    def pk_bytes(self, vk, forms: int = PK_COSETS) -> int:
+        """h2agg_pk_bytes: the device memory a proving key of this verifying key holds with these forms"""
+        out = C.c_size_t()
+        self._check(self._lib.h2agg_pk_bytes(vk._vk, forms, C.byref(out)))
+        return out.value
+
+    def pk_info(self, pk) -> dict:
+        """h2agg_pk_info: -> {"k", "e", "num_fixed", "num_permutation_columns", "forms", "bytes"}"""
+        k, e, forms = C.c_uint(), C.c_uint(), C.c_uint()
+        nf, np_, nbytes = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._check(self._lib.h2agg_pk_info(pk, C.byref(k), C.byref(e), C.byref(nf), C.byref(np_), C.byref(forms), C.byref(nbytes)))
+        return {"k": k.value, "e": e.value, "num_fixed": nf.value, "num_permutation_columns": np_.value, "forms": forms.value,
+                "bytes": nbytes.value}
+
+    def pk_ptr(self, pk, which: int, coset: int = 0):
+        """h2agg_pk_ptr: -> (the device address of the form `which` (PK_*), None for a form without columns; its columns).
+        Read-only; valid until the object goes."""
+        p, cols = C.c_void_p(), C.c_size_t()
+        self._check(self._lib.h2agg_pk_ptr(pk, which, coset, C.byref(p), C.byref(cols)))
+        return p.value, cols.value
+
+    def pk_quotient(self, pk, d_advice_ptr, d_instance_ptr, d_perm_z_ptr, d_lookup_z_ptr, d_lookup_ap_ptr, d_lookup_sp_ptr,
+                    challenges, theta: bytes, beta: bytes, gamma: bytes, y: bytes, delta: bytes, d_h_ptr):
+        """h2agg_pk_quotient: quotient_device with the fixed and sigma polynomials (and, with PK_COSETS, their values on every
+        coset) taken from the proving key; queued on the context's stream (no synchronisation, no read-back)"""
+        self._need32(theta=theta, beta=beta, gamma=gamma, y=y, delta=delta)
+        self._check(self._lib.h2agg_pk_quotient(self._ctx, pk, d_advice_ptr, d_instance_ptr, d_perm_z_ptr, d_lookup_z_ptr,
+                                                d_lookup_ap_ptr, d_lookup_sp_ptr, challenges, theta, beta, gamma, y, delta, d_h_ptr))
+
+    def pk_quotient_work_bytes(self, pk) -> int:
+        """h2agg_pk_quotient_work_bytes: the device work memory a pk_quotient call of this object holds in the context"""
+        out = C.c_size_t()
+        self._check(self._lib.h2agg_pk_quotient_work_bytes(pk, C.byref(out)))
+        return out.value
+
+    def pk_destroy(self, pk):
+        """h2agg_pk_destroy: waits for the context's stream and frees the object; the handle is cleared, a second call does
+        nothing"""
+        if pk:
+            self._lib.h2agg_pk_destroy(pk)
+            pk.value = None
 
     # ------------------------------------------------------------------ Fr column stores
     def columns_create(self, m: int, k: int) -> int:

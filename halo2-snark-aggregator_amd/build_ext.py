@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libh2agg.so")
 SOURCES = ["h2agg.hip"]
-DEPS = ["h2agg.hip", "hip_owners.hpp", "host.inc", "msm_run.inc", "chips_api.inc", "bases_api.inc", "msm_api.inc", "config_api.inc", "pairing_api.inc", "pairing.hpp", "fp.hpp", "fp_asm.inc", "g1.hpp", "batch_kernels.hpp", "sort_kernels.hpp", "fb_sort_kernels.hpp", "msm_kernels.hpp", "scalar_mul_kernels.hpp", "lp_kernels.hpp", "seg_msm_kernels.hpp", "seg_msm.inc", "g1_fft_kernels.hpp", "fr_host.inc", "params.inc", "fr_fft_kernels.hpp", "fr_fft.inc", "fr_chunk.hpp", "poly_kernels.hpp", "poly_open.inc", "shplonk_kernels.hpp", "shplonk.inc", "prod_kernels.hpp", "prod.inc", "lookup_kernels.hpp", "lookup.inc", "quotient_kernels.hpp", "quotient.inc", "keygen_kernels.hpp", "keygen.inc", "witness_kernels.hpp", "witness.inc", "columns_kernels.hpp", "columns.inc", "schema.hpp", "schema_shplonk.hpp", "tape_compile.hpp", "schema_api.inc", "comm.inc", "transcript.inc", "verifier.inc", "verify_run.inc", "poseidon_kernels.hpp", "poseidon_host.hpp", "poseidon_sponge_host.hpp", "poseidon_ifma_host.hpp", "hash_transcript_host.hpp", "hash_transcript_kernels.hpp", "../../include/h2agg.h"]
+DEPS = ["h2agg.hip", "hip_owners.hpp", "host.inc", "msm_run.inc", "chips_api.inc", "bases_api.inc", "msm_api.inc", "config_api.inc", "pairing_api.inc", "pairing.hpp", "fp.hpp", "fp_asm.inc", "g1.hpp", "batch_kernels.hpp", "sort_kernels.hpp", "fb_sort_kernels.hpp", "msm_kernels.hpp", "scalar_mul_kernels.hpp", "lp_kernels.hpp", "seg_msm_kernels.hpp", "seg_msm.inc", "g1_fft_kernels.hpp", "fr_host.inc", "params.inc", "fr_fft_kernels.hpp", "fr_fft.inc", "fr_chunk.hpp", "poly_kernels.hpp", "poly_open.inc", "shplonk_kernels.hpp", "shplonk.inc", "prod_kernels.hpp", "prod.inc", "lookup_kernels.hpp", "lookup.inc", "quotient_kernels.hpp", "quotient.inc", "keygen_kernels.hpp", "keygen.inc", "pk.inc", "witness_kernels.hpp", "witness.inc", "columns_kernels.hpp", "columns.inc", "schema.hpp", "schema_shplonk.hpp", "tape_compile.hpp", "schema_api.inc", "comm.inc", "transcript.inc", "verifier.inc", "verify_run.inc", "poseidon_kernels.hpp", "poseidon_host.hpp", "poseidon_sponge_host.hpp", "poseidon_ifma_host.hpp", "hash_transcript_host.hpp", "hash_transcript_kernels.hpp", "../../include/h2agg.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value"]
 
 

@@ -763,5 +763,6 @@ int h2agg_synchronize(h2agg_ctx* c) try {
 #include "lookup.inc"
 #include "quotient.inc"
 #include "keygen.inc"
+#include "pk.inc"
 #include "witness.inc"
 #include "columns.inc"

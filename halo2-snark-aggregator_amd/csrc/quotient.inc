@@ -194,40 +194,66 @@ const ph::HFr& qt_zeta() {
 // of the transforms' work array.  Only the existing route has a transform of size 2^(k + e), so only there the work array (and
 // the twiddle and shift tables, qt_queue) go by k + e.
 constexpr unsigned QT_MAX_K = FR_S;   // k + e: the two-adicity of Fr, 28 (w_ext = fft_omega(k + e) is a host scalar)
+// Who holds the key's columns (fixed, sigma, l_0 / l_last / l_blind).  QT_CALLER: the call — it builds the three Lagrange
+// columns and transforms all of them per coset into the one slab.  QT_PK: a proving key (pk.inc) holds the coefficients of the
+// three columns; the slab is as before, `lcoef` is gone.  QT_PK_COSETS: the proving key holds every coset's values, the slab
+// is the witness alone ([A + I + sets + 3 L][n]) and the fixed-form kernels read two bases (quotient_kernels.hpp).
+enum QtKeyMode { QT_CALLER = 0, QT_PK = 1, QT_PK_COSETS = 2 };
 struct QtLayout {
     uint32_t A, F, I, P, sets, L;
+    // columns of the slab; with QT_PK_COSETS fixed0, sigma0 and l0 are columns of the key's coset slab [F + P + 3][n] instead
     uint32_t fixed0, instance0, sigma0, z0, lz0, lap0, lsp0, l0, polys;
     size_t lcoef, acc, lin, ltab, ext, total, fft_work;
     unsigned e;
     bool split;
+    QtKeyMode mode;
+};
+// what a proving key lends to a call: the coefficients of l_0 / l_last / l_blind [3][n], and with QT_PK_COSETS the slabs
+// [2^e][F + P + 3][n]
+struct QtKey {
+    const uint8_t* lcoef;
+    const uint8_t* cosets;
 };
 
 // k + e <= 24: one inverse transform of size 2^(k + e) ends the call; above that, or after h2agg_quotient_configure(ctx, 1), the
 // coset-split ending, which transforms nothing larger than 2^k
 bool qt_split_route(unsigned k, unsigned e, int forced) { return forced != 0 || k + e > FFT_MAX_K; }
 
-QtLayout qt_layout(const h2agg_vk& vk, int forced_split) {
+QtLayout qt_layout(const h2agg_vk& vk, int forced_split, QtKeyMode mode = QT_CALLER) {
     QtLayout l;
+    l.mode = mode;
     l.A = vk.num_advice;
     l.F = (uint32_t)qe_nfixed(vk);
     l.I = vk.num_instance;
     l.P = (uint32_t)vk.perm_cols.size();
     l.sets = vk.n_sets;
     l.L = (uint32_t)vk.lookups.size();
-    l.fixed0 = l.A;
-    l.instance0 = l.fixed0 + l.F;
-    l.sigma0 = l.instance0 + l.I;
-    l.z0 = l.sigma0 + l.P;
-    l.lz0 = l.z0 + l.sets;
-    l.lap0 = l.lz0 + l.L;
-    l.lsp0 = l.lap0 + l.L;
-    l.l0 = l.lsp0 + l.L;
-    l.polys = l.l0 + 3;
+    if (mode == QT_PK_COSETS) {   // the slab: advice, instance, the Z of the sets, every lookup's Z, a', s'
+        l.instance0 = l.A;
+        l.z0 = l.instance0 + l.I;
+        l.lz0 = l.z0 + l.sets;
+        l.lap0 = l.lz0 + l.L;
+        l.lsp0 = l.lap0 + l.L;
+        l.polys = l.lsp0 + l.L;
+        l.fixed0 = 0;   // the key's coset slab: fixed, sigma, the three
+        l.sigma0 = l.F;
+        l.l0 = l.F + l.P;
+    } else {
+        l.fixed0 = l.A;
+        l.instance0 = l.fixed0 + l.F;
+        l.sigma0 = l.instance0 + l.I;
+        l.z0 = l.sigma0 + l.P;
+        l.lz0 = l.z0 + l.sets;
+        l.lap0 = l.lz0 + l.L;
+        l.lsp0 = l.lap0 + l.L;
+        l.l0 = l.lsp0 + l.L;
+        l.polys = l.l0 + 3;
+    }
     l.e = 0;
     while (((uint64_t)1 << l.e) < (uint64_t)vk.degree - 1) ++l.e;
     const size_t n = (size_t)1 << vk.k;
     l.lcoef = (size_t)l.polys * n;
-    l.acc = l.lcoef + 3 * n;
+    l.acc = l.lcoef + (mode == QT_CALLER ? 3 * n : 0);
     l.lin = l.acc + n;
     l.ltab = l.lin + n;
     l.ext = l.ltab + n;
@@ -255,9 +281,10 @@ struct QtSlabs {
 };
 
 int qt_check(h2agg_ctx* c, const h2agg_vk* vk, const QtSlabs& s, const uint8_t* challenges, const uint8_t* theta, const uint8_t* beta,
-             const uint8_t* gamma, const uint8_t* y, const uint8_t* delta, const void* h, QtLayout* l, QtScalars* sc) {
+             const uint8_t* gamma, const uint8_t* y, const uint8_t* delta, const void* h, QtLayout* l, QtScalars* sc,
+             QtKeyMode mode = QT_CALLER) {
     if (!vk) return fail(c, H2AGG_ERR_INVALID, "null verifying key");
-    *l = qt_layout(*vk, c->cfg_quotient_split);
+    *l = qt_layout(*vk, c->cfg_quotient_split, mode);
     if (const char* why = qt_shape_refusal(*vk, *l)) return fail(c, H2AGG_ERR_INVALID, why);
     if ((l->A && !s.advice) || (l->F && !s.fixed) || (l->I && !s.instance) || (l->P && (!s.sigma || !s.perm_z)) ||
         (l->L && (!s.lookup_z || !s.lookup_ap || !s.lookup_sp)) || !theta || !beta || !gamma || !y || !delta || !h)
@@ -271,7 +298,11 @@ int qt_check(h2agg_ctx* c, const h2agg_vk* vk, const QtSlabs& s, const uint8_t* 
 }
 
 // Queues the whole quotient: nothing synchronises unless a workspace has to grow (all of them grow before the first launch).
-int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalars& sc, const QtSlabs& in, uint8_t* d_h) {
+// key: null (l.mode QT_CALLER), or what the proving key of the call lends (in.fixed and in.sigma are then its coefficient
+// forms; with QT_PK_COSETS nothing reads them).
+int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalars& sc, const QtSlabs& in, uint8_t* d_h,
+             const QtKey* key = nullptr) {
+    const bool two = l.mode == QT_PK_COSETS;
     const unsigned k = vk.k, K = k + l.e;
     const size_t n = (size_t)1 << k, col = 32 * n;
     const uint32_t cosets = 1u << l.e;
@@ -318,7 +349,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     }
     uint8_t* w = (uint8_t*)c->qt_work.p;
     uint8_t* cos = w;
-    uint8_t* lcoef = w + 32 * l.lcoef;
+    const uint8_t* lcoef = key ? key->lcoef : w + 32 * l.lcoef;
     uint8_t* acc = w + 32 * l.acc;
     uint8_t* lin = w + 32 * l.lin;
     uint8_t* ltab = w + 32 * l.ltab;
@@ -334,7 +365,8 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     if (l.P) {
         std::vector<uint32_t> cols(l.P);
         for (uint32_t g = 0; g < l.P; ++g)
-            cols[g] = (vk.perm_cols[g].kind == 0 ? 0u : vk.perm_cols[g].kind == 1 ? l.fixed0 : l.instance0) + vk.perm_cols[g].index;
+            cols[g] = (vk.perm_cols[g].kind == 0 ? 0u : vk.perm_cols[g].kind == 1 ? l.fixed0 | (two ? QE_IN_KEY : 0u) : l.instance0) +
+                      vk.perm_cols[g].index;
         qe_put_queue(c, cols.data(), cols.size(), d_prog + cols_at);
         fr_table_launch(c, fft_omega(k), k, (uint8_t*)c->qt_tab.p);
     }
@@ -360,21 +392,27 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
     }
     phases.mark(FORWARD);
     const uint32_t u = (uint32_t)n - vk.blinding_factors - 1u;
-    hipLaunchKernelGGL(k_qe_lagrange_rows, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, lcoef, (uint32_t)n, u);
-    {
-        const FrFftSeg rows3 = {lcoef, 3};
-        TRY(fr_fft_queue_batch(c, &rows3, 1, 3, k, 1, nullptr, lcoef));
+    if (!key) {
+        uint8_t* rows = w + 32 * l.lcoef;
+        hipLaunchKernelGGL(k_qe_lagrange_rows, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, rows, (uint32_t)n, u);
+        const FrFftSeg rows3 = {rows, 3};
+        TRY(fr_fft_queue_batch(c, &rows3, 1, 3, k, 1, nullptr, rows));
     }
-    // ---- the sources of the slab's columns, in QtLayout's order: one transform launch per pass takes them all
-    const FrFftSeg src[FR_FFT_SEGS] = {{in.advice, l.A},    {in.fixed, l.F},     {in.instance, l.I},  {in.sigma, l.P}, {in.perm_z, l.sets},
-                                       {in.lookup_z, l.L},  {in.lookup_ap, l.L}, {in.lookup_sp, l.L}, {lcoef, 3}};
+    // ---- the sources of the slab's columns, in QtLayout's order: one transform launch per pass takes them all.  (A key with
+    // cosets: the witness alone — its segments without columns take no part.)
+    const FrFftSeg src[FR_FFT_SEGS] = {{in.advice, l.A},           {in.fixed, two ? 0 : l.F}, {in.instance, l.I},
+                                       {in.sigma, two ? 0 : l.P},  {in.perm_z, l.sets},       {in.lookup_z, l.L},
+                                       {in.lookup_ap, l.L},        {in.lookup_sp, l.L},       {lcoef, two ? 0u : 3u}};
+    const size_t key_slab = two ? col * ((size_t)l.F + l.P + 3) : 0;
     const dim3 rows((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
     ph::HFr s = zeta;
     for (uint32_t cs = 0; cs < cosets; ++cs, s = ph::mul(s, w_ext)) {
         if (cs) phases.mark(FORWARD);
-        TRY(fr_fft_queue_batch(c, src, FR_FFT_SEGS, l.polys, k, 0, &s, cos));
+        if (l.polys) TRY(fr_fft_queue_batch(c, src, FR_FFT_SEGS, l.polys, k, 0, &s, cos));
+        const uint8_t* kcos = two ? key->cosets + cs * key_slab : cos;   // the base of the key's columns on this coset
         QeCoset q;
         q.cos = cos;
+        q.key = kcos;
         q.acc_out = acc;
         hfr_words(ph::mul(sc.y, fr_radix()), q.yM);
         q.n = (uint32_t)n;
@@ -382,7 +420,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         const uint8_t* acc_in = nullptr;
         phases.mark(GATES);
         if (progs[0].m) {
-            qe_eval_queue(c, progs[0], d_prog + prog_at[0], false, k, cos, cos + l.fixed0 * col, cos + l.instance0 * col, &sc.y, nullptr,
+            qe_eval_queue(c, progs[0], d_prog + prog_at[0], false, k, cos, kcos + l.fixed0 * col, cos + l.instance0 * col, &sc.y, nullptr,
                           false, acc);
             acc_in = acc;
         }
@@ -411,7 +449,7 @@ int qt_queue(h2agg_ctx* c, const h2agg_vk& vk, const QtLayout& l, const QtScalar
         phases.mark(LOOKUPS);
         for (uint32_t j = 0; j < l.L; ++j) {
             for (int t = 0; t < 2; ++t)
-                qe_eval_queue(c, progs[1 + 2 * j + t], d_prog + prog_at[1 + 2 * j + t], false, k, cos, cos + l.fixed0 * col,
+                qe_eval_queue(c, progs[1 + 2 * j + t], d_prog + prog_at[1 + 2 * j + t], false, k, cos, kcos + l.fixed0 * col,
                               cos + l.instance0 * col, &sc.theta, nullptr, false, t ? ltab : lin);
             QeLookupArgs a;
             a.q = q;

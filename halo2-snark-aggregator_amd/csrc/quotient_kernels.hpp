@@ -154,15 +154,22 @@ __global__ void __launch_bounds__(BLOCK) k_qe_lagrange_rows(uint8_t* __restrict_
     fp_store<FrParams>(dst + 32 * (2 * (size_t)n + i), i > u ? one : Fr::zero());
 }
 
-// One coset's value slab cos[polys][n] (plain canonical: the transforms' output) and where the fixed-form kernels find their
-// columns in it.  Every index below is < polys (qt_layout, quotient.inc).
+// One coset's values (plain canonical: the transforms' output) and where the fixed-form kernels find their columns.  They
+// live in two bases: `cos`, the slab [polys][n] the call transformed for this coset, and `key`, the slab that holds the
+// key's own columns — sigma, l_0 / l_last / l_blind, and the fixed columns — on this coset.  A call without a proving key
+// transforms everything into one slab and passes key = cos; with the coset form of a proving key (pk.inc) `key` is that
+// object's slab [F + P + 3][n] of the coset, which no launch of the call writes.  A column place names its base: bit
+// QE_IN_KEY set reads `key`, the low bits are the column there.  Every index below is < the columns of its base (qt_layout,
+// quotient.inc).
+constexpr uint32_t QE_IN_KEY = 1u << 31;
 struct QeCoset {
     const uint8_t* cos;
+    const uint8_t* key;
     const uint8_t* acc_in;   // the y-fold so far (plain, [n]); null: 0
     uint8_t* acc_out;        // may be acc_in: a thread reads its own row before it writes it
     uint32_t yM[8];          // y R
     uint32_t n;
-    uint32_t l0;             // l_0, then l_last, then l_blind
+    uint32_t l0;             // in `key`: l_0, then l_last, then l_blind
 };
 
 FP_INLINE Fr qe_col(const uint8_t* cos, uint32_t col, uint32_t n, uint32_t row) {
@@ -176,12 +183,12 @@ struct QePermArgs {
     uint32_t gammaM[8];     // gamma R
     uint32_t deltaM[8];     // delta R
     uint32_t bsM[8];        // beta s R: times w^i R gives beta X R on the coset of s
-    const uint32_t* cols;   // [P]: the slab column of permutation column g
+    const uint32_t* cols;   // [P]: the place of permutation column g (QE_IN_KEY: a fixed column that lives in `key`)
     const uint8_t* w_lo;    // Montgomery w^i, i < 2^wT (fr_fft_table's pair, 2^k entries in all)
     const uint8_t* w_hi;
     uint32_t wT;
     uint32_t P, chunk, n_sets;   // n_sets = ceil(P / chunk) >= 1
-    uint32_t sigma0, z0;         // sigma_g at sigma0 + g, z_s at z0 + s
+    uint32_t sigma0, z0;         // sigma_g at sigma0 + g of `key`, z_s at z0 + s of `cos`
     uint32_t rot_last;           // n - (blinding_factors + 1)
 };
 
@@ -194,8 +201,9 @@ __global__ void __launch_bounds__(BLOCK) k_qe_permutation(const QePermArgs a) {
     if (i >= n) return;
     const uint32_t mask = n - 1u;
     const uint8_t* cos = a.q.cos;
+    const uint8_t* key = a.q.key;
     const Fr yM = fp_unpack<FrParams>(a.q.yM), one = Fr::one();
-    const Fr l0 = qe_col(cos, a.q.l0, n, i), ll = qe_col(cos, a.q.l0 + 1u, n, i), lb = qe_col(cos, a.q.l0 + 2u, n, i);
+    const Fr l0 = qe_col(key, a.q.l0, n, i), ll = qe_col(key, a.q.l0 + 1u, n, i), lb = qe_col(key, a.q.l0 + 2u, n, i);
     const Fr act = fp_sub<3, FrParams>(one, fp_add<FrParams>(ll, lb));   // < 4
     Fr acc = a.q.acc_in ? fp_to_mont<FrParams>(fp_load<FrParams>(a.q.acc_in + 32 * (size_t)i)) : Fr::zero();
     {
@@ -218,8 +226,9 @@ __global__ void __launch_bounds__(BLOCK) k_qe_permutation(const QePermArgs a) {
         const uint32_t g1 = (s + 1u) * a.chunk < a.P ? (s + 1u) * a.chunk : a.P;
 #pragma unroll 1
         for (uint32_t g = s * a.chunk; g < g1; ++g) {
-            const Fr t = fp_add<FrParams>(qe_col(cos, a.cols[g], n, i), gammaM);
-            const Fr sg = fp_mul<FrParams>(fp_load<FrParams>(cos + 32 * ((size_t)(a.sigma0 + g) * n + i)), betaR2);
+            const uint32_t place = a.cols[g];
+            const Fr t = fp_add<FrParams>(qe_col(place & QE_IN_KEY ? key : cos, place & ~QE_IN_KEY, n, i), gammaM);
+            const Fr sg = fp_mul<FrParams>(fp_load<FrParams>(key + 32 * ((size_t)(a.sigma0 + g) * n + i)), betaR2);
             left = fp_mul<FrParams>(left, fp_add<FrParams>(t, sg));
             right = fp_mul<FrParams>(right, fp_add<FrParams>(t, d));
             d = fp_mul<FrParams>(d, deltaM);
@@ -234,7 +243,7 @@ struct QeLookupArgs {
     uint32_t betaM[8], gammaM[8];   // beta R, gamma R
     const uint8_t* in;              // the theta-folds of the lookup's input and table expressions on this coset (plain, [n])
     const uint8_t* table;
-    uint32_t z, ap, sp;             // slab columns
+    uint32_t z, ap, sp;             // columns of `cos`
 };
 
 // One lookup's five expressions on one coset, folded behind acc_in (lookup.rs:34-119): l_0 (1 - z), l_last (z^2 - z),
@@ -244,8 +253,9 @@ __global__ void __launch_bounds__(BLOCK) k_qe_lookup(const QeLookupArgs a) {
     if (i >= n) return;
     const uint32_t mask = n - 1u;
     const uint8_t* cos = a.q.cos;
+    const uint8_t* key = a.q.key;
     const Fr yM = fp_unpack<FrParams>(a.q.yM), one = Fr::one();
-    const Fr l0 = qe_col(cos, a.q.l0, n, i), ll = qe_col(cos, a.q.l0 + 1u, n, i), lb = qe_col(cos, a.q.l0 + 2u, n, i);
+    const Fr l0 = qe_col(key, a.q.l0, n, i), ll = qe_col(key, a.q.l0 + 1u, n, i), lb = qe_col(key, a.q.l0 + 2u, n, i);
     const Fr act = fp_sub<3, FrParams>(one, fp_add<FrParams>(ll, lb));   // < 4
     Fr acc = a.q.acc_in ? fp_to_mont<FrParams>(fp_load<FrParams>(a.q.acc_in + 32 * (size_t)i)) : Fr::zero();
     const Fr betaM = fp_unpack<FrParams>(a.betaM), gammaM = fp_unpack<FrParams>(a.gammaM);

@@ -689,6 +689,113 @@ def resident_shplonk_prove(eng, g_handle: int, polys: ColumnView, queries, point
     return [evals[32 * q:32 * q + 32] for q in range(len(queries))], h1, h2
 
 
+# ---------------------------------------------------------------------------------------------- proving key on the device
+def pk_bytes(eng, vk, cosets: bool = True) -> int:
+    """the device memory a ProvingKey of this verifying key holds, in bytes (include/h2agg.h)"""
+    from . import PK_COSETS
+    return eng.pk_bytes(vk, PK_COSETS if cosets else 0)
+
+
+class ProvingKey:
+    """What a prover of one circuit keeps on the device between proofs (h2agg_pk_create): the fixed and sigma columns in Lagrange
+    and coefficient form, l_0 / l_last / l_blind, and with cosets=True their values on every coset of the extended domain, so
+    that the quotient transforms the witness alone.  A context manager, freed on exit or by close(); the verifying key and
+    the engine must outlive it."""
+
+    def __init__(self, eng, vk, handle):
+        self.eng, self.vk, self._pk = eng, vk, handle
+        self.info = eng.pk_info(handle)
+
+    @classmethod
+    def from_lagrange(cls, eng, vk, fixed_cols, sigma_cols, cosets: bool = True) -> "ProvingKey":
+        """fixed_cols / sigma_cols: lists of 2^k-element columns in Lagrange form (sigma_cols: permutation_key's first result)"""
+        from . import PK_COSETS
+        sh = vk.shape
+        k = sh["k"]
+        return cls(eng, vk, eng.pk_create(vk, _slab(fixed_cols, sh["num_fixed"], k, "fixed"),
+                                          _slab(sigma_cols, sh["num_permutation_columns"], k, "sigma"), PK_COSETS if cosets else 0))
+
+    @classmethod
+    def from_views(cls, eng, vk, fixed: ColumnView, sigma: ColumnView, cosets: bool = True) -> "ProvingKey":
+        """the same from views of stores that hold the Lagrange columns (None where the key has no column of the kind); the
+        stores are not written and may go once this returns"""
+        from . import PK_COSETS
+        sh = vk.shape
+        ptrs = [_key_view(v, count, sh["k"], what) for v, count, what in ((fixed, sh["num_fixed"], "fixed"),
+                                                                          (sigma, sh["num_permutation_columns"], "sigma"))]
+        return cls(eng, vk, eng.pk_create_resident(vk, *ptrs, PK_COSETS if cosets else 0))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self._pk:
+            self.eng.pk_destroy(self._pk)
+
+    handle = property(lambda self: self._pk)
+    cosets = property(lambda self: bool(self.info["forms"] & 1))
+
+    def ptr(self, which: int, coset: int = 0):
+        """-> (device address or None, columns) of one form (PK_FIXED_LAGRANGE .. PK_COSET of the package)"""
+        return self.eng.pk_ptr(self._pk, which, coset)
+
+    def work_bytes(self) -> int:
+        return self.eng.pk_quotient_work_bytes(self._pk)
+
+    def _witness_counts(self):
+        sh = self.vk.shape
+        chunk, nl = sh["degree"] - 2, len(sh["lookups"])
+        nsets = (sh["num_permutation_columns"] + chunk - 1) // chunk
+        return (("advice", sh["num_advice"]), ("instance", sh["num_instance"]), ("perm_z", nsets), ("lookup_z", nl),
+                ("lookup_ap", nl), ("lookup_sp", nl))
+
+    def resident_quotient(self, advice, instance, perm_z, lookup_z, lookup_ap, lookup_sp, challenges, theta: bytes, beta: bytes,
+                          gamma: bytes, y: bytes, delta: bytes, out: ColumnView) -> ColumnView:
+        """h2agg_pk_quotient over views of stores that hold the witness polynomials in coefficient form (None where the key has
+        none of the kind): the degree - 1 pieces into `out`, queued on the context's stream -> out"""
+        sh = self.vk.shape
+        k = sh["k"]
+        views = (advice, instance, perm_z, lookup_z, lookup_ap, lookup_sp)
+        ptrs = [_key_view(v, count, k, what) for v, (what, count) in zip(views, self._witness_counts())]
+        if out is None or out.count != sh["degree"] - 1 or out.k != k:
+            raise ValueError("out must be a view of %d columns of 2^%d rows" % (sh["degree"] - 1, k))
+        if any(v is not None and count and out.overlaps(v) for v, (_w, count) in zip(views, self._witness_counts())):
+            raise ValueError("out overlaps an input")
+        self.eng.pk_quotient(self._pk, *ptrs, _challenges(self.vk, challenges), theta, beta, gamma, y, delta, out.ptr())
+        return out
+
+    def quotient_pieces(self, advice, instance, perm_z, lookup_z, lookup_ap, lookup_sp, challenges, theta: bytes, beta: bytes,
+                        gamma: bytes, y: bytes, delta: bytes):
+        """quotient_pieces with the key's polynomials taken from this object: lists of witness polynomials in coefficient form
+        on the host -> the list of degree - 1 pieces.  Staged through a store that lives for the call."""
+        sh = self.vk.shape
+        k, pieces = sh["k"], sh["degree"] - 1
+        lists = (advice, instance, perm_z, lookup_z, lookup_ap, lookup_sp)
+        slabs = [_slab(cols, count, k, what) for cols, (what, count) in zip(lists, self._witness_counts())]
+        total = sum(count for _w, count in self._witness_counts())
+        with ColumnStore(self.eng, total + pieces, k) as store:
+            views, at = [], 0
+            for slab, (_what, count) in zip(slabs, self._witness_counts()):
+                views.append(store.view(at, count) if count else None)
+                if count:
+                    store.write(at, slab, count)
+                at += count
+            out = self.resident_quotient(*views, challenges, theta, beta, gamma, y, delta, store.view(total, pieces))
+            return out.read()
+
+
+def _key_view(view, count: int, k: int, what: str):
+    """the device address of a view that must hold `count` columns of 2^k rows; None where the key has none of the kind"""
+    if count == 0:
+        return None
+    if view is None or view.count != count or view.k != k:
+        raise ValueError("%s must be a view of %d columns of 2^%d rows" % (what, count, k))
+    return view.ptr()
+
+
 def _same_shape(views, what: str):
     first = views[0]
     if any(v.count != first.count or v.k != first.k for v in views):

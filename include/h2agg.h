@@ -1143,6 +1143,84 @@ int h2agg_columns_shplonk_begin(h2agg_ctx* ctx, uint64_t g_handle, uint64_t src,
                                 size_t nq, const uint8_t* points, size_t npoints, const uint8_t* evals, const uint8_t y[32],
                                 const uint8_t v[32], uint8_t h1_aff[64], h2agg_shplonk** out);
 
+/* ---- Proving key on the device: the forms a prover of one circuit keeps between proofs ---------------------------------------
+ * Stands for: what halo2_proofs' ProvingKey caches — fixed_values / fixed_polys / fixed_cosets, the permutation's permutations /
+ * polys / cosets, and l0, l_last, l_active_row — recalled from upstream, not pinned, like the blocks above; what the entry
+ * points compute is this definition.  None of it depends on a witness or a challenge, and h2agg_quotient* recomputes all of
+ * it in every call: the three Lagrange columns once, the transforms of the key's columns on every coset.  A prover that proves
+ * one circuit many times (the aggregator's own case) builds the object once and calls h2agg_pk_quotient.
+ *
+ * Elements are canonical 32-byte little-endian Fr.  n = 2^k is the key's, F = its fixed commitments, P = its permutation
+ * columns; e, w_ext, zeta, u, l_0, l_last, l_blind are those of h2agg_quotient; coset c' < 2^e is the shift s = zeta w_ext^c'.
+ *
+ * h2agg_pk_create — fixed[F][n] and sigma[P][n] are host slabs in LAGRANGE form (a slab whose count is zero may be NULL); sigma
+ *   is what h2agg_permutation_sigmas writes to sigma_lagrange.  Synchronous: when it returns every form is complete in device
+ *   memory that the object owns.  The object refers to ctx and vk, which must outlive it.  forms: 0 or H2AGG_PK_COSETS.
+ * h2agg_pk_create_resident — the same with the two slabs in DEVICE memory (for example h2agg_columns_ptr of a store); the
+ *   buffer rules of h2agg_fr_fft_device apply, the inputs are not written, and it still returns only when the forms are complete.
+ * The forms:
+ *   always  the Lagrange form as given;
+ *   always  the coefficient form: one batched inverse transform, byte for byte what h2agg_fr_fft_batch (inverse, no shift)
+ *           gives — for sigma what h2agg_permutation_sigmas writes to sigma_coeff;
+ *   always  l_0, l_last, l_blind in coefficient form: the inverse transforms of the rows (i == 0), (i == u), (i > u);
+ *   with H2AGG_PK_COSETS, for every coset c' one slab [F + P + 3][n]: the values on {s w^i} of the fixed polynomials, then the
+ *           sigma polynomials, then l_0, l_last, l_blind — one batched forward transform at shift s, every column byte for
+ *           byte what h2agg_fr_fft_device gives for it.
+ *   Without that bit the object is the low-memory key: h2agg_pk_quotient transforms the key's columns per coset from the
+ *   coefficient forms, as h2agg_quotient_device does, and saves only the per-call construction of the three columns.
+ * h2agg_pk_bytes — the device memory the object will hold:
+ *       32 x (2 (F + P) n + 3 n + [H2AGG_PK_COSETS] (F + P + 3) n 2^e)  bytes
+ *   (k = 24, F + P = 12, e = 2: 12 + 1.5 + 30 GiB).  Needs no context and no device, like h2agg_quotient_work_bytes, and
+ *   refuses the same shapes.
+ * h2agg_pk_info — k, e, F, P, forms and the bytes held; every output may be NULL.
+ * h2agg_pk_ptr — a read-only device pointer to one form and its number of columns, for the _device entry points:
+ *   H2AGG_PK_FIXED_LAGRANGE [F][n] (h2agg_vk_expressions_eval_device, the witness check), H2AGG_PK_SIGMA_LAGRANGE [P][n]
+ *   (h2agg_permutation_product_device), H2AGG_PK_FIXED_COEFF / H2AGG_PK_SIGMA_COEFF (h2agg_fr_poly_eval_device, the multiopen
+ *   slabs, h2agg_quotient_device), H2AGG_PK_LAGRANGE_COEFF [3][n]: l_0, l_last, l_blind, and H2AGG_PK_COSET: the slab
+ *   [F + P + 3][n] of coset `coset` (ignored for the other forms).  A form without columns answers NULL and 0 columns.
+ * h2agg_pk_quotient — h2agg_quotient_device with the key's polynomials taken from the object: device memory in and out, queued
+ *   on the context's stream, no synchronisation and no read-back (a workspace that has to grow drains the device first).
+ *   d_h is byte for byte what h2agg_quotient_device writes for the same witness polynomials and the object's FIXED_COEFF and
+ *   SIGMA_COEFF slabs, on both endings (k + e <= 24; the coset-split ending above that and under h2agg_quotient_configure).
+ *   With H2AGG_PK_COSETS nothing moves a key column, per coset or per call: the kernels read the object's coset slabs in
+ *   place, and the one batched transform per coset takes the witness alone.
+ *   Work memory, kept in the context, with H2AGG_PK_COSETS: (A + I + sets + 3 L + 3) n + 2^(k+e) elements (the witness slab of
+ *   a coset, the fold column, a lookup's two theta-folds, the extended evaluations or the cosets' inverse transforms) and the
+ *   transforms' work array by h2agg_fr_fft_batch's rule for A + I + sets + 3 L columns of n, raised to 2^(k+e) elements on the
+ *   default ending.  Without the bit: h2agg_quotient's two sums less the three coefficient columns.  A key with no witness
+ *   column at all is legal and transforms nothing per coset.
+ *   h2agg_last_phases (debug key "phases") gives the five names of h2agg_quotient_device; forward is the witness transforms.
+ * h2agg_pk_quotient_work_bytes — that work memory in bytes, on the route the key takes by its size (as
+ *   h2agg_quotient_work_bytes).
+ * h2agg_pk_destroy — waits for the context's stream, then frees.  NULL does nothing.
+ * Refusals, the context stays usable after each and create leaves *out = NULL: a shape h2agg_quotient_device refuses (k > 24,
+ *   k + e > 28, degree < 3 with permutation columns), a null required buffer, unknown bits in forms, a key used with another
+ *   context, an unknown `which`, coset >= 2^e or H2AGG_PK_COSET asked of a key built without the bit: H2AGG_ERR_INVALID.  An
+ *   element >= r in fixed or sigma: H2AGG_ERR_NONCANONICAL from create.  A scalar >= r: H2AGG_ERR_NONCANONICAL from the call.  A
+ *   witness element >= r: H2AGG_ERR_NONCANONICAL through the context's device status, as for h2agg_quotient_device.  Out of
+ *   memory: H2AGG_ERR_NOMEM, with nothing left allocated. */
+#define H2AGG_PK_COSETS 1u
+#define H2AGG_PK_FIXED_LAGRANGE 0
+#define H2AGG_PK_SIGMA_LAGRANGE 1
+#define H2AGG_PK_FIXED_COEFF 2
+#define H2AGG_PK_SIGMA_COEFF 3
+#define H2AGG_PK_LAGRANGE_COEFF 4
+#define H2AGG_PK_COSET 5
+typedef struct h2agg_pk h2agg_pk;
+int h2agg_pk_create(h2agg_ctx* ctx, const h2agg_vk* vk, const uint8_t* fixed, const uint8_t* sigma, unsigned forms, h2agg_pk** out);
+int h2agg_pk_create_resident(h2agg_ctx* ctx, const h2agg_vk* vk, const void* d_fixed, const void* d_sigma, unsigned forms,
+                             h2agg_pk** out);
+int h2agg_pk_bytes(const h2agg_vk* vk, unsigned forms, size_t* bytes_out);
+int h2agg_pk_info(const h2agg_pk* pk, unsigned* k_out, unsigned* e_out, size_t* fixed_out, size_t* sigma_out, unsigned* forms_out,
+                  size_t* bytes_out);
+int h2agg_pk_ptr(const h2agg_pk* pk, int which, size_t coset, const void** d_ptr_out, size_t* columns_out);
+int h2agg_pk_quotient(h2agg_ctx* ctx, const h2agg_pk* pk, const void* d_advice, const void* d_instance, const void* d_perm_z,
+                      const void* d_lookup_z, const void* d_lookup_ap, const void* d_lookup_sp, const uint8_t* challenges,
+                      const uint8_t theta[32], const uint8_t beta[32], const uint8_t gamma[32], const uint8_t y[32],
+                      const uint8_t delta[32], void* d_h);
+int h2agg_pk_quotient_work_bytes(const h2agg_pk* pk, size_t* bytes_out);
+void h2agg_pk_destroy(h2agg_pk* pk);
+
 /* ---- Fr expression tape ------------------------------------------------------
  * A straight-line program over Fr, run on the device by the interpreter EvaluationQuerySchema::eval records into:
  * registers 0 .. nconst-1 are the inputs (canonical, 32 B each), register nconst + k is the result of op k;

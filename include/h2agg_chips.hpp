@@ -382,4 +382,63 @@ inline size_t quotient_work_bytes(const h2agg_vk* vk) {
     return bytes;
 }
 
+// The proving key on the device (include/h2agg.h "Proving key on the device"): the fixed and sigma columns in Lagrange and
+// coefficient form, l_0 / l_last / l_blind, and with cosets their values on every coset of the extended domain.  RAII over
+// h2agg_pk_create[_resident] / _destroy; move-only; must not outlive its Gpu or the verifying key.  Build it once per circuit
+// and call quotient() once per proof.
+class ProvingKey {
+  public:
+    // fixed / sigma: host slabs [F][2^k] / [P][2^k] in Lagrange form (null where the key has none); synchronous
+    ProvingKey(const Gpu& g, const h2agg_vk* vk, const uint8_t* fixed, const uint8_t* sigma, bool cosets = true) : g_(&g) {
+        g.check(h2agg_pk_create(g.ctx(), vk, fixed, sigma, cosets ? H2AGG_PK_COSETS : 0u, &pk_));
+    }
+    // the same from device memory (Columns::ptr()); the slabs are not written
+    struct Resident {};
+    ProvingKey(const Gpu& g, const h2agg_vk* vk, Resident, const void* d_fixed, const void* d_sigma, bool cosets = true) : g_(&g) {
+        g.check(h2agg_pk_create_resident(g.ctx(), vk, d_fixed, d_sigma, cosets ? H2AGG_PK_COSETS : 0u, &pk_));
+    }
+    ~ProvingKey() { h2agg_pk_destroy(pk_); }
+    ProvingKey(ProvingKey&& o) noexcept : g_(o.g_), pk_(o.pk_) { o.pk_ = nullptr; }
+    ProvingKey& operator=(ProvingKey&& o) noexcept {
+        if (this != &o) {
+            h2agg_pk_destroy(pk_);
+            g_ = o.g_, pk_ = o.pk_;
+            o.pk_ = nullptr;
+        }
+        return *this;
+    }
+    ProvingKey(const ProvingKey&) = delete;
+    ProvingKey& operator=(const ProvingKey&) = delete;
+    const h2agg_pk* handle() const { return pk_; }
+    // device memory the object holds / work memory a quotient() call holds in the context, in bytes
+    size_t bytes() const {
+        size_t b = 0;
+        g_->check(h2agg_pk_info(pk_, nullptr, nullptr, nullptr, nullptr, nullptr, &b));
+        return b;
+    }
+    size_t quotient_work_bytes() const {
+        size_t b = 0;
+        g_->check(h2agg_pk_quotient_work_bytes(pk_, &b));
+        return b;
+    }
+    // a read-only device pointer to one form (H2AGG_PK_FIXED_LAGRANGE .. H2AGG_PK_COSET) and its number of columns
+    std::pair<const void*, size_t> ptr(int which, size_t coset = 0) const {
+        const void* p = nullptr;
+        size_t columns = 0;
+        g_->check(h2agg_pk_ptr(pk_, which, coset, &p, &columns));
+        return {p, columns};
+    }
+    // h2agg_pk_quotient: witness polynomials in coefficient form and the pieces in device memory; queued
+    void quotient(const void* d_advice, const void* d_instance, const void* d_perm_z, const void* d_lookup_z, const void* d_lookup_ap,
+                  const void* d_lookup_sp, const uint8_t* challenges, const Scalar& theta, const Scalar& beta, const Scalar& gamma,
+                  const Scalar& y, const Scalar& delta, void* d_h) const {
+        g_->check(h2agg_pk_quotient(g_->ctx(), pk_, d_advice, d_instance, d_perm_z, d_lookup_z, d_lookup_ap, d_lookup_sp, challenges,
+                                    theta.data(), beta.data(), gamma.data(), y.data(), delta.data(), d_h));
+    }
+
+  private:
+    const Gpu* g_;
+    h2agg_pk* pk_ = nullptr;
+};
+
 }  // namespace h2agg_chips
